@@ -21,7 +21,7 @@ large linears can gain. --shard-policy size / all / none override the measuremen
 Total work is fixed as P grows ("strong" scaling); value counts the whole model's bytes once
 per step.
 
-The line also carries config5_70b: BASELINE config 5's Llama-3-70B linear step (80 layers,
+A --full line also carries config5_70b: BASELINE config 5's Llama-3-70B linear step (80 layers,
 43.4 GB of int4 weights per token). At P = 1 every linear runs whole on the one GPU (the 1-GPU
 anchor of the 1/2/4/8 curve); at P > 1 under the Megatron plan (pairs + head gather) and, beside
 it as north_star_plan, the north star's plan (every linear column-sharded + RCCL all-gather),
@@ -29,9 +29,19 @@ it as north_star_plan, the north star's plan (every linear column-sharded + RCCL
 collectives-only times beside the whole step (--no-config5 skips it). --model 70b makes the 70B
 the headline instead; the default headline stays the 8B, so the N = 1 point equals BENCH.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) builds the step, warms it up, times the N
+steps and prints the headline line: value, ms_per_step, linear_steps_per_s, config, ranks.
+--dump-outputs DIR also writes what the last timed step computed, every linear's output row as
+DIR/<linear name>.npy (float32); weights and activations are seeded, so two builds run with the
+same arguments can be compared output for output. Everything from north_star on in the list that
+follows is measured only with --full, each in a run of its own after the timed steps; the --no-*
+options trim a --full run.
+
 Reported (one JSON line, rank 0):
   value        = algorithmic bytes per step x steps / wall time  (GB/s, whole job)
+  ms_per_step  = wall time of the timed steps / steps, in milliseconds
   linear_steps_per_s = steps / wall time (linears only; the model's decode rate is e2e_decode)
+ with --full also:
   north_star   = BASELINE's per-launch target shape (int4 g32 M=1 4096x4096, wo at 8B): us per
                  launch inside a replayed graph of that shape's launches, and its fraction of
                  8 TB/s (target 0.70, reported unmet while it is), split into the kernel's own
@@ -934,8 +944,10 @@ class LinearStep:
             packed, sz = make_int4_weight(n_loc, k_loc, g,
                                           seed=1000 * i + (rank if kind != "whole" else 0),
                                           device=device)
-            if k_loc not in self.xs:
-                self.xs[k_loc] = torch.randn(1, k_loc, device=device, dtype=torch.bfloat16)
+            if k_loc not in self.xs:  # seeded like the weights: the same inputs in every run
+                gen = torch.Generator(device=device).manual_seed(500000 + k_loc)
+                self.xs[k_loc] = torch.randn(1, k_loc, generator=gen, device=device,
+                                             dtype=torch.bfloat16)
             y_loc = torch.empty(n_loc, device=device, dtype=torch.bfloat16)  # M = 1 row
             y_full = (torch.empty(N, device=device, dtype=torch.bfloat16) if kind == "gather"
                       else y_loc)
@@ -1233,6 +1245,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--group-size", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can carry "
+                         "(roofline, per-shape and north-star figures, the reference's GPU kernel, "
+                         "prefill_mfma, config2_shapes, int8wo_m1, the HBM ceilings, the unfused "
+                         "layout, config5_70b, e2e_decode, cpu_baseline); the --no-* options "
+                         "below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed, every linear's output row, as "
+                         "DIR/<linear name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-reference-gpu", action="store_true",
@@ -1312,13 +1333,83 @@ def main():
     # ---- build the sharded weights, inputs and outputs (all resident in HBM) ----
     st = LinearStep(lins, shard_kinds(lins, P, g, policy, calib, args.shard_min_elems), P, rank,
                     g, device, rehearsal)
-    plan, xs, bytes_per_step, stream = st.plan, st.xs, st.bytes_per_step, st.stream
-    step, capture = st.step, st.capture
+    bytes_per_step, n_launches = st.bytes_per_step, len(st.plan)
 
     graph = None if args.no_graph else st.try_capture()
-    run = graph.replay if graph is not None else step
+    run = graph.replay if graph is not None else st.step
     ms = st.wall_ms(run, args.steps, args.warmup)
     elapsed = ms * args.steps * 1e-3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(st, args.dump_outputs)
+
+    rec = {
+        "metric": f"int4 WO linear GB/s + tokens/s vs CPU dequant path, {model_name} shapes M=1",
+        "value": round(bytes_per_step * args.steps / elapsed / 1e9, 2),
+        "unit": "GB/s",
+        # linears only (one step = every int4 linear of one decoded token); the model's
+        # real decode rate (attention, norms, argmax included) is e2e_decode's (--full)
+        "linear_steps_per_s": round(args.steps / elapsed, 2),
+        "n_gpus": P,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic (random-init nn.Linear weights quantized int4 g32; N(0,1) bf16 activations)",
+        "config": {
+            "workload": f"{model_name} int4 g{g} weight-only linears, M=1 decode: "
+                        + workload_desc(cfg, not args.no_fuse_w13)
+                        + f" ({n_launches} GEMV launches/step)",
+            "model": f"{model_name} (linears only)",
+            "global_batch": 1,
+            "seq_len": 1,
+            "group_size": g,
+            "bytes_per_step": bytes_per_step,
+            "parallelism": parallelism_desc(st, policy) if P > 1 else "single-gpu",
+            "hip_graph": graph is not None,
+        },
+        "ranks": census,
+    }
+    if args.full:
+        # everything beyond the headline figure; it frees the step's weights on its way
+        rec.update(measure_full(args, st, graph, rec["value"], cfg, rank, device, rehearsal,
+                                policy))
+    if calib:
+        rec["shard_calibration_us"] = {
+            ("x".join(str(v) for v in key[1:3]) + "->" + "x".join(str(v) for v in key[3:])
+             if key[0] == "pair" else f"{key[0]}x{key[1]}"): v for key, v in calib.items()}
+    if rank == 0:
+        print(json.dumps(rec), flush=True)
+
+    if P > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(st, out_dir):
+    """--dump-outputs: what the last timed step left in every linear's output buffer (what a caller
+    of the step receives: the full row for a whole or gathered linear, this rank's part for a
+    linear of a Megatron pair), one float32 .npy per linear, named as in llama_linears (6 MB
+    in all at 8B, 27 MB at 70B)."""
+    import numpy as np
+
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for (name, _n, _k, _packed, _sz, _y_loc, y_full, _kind) in st.plan:
+        np.save(os.path.join(out_dir, f"{name}.npy"), y_full.float().cpu().numpy())
+
+
+def measure_full(args, st, graph, value, cfg, rank, device, rehearsal, policy):
+    """--full: the measurements and checks beside the headline figure, each a run of its own after
+    the timed steps (module docstring, "Reported"). Returns the keys they add to the line. The 8B
+    step's weights are released before config5_70b builds its own, so `st` is spent afterwards."""
+    from torchao import _lib
+
+    g, P = st.g, st.P
+    plan, xs, bytes_per_step = st.plan, st.xs, st.bytes_per_step
+    step, capture = st.step, st.capture
+    run = graph.replay if graph is not None else step
 
     # ---- roofline: GEMV-only graph replayed back to back, GPU events on the replay stream ----
     groof = graph if (graph is not None and P == 1) else None
@@ -1418,8 +1509,7 @@ def main():
             and graph is not None:
         unfused = unfused_record(cfg, g, device, args.steps)
     config5 = None
-    n_launches, has_graph = len(plan), graph is not None
-    par_desc = parallelism_desc(st, policy) if P > 1 else "single-gpu"
+    n_launches = len(plan)
     if args.model == "8b" and not args.no_config5:
         # release the 8B step's weights first (the 70B step needs 43 GB / P per rank): the
         # plan / inputs / graphs bound here hold them too, so drop those references before
@@ -1436,36 +1526,9 @@ def main():
     if rank == 0 and P == 1 and not args.no_cpu_baseline and args.model == "8b":
         cpu = cpu_baseline(cfg, g)
 
+    rec = {}
     if rank == 0:
         rec = {
-            "metric": f"int4 WO linear GB/s + tokens/s vs CPU dequant path, {model_name} shapes M=1",
-            "value": round(bytes_per_step * args.steps / elapsed / 1e9, 2),
-            "unit": "GB/s",
-            # linears only (one step = every int4 linear of one decoded token); the model's
-            # real decode rate (attention, norms, argmax included) is e2e_decode's
-            "linear_steps_per_s": round(args.steps / elapsed, 2),
-            "n_gpus": P,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "bf16",
-            "data": "synthetic (random-init nn.Linear weights quantized int4 g32; N(0,1) bf16 activations)",
-            "config": {
-                "workload": f"{model_name} int4 g{g} weight-only linears, M=1 decode: "
-                            + workload_desc(cfg, not args.no_fuse_w13)
-                            + f" ({n_launches} GEMV launches/step)",
-                "model": f"{model_name} (linears only)",
-                "global_batch": 1,
-                "seq_len": 1,
-                "group_size": g,
-                "bytes_per_step": bytes_per_step,
-                "parallelism": par_desc,
-                "hip_graph": has_graph,
-            },
-            "ranks": census,
             "roofline": {
                 "bound": "hbm",
                 "kernel": "int4wo_gemv_kernel",
@@ -1530,7 +1593,7 @@ def main():
         if ref_gpu is not None:
             rec["reference_gpu"] = ref_gpu
             if "value" in ref_gpu:
-                rec["speedup_vs_reference_gpu"] = round(rec["value"] / ref_gpu["value"], 2)
+                rec["speedup_vs_reference_gpu"] = round(value / ref_gpu["value"], 2)
         if prefill is not None:
             rec["prefill_mfma"] = prefill
         if config2 is not None:
@@ -1541,16 +1604,9 @@ def main():
             rec["e2e_decode"] = e2e_decode()
         if comm_ms is not None:
             rec["collectives_ms_per_step"] = round(comm_ms, 4)
-        if calib:
-            rec["shard_calibration_us"] = {
-                ("x".join(str(v) for v in key[1:3]) + "->" + "x".join(str(v) for v in key[3:])
-                 if key[0] == "pair" else f"{key[0]}x{key[1]}"): v for key, v in calib.items()}
         if cpu is not None:
-            rec["speedup_vs_cpu_baseline"] = round(rec["value"] / cpu["value"], 1)
-        print(json.dumps(rec), flush=True)
-
-    if P > 1:
-        dist.destroy_process_group()
+            rec["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 1)
+    return rec
 
 
 if __name__ == "__main__":

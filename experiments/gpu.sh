@@ -36,10 +36,10 @@ run_one() {
       local rc=$?; head -c 600 $O/bench_$tag.json; echo; return $rc ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag \
-        -o bench -- python3 bench.py --no-cpu-baseline --no-reference-gpu --no-e2e --no-extras \
+        -o bench -- python3 bench.py --full --no-cpu-baseline --no-reference-gpu --no-e2e --no-extras \
         --no-config5 > $O/bench_prof_$tag.json 2> $O/bench_prof_$tag.err || return $?
       timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_$tag -o pmc \
-        -- python3 bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --no-reference-gpu \
+        -- python3 bench.py --full --no-graph --steps 2 --warmup 1 --no-cpu-baseline --no-reference-gpu \
         --no-prefill --no-e2e --no-extras --no-config5 > $O/bench_pmc_$tag.json \
         2> $O/bench_pmc_$tag.err || return $?
       python3 experiments/trace_summary.py "$(find $O/prof_$tag -name "*kernel_trace.csv" | head -1)" \
@@ -69,7 +69,7 @@ run_one() {
     rehearse)  # rehearse TAG P: bench.py's P-rank path on this one GPU (gloo, all ranks on card 0)
       local P=$1
       timeout -k 10 1100 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$P" \
-        --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus "$P" --backend gloo \
+        --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus "$P" --backend gloo \
         --steps 3 --warmup 1 > $O/rehearsal_$tag.jsonl 2> $O/rehearsal_$tag.err
       local rc=$?; grep '^{' $O/rehearsal_$tag.jsonl | head -c 800; echo; return $rc ;;
     *)

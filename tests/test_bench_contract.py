@@ -1,5 +1,5 @@
 """The bench line's contract, checked on the committed final-library line (profiles/r6af_bench.json,
-a default `python bench.py` run on an MI355X): the driver's keys and types, the roofline and
+a `python bench.py --full` run on an MI355X): the driver's keys and types, the roofline and
 cpu_baseline objects, and their internal arithmetic (frac = achieved / peak, achieved = algorithmic
 bytes / kernel time). CPU only: it reads JSON."""
 
