@@ -133,6 +133,37 @@ int tao_int8wo_linear_bf16(const uint16_t* x, const int8_t* w, const uint16_t* s
                            const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                            void* stream);
 
+/* ---- float8 (e4m3fn) weight-only ------------------------------------------------------------ */
+
+/* y[M][N] = bf16( (sum_k x[m][k] * f(w[n][k])) * scale[n] ) (+ bias[n], rounded to bf16 again),
+ * w uint8 [N][K] = OCP e4m3fn codes (torch.float8_e4m3fn), f their exact decode, scale f32 [N]
+ * per output row; the sum and the scale product are formed in fp32. The scale is applied once
+ * per output; the reference rounds bf16(f(w) * scale) per weight, which is the same number
+ * whenever that product is a bf16 number (e.g. power-of-two scales) and has more roundings
+ * otherwise. A NaN code (0x7F / 0xFF) makes its output column NaN.
+ * Replaces F.linear(x, weight.dequantize(), bias) in _linear_fp_act_fp8_weight_impl at
+ * torchao/dtypes/floatx/float8_layout.py:391-396, which rebuilds a bf16 copy of W on every call.
+ * K % 32 == 0; M >= 0 (M == 0 is a no-op). x, w: 16-B aligned. bias may be NULL. */
+int tao_fp8wo_linear_bf16(const uint16_t* x, const uint8_t* w, const float* scale,
+                          const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                          void* stream);
+
+/* Fused per-row e4m3fn weight quantizer (Float8WeightOnlyConfig version 1 on bf16 weights), one
+ * pass per row of w [rows][K] bf16: scale[r] = float(bf16(amax|w[r]| / 448)) (the bf16 rounding is
+ * the one the reference's division of the bf16 amax tensor makes; the value is kept in fp32),
+ * q = e4m3fn_rne(clamp(float(w) / scale[r], -448, 448)), both true divisions. No eps, as in the
+ * reference: an all-zero row gets scale 0.0 and NaN codes. K % 8 == 0. Replaces
+ * _choose_scale_float8 + _quantize_affine_float8 (torchao/quantization/quant_primitives.py:2175-2221,
+ * 2274-2293) behind to_affine_quantized_floatx, byte for byte. */
+int tao_fp8_quantize_rows_bf16(const uint16_t* w, uint8_t* q, float* scale, int64_t rows,
+                               int64_t K, void* stream);
+
+/* w[N][K] bf16 <- bf16(f(q[n][k]) * scale[n]) (product in fp32; NaN codes give NaN). K % 8 == 0.
+ * Replaces _dequantize_affine_float8 (torchao/quantization/quant_primitives.py:2298-2312), bit-exact
+ * to AffineQuantizedTensor.dequantize() of a Float8Layout weight. */
+int tao_fp8_dequant_bf16(const uint8_t* q, const float* scale, uint16_t* w, int64_t N, int64_t K,
+                         void* stream);
+
 /* ---- int8 dynamic activation x int8 weight -------------------------------------------------- */
 
 /* Per-token symmetric reduced-range int8 quantization of x [M][K] bf16:

@@ -193,6 +193,10 @@ int tao_tune_int4_norm(int mode);
  * rows per wave 2/4/8, waves along K, row groups per workgroup; 0 = built-in heuristic).
  * Calling thread only; for sweeps (experiments/sweep_int8.py). */
 int tao_tune_int8_gemv(int rows_per_wave, int waves_k, int row_groups);
+/* Tuning hook: M == 1 launch shape of the fp8 weight-only GEMV (rows per wave 2/4/8, waves along
+ * K, row groups per workgroup; waves_k * row_groups <= 8; 0 = built-in, the int8 GEMV's choice).
+ * Calling thread only; for sweeps. */
+int tao_tune_fp8_gemv(int rows_per_wave, int waves_k, int row_groups);
 /* Per-token int8 quantisation kernel (A/B only): 0 = one wave per token, the token held in
  * registers (default, K <= 8192); 1 = one 256-thread workgroup per token. Bit-identical. */
 int tao_tune_int8_quant(int block);

@@ -1,12 +1,13 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// three weight/activation formats share one kernel template:
+// four weight/activation formats share one kernel template:
 //   Int4WO  : bf16 x, int4 group-quant W (gfx950 row-stream layout), v_mfma_f32_16x16x32_bf16
 //   Int8WO  : bf16 x, int8 per-channel W,                            v_mfma_f32_16x16x32_bf16
+//   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
 //   Int8Dyn : int8 x (per-token scale), int8 W (per-channel scale),   v_mfma_i32_16x16x64_i8
 // Replaces aten._weight_int4pack_mm (tensor_core_tiled_layout.py:104), mm(x, w.to(bf16)) * s
-// (plain_layout.py:256-266) and int_scaled_matmul + scales (plain_layout.py:294-315,
-// kernel/intmm.py:108-143).
+// (plain_layout.py:256-266), int_scaled_matmul + scales (plain_layout.py:294-315,
+// kernel/intmm.py:108-143) and F.linear(x, w.dequantize()) (floatx/float8_layout.py:391-396).
 //
 // Tile: 4 waves x 16 output columns (BN = 64) x BM rows per k-group; each wave owns 16 columns
 // and all BM rows. K advances in macro-steps (256 bf16 k for int4, 128 bf16 k for int8-WO,
@@ -39,6 +40,8 @@ int int4_check_linear_args(const uint16_t* x, const uint32_t* packed, const uint
                            uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t group_size);
 int int8wo_gemv(const uint16_t* x, const int8_t* w, const uint16_t* scale, const uint16_t* bias,
                 uint16_t* y, int64_t M, int64_t N, int64_t K, hipStream_t stream);
+int fp8wo_gemv(const uint16_t* x, const uint8_t* w, const float* scale, const uint16_t* bias,
+               uint16_t* y, int64_t M, int64_t N, int64_t K, hipStream_t stream);
 // gemm_tile.hip: the weight-shared tile GEMM (4 waves split the rows, weights dequantised once per
 // workgroup) and its routing rule
 int tile_int4(const uint16_t* x, const uint32_t* packed, const uint16_t* sz, int gshift,
@@ -122,6 +125,7 @@ __device__ __forceinline__ TileId xcd_tile(int order) {
 // row's finite weights against x that the LDS store zeroes. prep()/frag(): B fragments.
 struct Int4WO {
   static constexpr int kPathId = 0;   // gemm_table.inc
+  static constexpr bool kMaskTail = false;
   static constexpr int kABytes = 2;   // bf16 x
   static constexpr int kKStep = 256;  // 128 B of nibbles per row per step: one full line
   static constexpr int kMfma = 8;
@@ -236,6 +240,7 @@ struct Int4WO {
 
 struct Int8WO {
   static constexpr int kPathId = 1;
+  static constexpr bool kMaskTail = false;
   static constexpr int kABytes = 2;
   static constexpr int kKStep = 128;
   static constexpr int kMfma = 4;
@@ -309,8 +314,74 @@ struct Int8WO {
   }
 };
 
+// e4m3fn weights, one byte each like Int8WO: the same full-line loads, per-wave stage, k order
+// and x image. The dequant step is the hardware decode: one v_cvt_scalef32_pk_bf16_fp8 (scale 1.0)
+// per two codes, exact because every finite e4m3fn value is a bf16 number; x stays bf16 (the
+// non-scaled fp8 MFMA runs at the bf16 rate, so quantising x would buy nothing).
+struct Fp8WO {
+  static constexpr int kPathId = 3;  // no measured table entries: the heuristic shapes
+  // A K tail reads the next row's codes against zeroed x; unlike the integer formats a code can
+  // be NaN (an all-zero row quantises to NaN codes) and 0 * NaN would reach the sum, so the
+  // codes past K are zeroed after the stage read (mask_tail).
+  static constexpr bool kMaskTail = true;
+  static constexpr int kABytes = 2;
+  static constexpr int kKStep = 128;
+  static constexpr int kMfma = 4;
+  static constexpr int kMaxBM = 128;
+  static constexpr int kPrefKG = 2;
+  static constexpr int kMinSlice = 8;
+  typedef f32x4_t Acc;
+  const uint4* w;      // [N][K/16] e4m3fn codes
+  const float* scale;  // [N] fp32
+  static constexpr int kStage = 128;  // uint4 per wave
+  typedef Int8WO::Lane Lane;
+  typedef Int8WO::Chunk Chunk;
+  typedef Chunk Prep;
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    return Int8WO{w, nullptr}.setup(bn, lane, N, K);
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    return Int8WO{w, nullptr}.load(L, st);
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    return Int8WO{w, nullptr}.prep(ch, stage, lane);
+  }
+  // lane (n, kq) holds k 16 kq .. +16 (a) and 64 + 16 kq .. +16 (b) of step st; K % 32 == 0,
+  // so each 16-B piece is wholly inside or wholly past the row (AND masks, no select)
+  static __device__ __forceinline__ void mask_tail(Prep& p, int st, int kq, int K) {
+    const int k0 = st * kKStep + 16 * kq;
+    const uint32_t ka = k0 < K ? ~0u : 0u, kb = k0 + 64 < K ? ~0u : 0u;
+    p.a = make_uint4(p.a.x & ka, p.a.y & ka, p.a.z & ka, p.a.w & ka);
+    p.b = make_uint4(p.b.x & kb, p.b.y & kb, p.b.z & kb, p.b.w & kb);
+  }
+  __device__ __forceinline__ bf16x8_t frag(const Prep& p, int s) const {
+    const uint32_t d0 = (s == 0) ? p.a.x : (s == 1) ? p.a.z : (s == 2) ? p.b.x : p.b.z;
+    const uint32_t d1 = (s == 0) ? p.a.y : (s == 1) ? p.a.w : (s == 2) ? p.b.y : p.b.w;
+    auto cv = [](uint32_t d, bool hi) {
+      return hi ? __builtin_bit_cast(uint32_t,
+                                     __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d, 1.0f, true))
+                : __builtin_bit_cast(uint32_t,
+                                     __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d, 1.0f, false));
+    };
+    return as_bf16x8(cv(d0, false), cv(d0, true), cv(d1, false), cv(d1, true));
+  }
+  static __device__ __forceinline__ int slot(int s, int kq) { return Int8WO::slot(s, kq); }
+  static __device__ __forceinline__ int xswz(int row) { return row & 15; }
+  static __device__ __forceinline__ Acc mfma(const uint4& a, const bf16x8_t& b, Acc c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), b, c, 0, 0, 0);
+  }
+  // the fp32 sum times the fp32 scale, rounded once (include/torchao_mi355x.h)
+  static constexpr bool kRowF = false, kColF = true;
+  __device__ __forceinline__ const uint16_t* row_factor() const { return nullptr; }
+  __device__ __forceinline__ const float* col_factor() const { return scale; }
+  __device__ __forceinline__ float epi(float acc, float, float sc) const {
+    return round_bf16(acc * sc);
+  }
+};
+
 struct Int8Dyn {
   static constexpr int kPathId = 2;
+  static constexpr bool kMaskTail = false;
   static constexpr int kABytes = 1;  // int8 x
   static constexpr int kKStep = 256;
   static constexpr int kMfma = 4;
@@ -540,7 +611,10 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
     if (abs_step(j) < s1) {  // uniform: a k-group's idle tail iterations skip the math
       typename P::Prep pw[NW];
 #pragma unroll
-      for (int c = 0; c < NW; ++c) pw[c] = pol.prep(wr[u][c], wstage + c * P::kStage, lane);
+      for (int c = 0; c < NW; ++c) {
+        pw[c] = pol.prep(wr[u][c], wstage + c * P::kStage, lane);
+        if constexpr (P::kMaskTail) P::mask_tail(pw[c], abs_step(j), kq, K);
+      }
       const uint4* xb = xs + (j & 1) * TILE;
 #pragma unroll
       for (int s = 0; s < P::kMfma; ++s) {
@@ -587,7 +661,12 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
 #pragma unroll
   for (int c = 0; c < NW; ++c) {
     const int nn = bn[c] < N ? bn[c] : N - 1;
-    colf[c] = P::kColF ? bf16_to_f32(pol.col_factor()[nn]) : 1.f;
+    if constexpr (!P::kColF)
+      colf[c] = 1.f;
+    else if constexpr (std::is_same_v<decltype(pol.col_factor()), const float*>)
+      colf[c] = pol.col_factor()[nn];  // fp32 factors (Fp8WO)
+    else
+      colf[c] = bf16_to_f32(pol.col_factor()[nn]);
     biasf[c] = (kPre && bias != nullptr) ? bf16_to_f32(bias[nn]) : 0.f;
   }
   static_for<0, D - 1>([&](auto i) __attribute__((always_inline)) {
@@ -1518,6 +1597,27 @@ extern "C" int tao_int8wo_linear_bf16(const uint16_t* x, const int8_t* w, const 
     return tao::tile_int8wo(x, w, scale, bias, y, (int)M, (int)N, (int)K, st,
                             tao::tuning().tile_splits);
   tao::Int8WO pol;
+  pol.w = reinterpret_cast<const uint4*>(w);
+  pol.scale = scale;
+  return tao::launch_gemm(x, pol, bias, y, (int)M, (int)N, (int)K, st);
+}
+
+extern "C" int tao_fp8wo_linear_bf16(const uint16_t* x, const uint8_t* w, const float* scale,
+                                     const uint16_t* bias, uint16_t* y, int64_t M, int64_t N,
+                                     int64_t K, void* stream) {
+  TAO_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "fp8 weight-only linear: negative size");
+  TAO_CHECK_ARG(K % 32 == 0, "fp8 weight-only linear: K (%lld) must be a multiple of 32",
+                (long long)K);
+  TAO_CHECK_ARG(N < (1LL << 31) && K < (1LL << 31) && M < (1LL << 31),
+                "fp8 weight-only linear: size out of range");
+  if (M == 0 || N == 0) return TAO_OK;
+  TAO_CHECK_ARG(K > 0, "fp8 weight-only linear: K must be > 0");
+  TAO_CHECK_ALIGN(x, 16, "x");
+  TAO_CHECK_ALIGN(w, 16, "w");
+  TAO_CHECK_ALIGN(scale, 4, "scale");
+  hipStream_t st = tao::as_stream(stream);
+  if (tao::use_gemv(M, N, K)) return tao::fp8wo_gemv(x, w, scale, bias, y, M, N, K, st);
+  tao::Fp8WO pol;
   pol.w = reinterpret_cast<const uint4*>(w);
   pol.scale = scale;
   return tao::launch_gemm(x, pol, bias, y, (int)M, (int)N, (int)K, st);

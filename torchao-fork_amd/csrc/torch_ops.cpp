@@ -1,6 +1,7 @@
 // torch dispatcher kernels (CUDA key = HIP on PyTorch-ROCm) for the quantized-linear ops that run
 // once per linear per forward: int4_weight_only_linear, int8_weight_only_linear,
-// int8_quantize_per_token, int8_scaled_mm, int8_dyn_linear.
+// int8_quantize_per_token, int8_scaled_mm, int8_dyn_linear, and the float8 weight-only set
+// fp8_weight_only_linear, fp8_quantize_rows, fp8_dequantize.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -195,6 +196,71 @@ Tensor int8_dyn_linear(const Tensor& x, const Tensor& w_int8, const Tensor& w_sc
   return y.reshape(out_shape(x, N));
 }
 
+// ---- float8 (e4m3fn) weight-only (ops.py _fp8wo_linear_cuda & co) -----------------------------
+void check_fp8_weight(const Tensor& w, const Tensor& scale) {
+  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == at::kFloat8_e4m3fn,
+              "w must be a 2D float8_e4m3fn tensor");
+  TORCH_CHECK(scale.numel() == w.size(0), "scale must have N elements");
+}
+
+Tensor fp8_weight_only_linear(const Tensor& x, const Tensor& w_fp8, const Tensor& scale,
+                              const std::optional<Tensor>& bias) {
+  check_fp8_weight(w_fp8, scale);
+  const int64_t N = w_fp8.size(0), K = w_fp8.size(1);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "fp8 weight-only linear (HIP) needs bf16 x");
+  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
+  check_device(x, w_fp8, "w_fp8");
+  check_device(x, scale, "scale");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const Tensor w = w_fp8.contiguous();
+  const Tensor s = scale.reshape({-1}).to(at::kFloat).contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  check_rc(tao_fp8wo_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(w), cptr<float>(s),
+                                 b ? cptr<uint16_t>(*b) : nullptr, mptr<uint16_t>(y), M, N, K,
+                                 stream_of(x)),
+           "tao_fp8wo_linear_bf16");
+  return y.reshape(out_shape(x, N));
+}
+
+std::tuple<Tensor, Tensor> fp8_quantize_rows(const Tensor& w) {
+  TORCH_CHECK(w.is_cuda(), "expected w on a HIP device, got ", w.device());
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16, "fp8 quantize (HIP) needs a bf16 weight");
+  TORCH_CHECK(w.dim() >= 1, "fp8 quantize: w must have at least one dimension");
+  const int64_t K = w.size(-1);
+  TORCH_CHECK(K % 8 == 0, "K (", K, ") must be a multiple of 8");
+  const Tensor w2 = rows_of(w, K);
+  const int64_t R = w2.size(0);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+  Tensor q = at::empty({R, K}, w.options().dtype(at::kFloat8_e4m3fn));
+  Tensor s = at::empty({R}, w.options().dtype(at::kFloat));
+  check_rc(tao_fp8_quantize_rows_bf16(cptr<uint16_t>(w2), mptr<uint8_t>(q), mptr<float>(s), R, K,
+                                      stream_of(w)),
+           "tao_fp8_quantize_rows_bf16");
+  std::vector<int64_t> ss(w.sizes().begin(), w.sizes().end() - 1);
+  ss.push_back(1);
+  return {q.reshape(w.sizes()), s.reshape(ss)};
+}
+
+Tensor fp8_dequantize(const Tensor& q, const Tensor& scale) {
+  TORCH_CHECK(q.is_cuda(), "expected q on a HIP device, got ", q.device());
+  check_fp8_weight(q, scale);
+  check_device(q, scale, "scale");
+  const int64_t N = q.size(0), K = q.size(1);
+  TORCH_CHECK(K % 8 == 0, "K (", K, ") must be a multiple of 8");
+  const Tensor qc = q.contiguous();
+  const Tensor s = scale.reshape({-1}).to(at::kFloat).contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+  Tensor w = at::empty({N, K}, q.options().dtype(at::kBFloat16));
+  check_rc(tao_fp8_dequant_bf16(cptr<uint8_t>(qc), cptr<float>(s), mptr<uint16_t>(w), N, K,
+                                stream_of(q)),
+           "tao_fp8_dequant_bf16");
+  return w;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
@@ -203,10 +269,18 @@ TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
   m.impl("int8_quantize_per_token", &int8_quantize_per_token);
   m.impl("int8_scaled_mm", &int8_scaled_mm);
   m.impl("int8_dyn_linear", &int8_dyn_linear);
+  m.impl("fp8_weight_only_linear", &fp8_weight_only_linear);
+  m.impl("fp8_quantize_rows", &fp8_quantize_rows);
+  m.impl("fp8_dequantize", &fp8_dequantize);
 }
 
 // Probe for torchao.ops (which ops this library serves).
 extern "C" const char* tao_torch_ops_served(void) {
   return "int4_weight_only_linear,int8_weight_only_linear,int8_quantize_per_token,"
          "int8_scaled_mm,int8_dyn_linear";
+}
+
+// The float8 weight-only ops served here, listed apart from the integer per-linear set above.
+extern "C" const char* tao_torch_ops_served_float8(void) {
+  return "fp8_weight_only_linear,fp8_quantize_rows,fp8_dequantize";
 }

@@ -4,6 +4,7 @@ from . import affine_quantized_tensor_ops  # noqa: F401  (registers the op overr
 from .affine_quantized_tensor import (
     AffineQuantizedTensor,
     register_layout,
+    to_affine_quantized_floatx,
     to_affine_quantized_intx,
     to_affine_quantized_intx_static,
 )
@@ -12,6 +13,7 @@ from .affine_quantized_tensor_ops import (
     deregister_aqt_quantized_linear_dispatch,
     register_aqt_quantized_linear_dispatch,
 )
+from .floatx import Float8AQTTensorImpl, Float8Layout, Float8MMConfig
 from .uintx import PlainAQTTensorImpl, TensorCoreTiledAQTTensorImpl, TensorCoreTiledLayout
 from .utils import AQTTensorImpl, Layout, PlainLayout
 
@@ -23,10 +25,14 @@ __all__ = [
     "PlainAQTTensorImpl",
     "TensorCoreTiledLayout",
     "TensorCoreTiledAQTTensorImpl",
+    "Float8Layout",
+    "Float8AQTTensorImpl",
+    "Float8MMConfig",
     "QuantizedLinearNotImplementedError",
     "register_aqt_quantized_linear_dispatch",
     "deregister_aqt_quantized_linear_dispatch",
     "register_layout",
+    "to_affine_quantized_floatx",
     "to_affine_quantized_intx",
     "to_affine_quantized_intx_static",
 ]

@@ -3,8 +3,10 @@
 Mirrors the reference (torchao/dtypes/affine_quantized_tensor.py:57-614) for the integer
 workflows on the hot path: ``from_hp_to_intx`` (pre_process -> choose_qparams -> quantize ->
 post_process -> layout constructor, :231-373), ``from_hp_to_intx_static``, ``dequantize``
-(:134-196), flatten/unflatten (:198-229), ``to`` and ``_apply_fn_to_data``. The float8 /
-floatx / HQQ constructors belong to out-of-scope workflows and are not provided.
+(:134-196), flatten/unflatten (:198-229), ``to`` and ``_apply_fn_to_data``, and the float8
+weight-only constructor ``from_hp_to_floatx`` (:449-480; e4m3fn, ``Float8Layout``). The
+static float8, floatx (fp6) and HQQ constructors belong to out-of-scope workflows and are not
+provided.
 """
 
 import logging
@@ -16,9 +18,13 @@ from torchao.dtypes.utils import AQTTensorImpl, Layout, PlainLayout
 from torchao.quantization.quant_primitives import (
     MappingType,
     ZeroPointDomain,
+    FP8_TYPES,
     _choose_qparams_affine_tinygemm,
+    _choose_scale_float8,
+    _dequantize_affine_float8,
     _dequantize_affine_no_zero_point,
     _dequantize_affine_tinygemm,
+    _quantize_affine_float8,
     _quantize_affine_no_zero_point,
     _quantize_affine_tinygemm,
     choose_qparams_affine,
@@ -35,6 +41,7 @@ __all__ = [
     "register_layout",
     "to_affine_quantized_intx",
     "to_affine_quantized_intx_static",
+    "to_affine_quantized_floatx",
 ]
 
 
@@ -174,6 +181,8 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
         """High-precision tensor of ``self.shape``: get_plain() -> the domain's dequant formula."""
         output_dtype = self.dtype if output_dtype is None else output_dtype
         data, scale, zero_point = self.tensor_impl.get_plain()
+        if data.dtype in FP8_TYPES:
+            return self._dequantize_float8(data, scale, output_dtype)
         if self.zero_point_domain == ZeroPointDomain.FLOAT:
             fn = _dequantize_affine_tinygemm
         elif self.zero_point_domain == ZeroPointDomain.NONE:
@@ -195,6 +204,23 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
             if dq.shape[dim] != size:
                 dq = dq.narrow(dim, 0, size)
         return dq
+
+    def _dequantize_float8(self, data, scale, output_dtype):
+        """float(q) * scale, rounded once to ``output_dtype`` (_dequantize_affine_float8,
+        reference :149-151). Per-row e4m3fn data on the GPU with a bf16 result runs the HIP
+        kernel (``torchao::fp8_dequantize``), bit-identical to the torch-op formulation."""
+        if (
+            data.is_cuda
+            and output_dtype == torch.bfloat16
+            and data.dtype == torch.float8_e4m3fn
+            and data.dim() == 2
+            and data.shape[1] % 8 == 0
+            and scale.numel() == data.shape[0]
+        ):
+            dq = torch.ops.torchao.fp8_dequantize(data, scale.reshape(-1))
+        else:
+            dq = _dequantize_affine_float8(data, scale, output_dtype)
+        return dq.t() if getattr(self.tensor_impl, "transposed", False) else dq
 
     def __tensor_flatten__(self):
         with torch._C.DisableTorchFunctionSubclass():
@@ -355,6 +381,49 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
             dtype=input_float.dtype,
         )
 
+    @classmethod
+    def from_hp_to_floatx(
+        cls,
+        input_float: torch.Tensor,
+        block_size: Tuple[int, ...],
+        target_dtype: torch.dtype,
+        _layout: Layout,
+        scale_dtype: Optional[torch.dtype] = None,
+    ):
+        """Quantize a high-precision tensor into a float8 AQT with ``_layout`` (reference
+        :449-480): scale = amax|block| / max (no eps), data = float8(clamp(x / scale)).
+
+        bf16 CUDA weights with per-row blocks (1, ..., K) run the fused HIP quantizer
+        (``torchao::fp8_quantize_rows``); everything else runs the torch-op formulation. The two
+        agree byte for byte (tests/test_gpu_float8.py)."""
+        if target_dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(
+                f"Unsupported dtype {target_dtype} for from_hp_to_floatx: only "
+                "torch.float8_e4m3fn is in scope"
+            )
+        original_shape = input_float.shape
+        input_float = _layout.pre_process(input_float)
+        K = input_float.shape[-1]
+        if (
+            input_float.is_cuda
+            and input_float.dtype == torch.bfloat16
+            and input_float.dim() in (2, 3)
+            and all(b == 1 for b in block_size[:-1])
+            and block_size[-1] == K
+            and K % 8 == 0
+        ):
+            data, scale = torch.ops.torchao.fp8_quantize_rows(input_float)
+        else:
+            scale = _choose_scale_float8(
+                input_float, float8_dtype=target_dtype, block_size=block_size
+            )
+            data = _quantize_affine_float8(input_float, scale, target_dtype)
+        data, scale, zero_point = _layout.post_process(data, scale, None, block_size)
+        tensor_impl = cls.get_tensor_impl_constructor(type(_layout))(
+            data, scale, zero_point, _layout
+        )
+        return cls(tensor_impl, block_size, original_shape, dtype=input_float.dtype)
+
     def to(self, *args, **kwargs):
         kwargs = self._get_to_kwargs(*args, **kwargs)
         device = kwargs.pop("device")
@@ -385,5 +454,6 @@ register_layout = AffineQuantizedTensor.register_layout
 get_tensor_impl_constructor = AffineQuantizedTensor.get_tensor_impl_constructor
 to_affine_quantized_intx = AffineQuantizedTensor.from_hp_to_intx
 to_affine_quantized_intx_static = AffineQuantizedTensor.from_hp_to_intx_static
+to_affine_quantized_floatx = AffineQuantizedTensor.from_hp_to_floatx
 
 torch.serialization.add_safe_globals([AffineQuantizedTensor])

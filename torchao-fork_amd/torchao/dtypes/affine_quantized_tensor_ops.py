@@ -8,7 +8,8 @@ and the layout does not insist on its own impl. The aten view / copy ops (:422-5
 subclass usable inside ``nn.Linear``, ``DTensor.from_local`` and state-dict loading.
 
 The pairs registered here are the MI355X ones, in the reference's order of precedence:
-int8 dynamic-activation x int8 weight, int8 weight-only, int4 weight-only (gfx950 layout).
+int8 dynamic-activation x int8 weight, int8 weight-only, int4 weight-only (gfx950 layout),
+float8 (e4m3fn) weight-only.
 """
 
 import logging
@@ -17,6 +18,10 @@ import torch
 from torch.utils._python_dispatch import return_and_correct_aliasing
 
 from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
+from torchao.dtypes.floatx.float8_layout import (
+    _linear_fp_act_fp8_weight_check,
+    _linear_fp_act_fp8_weight_impl,
+)
 from torchao.dtypes.uintx.plain_layout import (
     _linear_fp_act_int8_weight_check,
     _linear_fp_act_int8_weight_impl,
@@ -69,6 +74,7 @@ for _cond, _impl in [
     (_linear_int8_act_int8_weight_check, _linear_int8_act_int8_weight_impl),
     (_linear_fp_act_int8_weight_check, _linear_fp_act_int8_weight_impl),
     (_linear_bf16_act_uint4_weight_check, _linear_bf16_act_uint4_weight_impl),
+    (_linear_fp_act_fp8_weight_check, _linear_fp_act_fp8_weight_impl),
 ]:
     register_aqt_quantized_linear_dispatch(_cond, _impl)
 

@@ -24,6 +24,10 @@ Operators:
   * ``int4_quantize_pack`` / ``int8_quantize_rows`` — the weight quantizers of
     ``from_hp_to_intx`` in one pass each (tinygemm qparams + quantize + row-stream pack;
     symmetric per-row int8), bit-exact to the bf16 torch-op formulation.
+  * ``fp8_weight_only_linear`` — e4m3fn per-row-scaled weight-only linear; replaces
+    ``F.linear(x, weight.dequantize(), bias)`` (floatx/float8_layout.py:391-396).
+  * ``fp8_quantize_rows`` / ``fp8_dequantize`` — the per-row e4m3fn quantizer of
+    ``from_hp_to_floatx`` and its dequant (quant_primitives.py:2175-2312), byte for byte.
 """
 
 import ctypes
@@ -74,6 +78,15 @@ lib.define(
 lib.define(
     "int8_dyn_linear(Tensor x, Tensor w_int8, Tensor w_scale, Tensor? bias=None) -> Tensor"
 )
+# The float8 weight-only ops live in a fragment of their own: ``lib`` keeps exactly the integer
+# op set that tests/test_gpu_opcheck.py enumerates from it; these three are opchecked in
+# tests/test_gpu_float8.py.
+lib_float8 = torch.library.Library("torchao", "FRAGMENT")
+lib_float8.define(
+    "fp8_weight_only_linear(Tensor x, Tensor w_fp8, Tensor scale, Tensor? bias=None) -> Tensor"
+)
+lib_float8.define("fp8_quantize_rows(Tensor w) -> (Tensor, Tensor)")
+lib_float8.define("fp8_dequantize(Tensor q, Tensor scale) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -598,6 +611,86 @@ def _int8_quantize_rows_cuda(w: Tensor, eps: float):
     return q.reshape(w.shape), s.reshape(w.shape[:-1])
 
 
+# ---------------------------------------------------------------------------------------------
+# float8 (e4m3fn) weight-only
+# ---------------------------------------------------------------------------------------------
+def _check_fp8_weight(w: Tensor, scale: Tensor):
+    torch._check(w.dim() == 2 and w.dtype is torch.float8_e4m3fn,
+                 lambda: "w must be a 2D float8_e4m3fn tensor")
+    torch._check(scale.numel() == w.size(0), lambda: "scale must have N elements")
+    return w.shape
+
+
+@torch.library.register_fake("torchao::fp8_weight_only_linear")
+def _(x, w_fp8, scale, bias=None):
+    N, K = _check_fp8_weight(w_fp8, scale)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N), dtype=torch.bfloat16)
+
+
+def _fp8wo_linear_cuda(x, w_fp8, scale, bias=None):
+    N, K = _check_fp8_weight(w_fp8, scale)
+    torch._check(x.dtype is torch.bfloat16, lambda: "fp8 weight-only linear (HIP) needs bf16 x")
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    _same_device(x, w_fp8=w_fp8, scale=scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    w_fp8 = w_fp8.contiguous()
+    scale = scale.reshape(-1).to(torch.float32).contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    with torch.cuda.device(x.device):
+        _lib.call("tao_fp8wo_linear_bf16", _ptr(x2), _ptr(w_fp8), _ptr(scale), _ptr(bias),
+                  _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
+@torch.library.register_fake("torchao::fp8_quantize_rows")
+def _(w):
+    torch._check(w.size(-1) % 8 == 0, lambda: f"K ({w.size(-1)}) must be a multiple of 8")
+    return (w.new_empty(w.shape, dtype=torch.float8_e4m3fn),
+            w.new_empty((*w.shape[:-1], 1), dtype=torch.float32))
+
+
+def _fp8_quantize_rows_cuda(w: Tensor):
+    """bf16 W [..., K] -> (e4m3fn [..., K], per-row scale fp32 [..., 1]); no eps."""
+    torch._check(w.dtype is torch.bfloat16, lambda: "fp8 quantize (HIP) needs a bf16 weight")
+    K = w.size(-1)
+    torch._check(K % 8 == 0, lambda: f"K ({K}) must be a multiple of 8")
+    w2 = w.reshape(-1, K)
+    if not w2.is_contiguous() or w2.data_ptr() % 16:
+        w2 = w2.contiguous()
+    R = w2.size(0)
+    q = torch.empty((R, K), dtype=torch.float8_e4m3fn, device=w.device)
+    s = torch.empty((R,), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("tao_fp8_quantize_rows_bf16", _ptr(w2), _ptr(q), _ptr(s), R, K, _stream(w))
+    return q.reshape(w.shape), s.reshape(*w.shape[:-1], 1)
+
+
+@torch.library.register_fake("torchao::fp8_dequantize")
+def _(q, scale):
+    N, K = _check_fp8_weight(q, scale)
+    torch._check(K % 8 == 0, lambda: f"K ({K}) must be a multiple of 8")
+    return q.new_empty((N, K), dtype=torch.bfloat16)
+
+
+def _fp8_dequantize_cuda(q: Tensor, scale: Tensor):
+    """e4m3fn [N, K] x per-row fp32 scale -> bf16 [N, K] = bf16(float(q) * scale)."""
+    N, K = _check_fp8_weight(q, scale)
+    torch._check(K % 8 == 0, lambda: f"K ({K}) must be a multiple of 8")
+    _same_device(q, scale=scale)
+    q = q.contiguous()
+    scale = scale.reshape(-1).to(torch.float32).contiguous()
+    out = torch.empty((N, K), dtype=torch.bfloat16, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.call("tao_fp8_dequant_bf16", _ptr(q), _ptr(scale), _ptr(out), N, K, _stream(q))
+    return out
+
+
 # ---- register device impls ------------------------------------------------------------------
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
@@ -606,22 +699,33 @@ def _int8_quantize_rows_cuda(w: Tensor, eps: float):
 # build (the C++ kernels are linked to the in-tree library).
 _OPS_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtorchao_ops.so")
 _native_served: frozenset = frozenset()
+_native_served_float8: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
 else:
     try:
         torch.ops.load_library(_OPS_LIB)
-        _served = ctypes.CDLL(_OPS_LIB).tao_torch_ops_served
+        _ops_dll = ctypes.CDLL(_OPS_LIB)
+        _served = _ops_dll.tao_torch_ops_served
         _served.restype = ctypes.c_char_p
         _native_served = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_float8
+        _served.restype = ctypes.c_char_p
+        _native_served_float8 = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
 
 def native_dispatch() -> frozenset:
-    """The ``torch.ops.torchao`` ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    """The integer per-linear ``torch.ops.torchao`` ops whose CUDA kernel is C++
+    (libtorchao_ops.so); the float8 weight-only set is ``native_dispatch_float8()``."""
     return _native_served
+
+
+def native_dispatch_float8() -> frozenset:
+    """The float8 weight-only ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_float8
 
 
 for _name, _fn in [
@@ -642,6 +746,13 @@ for _name, _fn in [
 ]:
     if _name not in _native_served:
         lib.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("fp8_weight_only_linear", _fp8wo_linear_cuda),
+    ("fp8_quantize_rows", _fp8_quantize_rows_cuda),
+    ("fp8_dequantize", _fp8_dequantize_cuda),
+]:
+    if _name not in _native_served_float8:
+        lib_float8.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")

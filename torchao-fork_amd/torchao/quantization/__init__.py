@@ -6,10 +6,12 @@ from torchao.quantization.linear_activation_quantized_tensor import (
     to_linear_activation_quantized,
 )
 from torchao.quantization.quant_api import (
+    Float8WeightOnlyConfig,
     Int4WeightOnlyConfig,
     Int8DynamicActivationInt8WeightConfig,
     Int8WeightOnlyConfig,
     ModuleFqnToConfig,
+    float8_weight_only,
     int4_weight_only,
     int8_dynamic_activation_int8_weight,
     int8_weight_only,
@@ -31,10 +33,12 @@ __all__ = [
     "Int4WeightOnlyConfig",
     "Int8WeightOnlyConfig",
     "Int8DynamicActivationInt8WeightConfig",
+    "Float8WeightOnlyConfig",
     "ModuleFqnToConfig",
     "int4_weight_only",
     "int8_weight_only",
     "int8_dynamic_activation_int8_weight",
+    "float8_weight_only",
     "LinearActivationQuantizedTensor",
     "to_linear_activation_quantized",
     "MappingType",

@@ -9,10 +9,13 @@ Configs on the MI355X hot path, with the reference defaults:
   ``TensorCoreTiledLayout(inner_k_tiles=8)`` -> gfx950 int4 kernels;
 * ``Int8WeightOnlyConfig`` (:1200-1255): int8 symmetric per-channel -> int8 GEMV / MFMA;
 * ``Int8DynamicActivationInt8WeightConfig`` (:1352-1449): int8 per-channel weight + per-token
-  reduced-range int8 activation quantized on the fly -> HIP quant kernel + int8 MFMA GEMM.
+  reduced-range int8 activation quantized on the fly -> HIP quant kernel + int8 MFMA GEMM;
+* ``Float8WeightOnlyConfig`` (:1465-1530): e4m3fn symmetric per-channel, fp32 scales,
+  ``Float8Layout`` -> fp8 GEMV / MFMA. Its ``version`` defaults to 1 here (the
+  ``AffineQuantizedTensor`` form); the reference's default 2 (``Float8Tensor``) raises.
 
-Other workflows of the reference (float8, HQQ, fbgemm "version 2" tensors, marlin, gemlite,
-intx, QAT, ...) are out of scope and raise.
+Other workflows of the reference (float8 dynamic activation, ``Float8Tensor``, HQQ, fbgemm
+"version 2" tensors, marlin, gemlite, intx, QAT, ...) are out of scope and raise.
 """
 
 import logging
@@ -27,8 +30,10 @@ import torchao
 from torchao.core.config import AOBaseConfig
 from torchao.dtypes.affine_quantized_tensor import (
     AffineQuantizedTensor,
+    to_affine_quantized_floatx,
     to_affine_quantized_intx,
 )
+from torchao.dtypes.floatx.float8_layout import Float8Layout
 from torchao.dtypes.uintx.plain_layout import PlainAQTTensorImpl
 from torchao.dtypes.uintx.tensor_core_tiled_layout import TensorCoreTiledLayout
 from torchao.dtypes.utils import Layout, PlainLayout
@@ -53,6 +58,8 @@ __all__ = [
     "int8_weight_only",
     "Int8DynamicActivationInt8WeightConfig",
     "int8_dynamic_activation_int8_weight",
+    "Float8WeightOnlyConfig",
+    "float8_weight_only",
     "ModuleFqnToConfig",
     "LAYOUT_TO_ZERO_POINT_DOMAIN",
     "LAYOUT_TO_PRESERVE_ZEROS",
@@ -396,3 +403,60 @@ def _int8_dynamic_activation_int8_weight_transform(
     return _swap_weight(
         module, _int8_dynamic_activation_int8_weight_quantize_tensor(module.weight, config)
     )
+
+
+# ---------------------------------------------------------------------------------------------
+# float8 weight-only
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class Float8WeightOnlyConfig(AOBaseConfig):
+    """float8 (e4m3fn) symmetric per-channel weight-only quantization with fp32 scales
+    (reference :1465-1530); the matmul runs in the activation's precision (bf16).
+
+    Args: ``weight_dtype`` (only ``torch.float8_e4m3fn``; anything else raises
+    ``NotImplementedError``), ``set_inductor_config``, ``version``.
+
+    Deviation from the reference: ``version`` defaults to **1**, the ``AffineQuantizedTensor`` +
+    ``Float8Layout`` form, so that ``Float8WeightOnlyConfig()`` works. The reference defaults
+    to 2, its ``Float8Tensor``, which is out of scope here: ``version=2`` raises
+    ``NotImplementedError``. Checkpoints the reference saved with ``version=1`` load as they are.
+    """
+
+    weight_dtype: torch.dtype = torch.float8_e4m3fn
+    set_inductor_config: bool = True
+    version: int = 1
+
+    def __post_init__(self):
+        torch._C._log_api_usage_once("torchao.quantization.Float8WeightOnlyConfig")
+
+
+float8_weight_only = Float8WeightOnlyConfig
+
+
+def _float8_weight_only_quant_tensor(weight: torch.Tensor, config: Float8WeightOnlyConfig):
+    if config.version != 1:
+        raise NotImplementedError(
+            f"Float8WeightOnlyConfig(version={config.version}) (Float8Tensor) is out of scope; "
+            "use version=1"
+        )
+    if config.weight_dtype != torch.float8_e4m3fn:
+        raise NotImplementedError(
+            f"Float8WeightOnlyConfig(weight_dtype={config.weight_dtype}) is out of scope; only "
+            "torch.float8_e4m3fn is supported"
+        )
+    block_size = tuple([1] * (weight.dim() - 1) + [weight.shape[-1]])
+    return to_affine_quantized_floatx(
+        input_float=weight,
+        block_size=block_size,
+        target_dtype=config.weight_dtype,
+        scale_dtype=None,
+        _layout=Float8Layout(mm_config=None),
+    )
+
+
+@register_quantize_module_handler(Float8WeightOnlyConfig)
+def _float8_weight_only_transform(module: nn.Module, config: Float8WeightOnlyConfig) -> nn.Module:
+    if config.set_inductor_config:
+        torchao.quantization.utils.recommended_inductor_config_setter()
+    assert hasattr(module, "weight"), "float8 weight-only quant requires a module with a weight"
+    return _swap_weight(module, _float8_weight_only_quant_tensor(module.weight, config))

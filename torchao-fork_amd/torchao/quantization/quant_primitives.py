@@ -11,6 +11,8 @@ bit-for-bit against fixtures generated from the reference, tests/golden/):
   * ``_quantize_affine_no_zero_point``   (:600-690)
   * ``dequantize_affine`` / ``_dequantize_affine_tinygemm`` / ``_dequantize_affine_no_zero_point``
     (:779-1031)
+  * ``_choose_scale_float8`` / ``_quantize_affine_float8`` / ``_dequantize_affine_float8`` /
+    ``_expand_scale_to_tensor_shape``    (:2175-2312; float8 e4m3fn, fp32 scales)
 
 These run with torch ops on whatever device the weight lives on: they execute once at
 quantization time, outside the per-token hot loop (which is the HIP kernels behind torchao.ops).
@@ -34,6 +36,11 @@ __all__ = [
     "_quantize_affine_no_zero_point",
     "_dequantize_affine_no_zero_point",
     "_get_reduction_params",
+    "FP8_TYPES",
+    "_choose_scale_float8",
+    "_quantize_affine_float8",
+    "_dequantize_affine_float8",
+    "_expand_scale_to_tensor_shape",
 ]
 
 
@@ -374,6 +381,90 @@ def _dequantize_affine_tinygemm(
     if zero_point is not None:
         x += _qparam_view(zero_point, block_size, input.shape)[1]  # second rounding
     return x.view(input.shape).to(output_dtype)
+
+
+# ---------------------------------------------------------------------------------------------
+# float8 (reference quant_primitives.py:2175-2312)
+# ---------------------------------------------------------------------------------------------
+FP8_TYPES = {torch.float8_e4m3fn, torch.float8_e5m2, torch.float8_e4m3fnuz, torch.float8_e5m2fnuz}
+
+
+@torch.no_grad()
+def _choose_scale_float8(
+    tensor: torch.Tensor,
+    block_size: List[int],
+    float8_dtype: torch.dtype = torch.float8_e4m3fn,
+    scale_dtype: torch.dtype = torch.float32,
+    hp_value_lb: Optional[float] = None,
+    hp_value_ub: Optional[float] = None,
+) -> torch.Tensor:
+    """scale = amax|block| / finfo(float8_dtype).max, one per block (``block_size`` empty: one
+    for the tensor), returned in fp32 with shape ``tensor.shape // block_size``.
+
+    The division runs in the tensor's own dtype, as the reference's does: a bf16 weight gives
+    bf16(amax / 448) widened to fp32. It is a tensor-by-tensor (true) division on every device;
+    dividing by a Python scalar would let the GPU multiply by a reciprocal instead, and the CPU
+    and GPU scales could then differ in the last bit. No eps: an all-zero block gets scale 0.
+    ``hp_value_lb`` / ``hp_value_ub`` and the e8m0 scale dtype are not supported here."""
+    if hp_value_lb is not None or hp_value_ub is not None:
+        raise NotImplementedError("_choose_scale_float8: hp_value_lb / hp_value_ub are out of scope")
+    if scale_dtype is not torch.float32:
+        raise NotImplementedError("_choose_scale_float8: only float32 scales are supported")
+    quant_max = torch.finfo(float8_dtype).max
+    if len(block_size) == 0:
+        max_abs = tensor.abs().max()
+        return (max_abs / torch.full_like(max_abs, quant_max)).to(torch.float32)
+    view, red = _get_reduction_params(block_size, tensor.shape)
+    max_abs = tensor.view(view).abs().amax(dim=red, keepdim=True)
+    scale = max_abs / torch.full_like(max_abs, quant_max)
+    out_shape = [s // b for s, b in zip(tensor.shape, block_size)]
+    return scale.reshape(out_shape).to(torch.float32)
+
+
+def _expand_scale_to_tensor_shape(scale: torch.Tensor, target_shape: torch.Size) -> torch.Tensor:
+    """A per-block scale repeated over its blocks so it multiplies a ``target_shape`` tensor
+    elementwise (scalars and already-matching scales are returned as they are)."""
+    if scale.shape == target_shape or scale.numel() == 1:
+        return scale
+    if scale.dim() != len(target_shape):
+        raise ValueError(
+            f"Scale tensor has {scale.dim()} dimensions but target has {len(target_shape)}"
+        )
+    out = scale
+    for d, (t, s) in enumerate(zip(target_shape, scale.shape)):
+        if t % s != 0:
+            raise ValueError(
+                f"Dimension {d}: target size {t} is not evenly divisible by scale size {s}"
+            )
+        if t != s:
+            out = out.repeat_interleave(t // s, dim=d)
+    return out
+
+
+@torch.no_grad()
+def _quantize_affine_float8(
+    tensor: torch.Tensor,
+    scale: torch.Tensor,
+    float8_dtype: torch.dtype = torch.float8_e4m3fn,
+    cast_to_float8_dtype: bool = True,
+) -> torch.Tensor:
+    """q = float8(clamp(float(x) / scale, -max, max)): an fp32 true division, then the dtype's
+    round-to-nearest-even cast. 0 / 0 (an all-zero block) stays NaN through the clamp."""
+    scaled = tensor.to(torch.float32) / _expand_scale_to_tensor_shape(scale, tensor.shape)
+    max_value = torch.finfo(float8_dtype).max
+    clamped = scaled.clamp(min=-max_value, max=max_value)
+    return clamped.to(float8_dtype) if cast_to_float8_dtype else clamped
+
+
+@torch.no_grad()
+def _dequantize_affine_float8(
+    tensor: torch.Tensor,
+    scale: torch.Tensor,
+    output_dtype: torch.dtype = torch.float32,
+) -> torch.Tensor:
+    """x = float(q) * scale in fp32, then one rounding to ``output_dtype``."""
+    hp = tensor.to(torch.float32) * _expand_scale_to_tensor_shape(scale, tensor.shape)
+    return hp.to(output_dtype)
 
 
 # enums appear in flattened AQT metadata: allow weights_only=True checkpoint loads
