@@ -86,6 +86,49 @@ def test_gemv_forced_launch_shapes(rpw, wk, rg):
             assert "gemv" in _last_kernel()
 
 
+@pytest.mark.parametrize("K", [8224, 16416])  # 9 and 17 slices: 8 waves along K
+@pytest.mark.parametrize("rpw,wk,rg", [(4, 0, 8), (2, 0, 2)])
+def test_gemv_row_groups_clamped_to_the_workgroup(rpw, wk, rg, K):
+    """A tuning with waves_k = 0 passes tao_tune_int8_gemv whatever its row_groups, and the built-in
+    waves along K (min(slices, 8) here) times those row groups can exceed the 8 waves of a
+    workgroup: every int8 GEMV launcher halves the row groups until the workgroup fits, so the
+    linear runs (and stays exact) instead of failing its launch."""
+    from torchao._models.llama import kernels
+
+    with tuning(int8_gemv=(rpw, wk, rg)):
+        check(f"int8 gemv clamped rpw={rpw} wk={wk} g={rg}", 1, 37, K)
+        assert "gemv" in _last_kernel()
+        check(f"int8wo_decode clamped rpw={rpw} wk={wk} g={rg}", 1, 37, K, with_bias=False,
+              run=lambda x, w, scale, b: kernels.int8wo_decode(x, w, scale))
+
+
+@pytest.mark.parametrize("rpw,wk,rg", [(4, 0, 8), (2, 0, 2)])
+def test_int8dq_row_groups_clamped_to_the_workgroup(rpw, wk, rg):
+    """The same two tunings through the int8 dynamic-activation fused entry (its launcher makes
+    (4, 0, 8) 4 waves along K x 8 row groups at 9 slices) against its unfused chain on the built-in
+    shape: the int32 sums are exact, so any launch shape gives the same bits."""
+    import torch.nn as nn
+    from torchao._models.llama import kernels
+    from torchao._models.llama.model import _int8dq_parts
+    from torchao.quantization import Int8DynamicActivationInt8WeightConfig, quantize_
+
+    K = 8224
+    torch.manual_seed(K)
+    lin = nn.Linear(K, 38, bias=False, device=DEV, dtype=torch.bfloat16)
+    with torch.no_grad():
+        lin.weight.uniform_(-1 / K ** 0.5, 1 / K ** 0.5)
+    quantize_(lin, Int8DynamicActivationInt8WeightConfig())
+    parts = _int8dq_parts(lin)
+    assert parts is not None
+    x = torch.randn(1, 1, K, device=DEV, dtype=torch.bfloat16)
+    want_plain = lin(x)
+    # (the unfused SiLU-mul kernel takes an even number of outputs: run it on the 38 rows twice)
+    want_swiglu = kernels.silu_mul(torch.cat([want_plain, want_plain], -1))[..., :19]
+    with tuning(int8_gemv=(rpw, wk, rg)):
+        assert torch.equal(kernels.int8dq_decode(x, *parts), want_plain)
+        assert torch.equal(kernels.int8dq_decode(x, *parts, epilogue="swiglu"), want_swiglu)
+
+
 # ---- the MFMA kernel ------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("N,K", E.MFMA_NK)

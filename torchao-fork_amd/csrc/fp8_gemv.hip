@@ -6,14 +6,13 @@
 // GEMM; here the 1-B codes are read once. The scale is applied once per output instead of once
 // per weight.
 //
-// Same decomposition as int8_gemv.hip: a slice is 1024 k of one row = 64 lanes x 16 B; a wave
-// owns RPW rows; Wk waves split K inside a workgroup; LDS combines the waves.
+// The byte-weight decomposition of tao_gemv.h (a slice is 1024 k of one row); launcher and M
+// dispatcher are the ones shared with int8wo_gemv_kernel (wo8_gemv).
 // Per lane: one v_cvt_scalef32_pk_bf16_fp8 (scale 1.0: exact, all finite e4m3fn values are bf16
 // numbers) turns two codes into a bf16 pair, one v_dot2c_f32_bf16 multiplies it with the x pair
 // as loaded: 1.0 VALU per weight and no x conversion (v_cvt_pk_f32_fp8 + v_fma_f32 would be 1.5
 // plus the bf16 -> f32 shifts of x). No bias trick is needed: the codes decode signed.
-#include "tao_common.h"
-#include "tao_reduce.h"
+#include "tao_gemv.h"
 
 namespace tao {
 
@@ -95,70 +94,34 @@ __global__ __launch_bounds__(512) void fp8wo_gemv_kernel(
     for (int m = 0; m < MT; ++m) v[r * MT + m] = acc[r][m];
   wave_reduce_scatter<V>(v, lane);
 
-  constexpr int T = Log2<V>::value;
-  const bool owner = (lane & ((64 >> T) - 1)) == 0;
-  const int idx = lane >> (6 - T);
-  float total = v[0];
-  bool writer = owner;
-  int widx = idx;
-  if (Wk > 1) {
-    if (owner) red[(rg * Wk + wk) * V + idx] = v[0];
-    __syncthreads();
-    writer = (wk == 0) && (lane < V);
-    widx = lane;
-    if (writer) {
-      total = 0.f;
-      for (int kk = 0; kk < Wk; ++kk) total += red[(rg * Wk + kk) * V + widx];
-    }
-  }
-  if (writer) {
-    const int r = widx / MT, m = widx % MT;
+  const WgTotal<float> t = wg_combine<V>(v[0], red, lane, wk, rg, Wk);
+  if (t.writer) {
+    const int r = t.widx / MT, m = t.widx % MT;
     const int n = row0 + r;
     if (n < N && m < M) {
       // the fp32 sum times the fp32 scale, rounded once; then + bias, rounded again
-      float o = round_bf16(total * scale[n]);
+      float o = round_bf16(t.total * scale[n]);
       if (bias != nullptr) o = round_bf16(o + bf16_to_f32(bias[n]));
       y[(size_t)m * N + n] = f32_to_bf16(o);
     }
   }
 }
 
-template <int MT, int RPW>
-int launch_gemv(const uint16_t* x, const uint8_t* w, const float* scale, const uint16_t* bias,
-                uint16_t* y, int M, int N, int K, hipStream_t stream, int wk = 0, int g = 0) {
-  const int nchunk = K / 16;
-  const int S = (nchunk + 63) / 64;
-  int Wk = S < 8 ? S : 8;
-  int G = (8 / Wk) > 0 ? 8 / Wk : 1;
-  if (wk > 0) Wk = wk < S ? wk : S;
-  if (g > 0) G = g;
-  while (G > 1 && Wk * G > 8) G >>= 1;  // __launch_bounds__(512)
-  const int rows_per_wg = G * RPW;
-  const int grid = (N + rows_per_wg - 1) / rows_per_wg;
-  const size_t lds = (size_t)G * Wk * RPW * MT * sizeof(float);
-  launch((fp8wo_gemv_kernel<MT, RPW>), dim3(grid), dim3(64 * Wk * G), lds, stream, x,
-         reinterpret_cast<const uint4*>(w), scale, bias, y, M, N, K, Wk, G, S);
-  return check_launch("fp8wo_gemv_kernel");
-}
+struct Fp8Gemv {  // what wo8_gemv launches
+  using scale_t = float;
+  static constexpr const char* name = "fp8wo_gemv_kernel";
+  template <int MT, int RPW>
+  static auto kernel() {
+    return fp8wo_gemv_kernel<MT, RPW>;
+  }
+};
 
 }  // namespace
 
 int fp8wo_gemv(const uint16_t* x, const uint8_t* w, const float* scale, const uint16_t* bias,
                uint16_t* y, int64_t M, int64_t N, int64_t K, hipStream_t stream) {
-  if (M <= 1) {
-    // the int8 GEMV's M == 1 shape (same bytes, same decomposition: int8_gemv.hip): 4 rows per
-    // wave, Wk = min(S, 8), one row group per workgroup; tao_tune_fp8_gemv overrides
-    const int rpw = tuning().fp8_rpw, wk = tuning().fp8_wk;
-    const int tg = tuning().fp8_g, g = tg > 0 ? tg : 1;
-    if (rpw == 2)
-      return launch_gemv<1, 2>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream, wk, g);
-    if (rpw == 8)
-      return launch_gemv<1, 8>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream, wk, g);
-    return launch_gemv<1, 4>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream, wk, g);
-  }
-  if (M <= 2) return launch_gemv<2, 4>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream);
-  if (M <= 4) return launch_gemv<4, 2>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream);
-  return launch_gemv<8, 1>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream);
+  return wo8_gemv<Fp8Gemv>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream,
+                            tuning().fp8_rpw, tuning().fp8_wk, tuning().fp8_g);
 }
 
 }  // namespace tao

@@ -6,22 +6,17 @@
 // cap of tao_tune_linear_crossover. HBM-bound: every packed weight byte and every (scale, zero)
 // pair is read exactly once, with 16-B non-temporal loads; x (<= 8 x K bf16) stays in L1/L2.
 //
-// Work decomposition:
-//   * a "slice" is 2048 consecutive k of one row = 64 lanes x 32 k = one 1-KiB wave load
+// The work decomposition of tao_gemv.h, with
+//   * a "slice" of 2048 consecutive k of one row = 64 lanes x 32 k = one 1-KiB wave load
 //     (16 B of nibbles per lane) + one 256-B (scale, zero) load at group size 32;
-//   * a wave owns RPW rows and one slice at a time; a workgroup is G row-groups x Wk waves along
-//     K (Wk = min(slices, 8)); slices beyond Wk are looped;
 //   * per lane: D = sum x*(128+q) via v_dot2c_f32_bf16 on magic-number bf16 pairs (formed by
 //     byte permutes: 7 VALU per 8 weights), Sx = sum x, then s*(D - 136 Sx) + z*Sx per 32-k chunk —
-//     every 32-k chunk lies in exactly one quantisation group because g in {32..256};
-//   * cross-lane: reduce-scatter over the RPW*M partials (V/2 + V/4 + ... shuffles), then a
-//     butterfly over the remaining lanes; cross-wave: LDS, one wave finishes and writes y.
+//     every 32-k chunk lies in exactly one quantisation group because g in {32..256}.
 #include <atomic>
 #include <type_traits>
 
-#include "tao_common.h"
 #include "tao_attn.h"
-#include "tao_reduce.h"
+#include "tao_gemv.h"
 
 // The timing-only variant builds of rounds 1-5 (no x loads, no arithmetic, no (scale, zero)
 // loads, no reduction, per-workgroup s_memrealtime stamps, the RMSNorm-prologue variants and the
@@ -35,25 +30,13 @@ TAO_DECODE_ERROR_WORD(int4gemv_decode_status)
 
 namespace {
 
-// Decode-step fusions of the M == 1 GEMV (tao_int4wo_decode_bf16). They fold
-// the small ops around a Llama block's linears into the linear itself, so a decode token costs
-// fewer launches; each keeps the unfused kernels' op order and bf16 roundings
-// (decode_ops.hip: rmsnorm_kernel, silu_mul_kernel, rope_kv_kernel).
-//   PRO         x -> bf16(bf16(x * rsqrt(mean(x^2) + eps)) * norm_w) on the fly (RMSNorm,
-//               reference torchao/_models/llama/model.py RMSNorm.forward);
-//   kEpiSwiGLU  rows (2i, 2i+1) hold (w1_i, w3_i): y[i] = bf16(bf16(silu(a)) * b);
-//   kEpiRopeKV  rows = [q | k | v] heads of wqkv: q rotated into y, k rotated and v stored
-//               into the caches at pos[0] (Attention.forward + KVCache.update).
-enum { kEpiNone = 0, kEpiSwiGLU = 1, kEpiRopeKV = 2 };
+// Decode-step fusions of the M == 1 GEMV (tao_int4wo_decode_bf16; DecodeFuse in
+// tao_gemv.h). They fold the small ops around a Llama block's linears into the linear itself, so
+// a decode token costs fewer launches; each keeps the unfused kernels' op order and bf16
+// roundings (reference torchao/_models/llama/model.py: RMSNorm.forward, Attention.forward +
+// KVCache.update).
 constexpr int kMaxNormPT = 4;  // max 16-B pieces of x per thread in the RMSNorm prologue
-struct GemvFuse {
-  const uint16_t* norm_w;  // [K] RMSNorm weight (PRO)
-  float eps;
-  const float* freqs;      // [T][D/2] (cos, sin) pairs (kEpiRopeKV)
-  const int64_t* pos;
-  uint16_t* k_cache;       // [Hkv][T][D]
-  uint16_t* v_cache;
-  int H, Hkv, D, T;
+struct GemvFuse : DecodeFuse {
   int norm_deferred;  // PRO: 1 = stage bf16(x * w) and scale the outputs by r (see norm_finish)
   const float* merge;  // MRG: split attention partials [H][MRG][132] (tao_attn_decode_split_bf16)
 };
@@ -61,12 +44,6 @@ struct GemvFuse {
 __device__ __forceinline__ uint32_t mul_pair_bf16(uint32_t xv, uint32_t wv) {
   const float lo = bf16lo_to_f32(xv) * bf16lo_to_f32(wv);
   const float hi = bf16hi_to_f32(xv) * bf16hi_to_f32(wv);
-  return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
-}
-
-__device__ __forceinline__ uint32_t rmsnorm_pair(uint32_t xv, uint32_t wv, float r) {
-  const float lo = round_bf16(bf16lo_to_f32(xv) * r) * bf16lo_to_f32(wv);
-  const float hi = round_bf16(bf16hi_to_f32(xv) * r) * bf16hi_to_f32(wv);
   return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
 }
 
@@ -79,13 +56,6 @@ __device__ __forceinline__ uint32_t rmsnorm_pair(uint32_t xv, uint32_t wv, float
 // calls it).
 // COH (tao_int4wo_qkv_attn_bf16): the RoPE epilogue's q and cache stores are agent-scope (sc1)
 // stores, read by the same launch's attention workgroups after their ticket wait.
-__device__ __forceinline__ void st_coh(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t ld_coh(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 template <int MT, int RPW, bool PAIR, int NPT = 0, int EPI = kEpiNone, int MRG = 0,
           bool COH = false>
 __device__ __forceinline__ void gemv_body(
@@ -203,15 +173,8 @@ __device__ __forceinline__ void gemv_body(
     }
     float ss = 0.f;
 #pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const bool ok = threadIdx.x + u * (int)blockDim.x < nx;
-      const uint32_t d[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float a = ok ? bf16lo_to_f32(d[j]) : 0.f, b = ok ? bf16hi_to_f32(d[j]) : 0.f;
-        ss = fmaf(a, a, fmaf(b, b, ss));
-      }
-    }
+    for (int u = 0; u < NPT; ++u)
+      ss = sumsq_piece(xv[u], threadIdx.x + u * (int)blockDim.x < nx, ss);
     ss = wave_sum(ss);
     float* ssr = red + G * Wk * V;
     if (lane == 0) ssr[wave] = ss;
@@ -242,9 +205,7 @@ __device__ __forceinline__ void gemv_body(
       const int i = threadIdx.x + u * (int)blockDim.x;
       if (i < nx) {
         const int c = i >> 2;
-        xs[c * 4 + (((i & 3) + (c >> 2)) & 3)] =
-            make_uint4(rmsnorm_pair(xv[u].x, gv[u].x, r), rmsnorm_pair(xv[u].y, gv[u].y, r),
-                       rmsnorm_pair(xv[u].z, gv[u].z, r), rmsnorm_pair(xv[u].w, gv[u].w, r));
+        xs[c * 4 + (((i & 3) + (c >> 2)) & 3)] = rmsnorm_piece(xv[u], gv[u], r);
       }
     }
     __syncthreads();
@@ -381,81 +342,28 @@ __device__ __forceinline__ void gemv_body(
     for (int m = 0; m < MT; ++m) v[r * MT + m] = acc[r][m];
   wave_reduce_scatter<V>(v, lane);
 
-  constexpr int T = Log2<V>::value;
-  const bool owner = (lane & ((64 >> T) - 1)) == 0;
-  const int idx = lane >> (6 - T);
-
-  float total = v[0];
   if constexpr (PRO) {
     if (fu.norm_deferred && fu.norm_w != nullptr) {  // the deferred RMSNorm scale (norm_finish)
       const float* ssr = red + G * Wk * V;
       float t = 0.f;
       for (int w = 0; w < G * Wk; ++w) t += ssr[w];
-      const float rn = rsqrtf(t / (float)K + fu.eps);
-      total *= rn;
-      v[0] *= rn;
+      v[0] *= rsqrtf(t / (float)K + fu.eps);
     }
   }
-  bool writer = owner;
-  int widx = idx;
-  if (Wk > 1) {
-    if (owner) red[(rg * Wk + wk) * V + idx] = v[0];
-    __syncthreads();
-    writer = (wk == 0) && (lane < V);
-    widx = lane;
-    if (writer) {
-      total = 0.f;
-      for (int kk = 0; kk < Wk; ++kk) total += red[(rg * Wk + kk) * V + widx];
-    }
-  }
+  const WgTotal<float> t = wg_combine<V>(v[0], red, lane, wk, rg, Wk);
   if constexpr (EPI == kEpiNone) {
-    if (writer) {
-      const int r = widx / MT, m = widx % MT;
+    if (t.writer) {
+      const int r = t.widx / MT, m = t.widx % MT;
       const int n = row0 + r;
       if (n < N && m < M) {
-        uint16_t out = f32_to_bf16(total);
+        uint16_t out = f32_to_bf16(t.total);
         if (bias != nullptr) out = f32_to_bf16(bf16_to_f32(out) + bf16_to_f32(bias[n]));
         y[(size_t)m * N + n] = out;
       }
     }
   } else {
-    // Row pair (2p, 2p+1) meets in lane p of the writing wave. Row r's total sits in lane r
-    // (Wk > 1) or in owner lane r << (6 - T) (Wk == 1); every lane takes part in the shuffles.
-    const float o = round_bf16(total);
-    const int sh = Wk > 1 ? 0 : 6 - T;
-    const int pl = lane < RPW / 2 ? lane : 0;
-    const float a = __shfl(o, (2 * pl) << sh);
-    const float b = __shfl(o, (2 * pl + 1) << sh);
-    const int n = row0 + 2 * pl;
-    if ((Wk == 1 || wk == 0) && lane < RPW / 2 && n < N) {
-      if constexpr (EPI == kEpiSwiGLU) {
-        y[n >> 1] = f32_to_bf16(round_bf16(a / (1.f + __expf(-a))) * b);
-      } else {
-        const int D = fu.D, HD = fu.H * fu.D, KD = fu.Hkv * fu.D;
-        int64_t p = fu.pos[0];
-        const bool pok = p >= 0 && p < fu.T;  // KV cache row inside [0, T)
-        if (!pok) {  // report (tao_decode_status) and write no cache row
-          flag_decode_error(kDecodeErrKvPos);
-          p = p < 0 ? 0 : fu.T - 1;
-        }
-        uint32_t ov = (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
-        if (n < HD + KD) {
-          const float2 cs = reinterpret_cast<const float2*>(fu.freqs)[p * (D >> 1) + ((n % D) >> 1)];
-          const float o0 = a * cs.x - b * cs.y, o1 = b * cs.x + a * cs.y;
-          ov = (uint32_t)f32_to_bf16(o0) | ((uint32_t)f32_to_bf16(o1) << 16);
-        }
-        if (n < HD) {
-          if constexpr (COH) st_coh(reinterpret_cast<uint32_t*>(y) + (n >> 1), ov);
-          else reinterpret_cast<uint32_t*>(y)[n >> 1] = ov;
-        } else if (pok) {
-          const int nk = n < HD + KD ? n - HD : n - HD - KD;
-          uint16_t* cache = n < HD + KD ? fu.k_cache : fu.v_cache;
-          const size_t off = ((size_t)(nk / D) * fu.T + p) * D + nk % D;
-          if constexpr (COH) st_coh(reinterpret_cast<uint32_t*>(cache) + (off >> 1), ov);
-          else reinterpret_cast<uint32_t*>(cache)[off >> 1] = ov;
-        }
-      }
-    }
+    pair_epilogue<EPI, RPW, COH>(round_bf16(t.total), lane, wk, Wk, row0, N, y, fu,
+                                 [] { flag_decode_error(kDecodeErrKvPos); });
   }
 }
 
@@ -492,6 +400,11 @@ struct QkvAttn {
   float scale;
 };
 constexpr int kQaRec = 132;  // o[128], m, l, 2 pad
+
+// agent-scope (sc1) load: the consumer side of the GEMV's st_coh stores (tao_gemv.h)
+__device__ __forceinline__ uint32_t ld_coh(const uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 template <int NW, int NS>
 __device__ __forceinline__ void qkv_attn_tail(const GemvFuse& fu, const QkvAttn& qa,
@@ -990,38 +903,18 @@ extern "C" int tao_int4wo_decode_bf16(const uint16_t* x, const uint32_t* packed,
                                       int64_t max_seq, void* stream) {
   int rc = tao::int4_check_linear_args(x, packed, scales_and_zeros, y, 1, N, K, group_size);
   if (rc != TAO_OK) return rc;
-  TAO_CHECK_ARG(epilogue >= tao::kEpiNone && epilogue <= tao::kEpiRopeKV,
-                "int4 decode: epilogue must be 0 (none), 1 (swiglu) or 2 (rope_kv)");
-  TAO_CHECK_ARG(epilogue == tao::kEpiNone || N % 2 == 0, "int4 decode: N (%lld) must be even",
-                (long long)N);
+  rc = tao::check_decode_epilogue("int4 decode", epilogue, N);
+  if (rc != TAO_OK) return rc;
   if (norm_weight != nullptr) {
     TAO_CHECK_ALIGN(norm_weight, 16, "norm_weight");
     TAO_CHECK_ARG(K <= 8 * tao::kMaxNormPT * 512,
                   "int4 decode: RMSNorm prologue needs K <= %d", 8 * tao::kMaxNormPT * 512);
   }
   tao::GemvFuse fu{};
-  fu.norm_w = norm_weight;
-  fu.eps = eps;
+  rc = tao::check_decode_fuse("int4 decode", epilogue, N, norm_weight, eps, y, freqs, pos, k_cache,
+                              v_cache, n_head, n_kv_head, head_dim, max_seq, &fu);
+  if (rc != TAO_OK) return rc;
   fu.norm_deferred = tao::tuning().norm;
-  if (epilogue == tao::kEpiRopeKV) {
-    TAO_CHECK_ARG(n_head > 0 && n_kv_head > 0 && head_dim > 0 && head_dim % 2 == 0 &&
-                      max_seq > 0 && N == (n_head + 2 * n_kv_head) * head_dim,
-                  "int4 decode rope_kv: N (%lld) must be (n_head + 2 n_kv_head) * head_dim",
-                  (long long)N);
-    TAO_CHECK_ARG(freqs != nullptr && pos != nullptr && k_cache != nullptr && v_cache != nullptr,
-                  "int4 decode rope_kv: freqs, pos and caches are required");
-    TAO_CHECK_ALIGN(k_cache, 4, "k_cache");
-    TAO_CHECK_ALIGN(v_cache, 4, "v_cache");
-    TAO_CHECK_ALIGN(y, 4, "y");
-    fu.freqs = freqs;
-    fu.pos = pos;
-    fu.k_cache = k_cache;
-    fu.v_cache = v_cache;
-    fu.H = (int)n_head;
-    fu.Hkv = (int)n_kv_head;
-    fu.D = (int)head_dim;
-    fu.T = (int)max_seq;
-  }
   if (N == 0) return TAO_OK;
   const int gs = tao::gshift_of(group_size);
   hipStream_t st = tao::as_stream(stream);

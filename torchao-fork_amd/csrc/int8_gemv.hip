@@ -3,14 +3,13 @@
 // Replaces torch.mm(x, w.t().to(bf16)) * scale at torchao/dtypes/uintx/plain_layout.py:256-266,
 // which materialises a bf16 copy of W (2x the bytes) before a library GEMM; here W is read once.
 //
-// Same decomposition as int4_gemv.hip: a slice is 1024 k of one row = 64 lanes x 16 B (int8);
-// a wave owns RPW rows; Wk waves split K inside a workgroup; LDS combines the waves.
-// Per lane: bytes are biased to unsigned (xor 0x80), converted with v_cvt_f32_ubyte{0..3} and
-// FMA'd against x in f32; the bias is removed once per chunk as 128 * sum(x).
+// The byte-weight decomposition of tao_gemv.h (a slice is 1024 k of one row), and the M == 1
+// decode-step fusions. Per lane: bytes are biased to unsigned (xor 0x80), converted with
+// v_cvt_f32_ubyte{0..3} and FMA'd against x in f32; the bias is removed once per chunk as
+// 128 * sum(x).
 #include <atomic>
 
-#include "tao_common.h"
-#include "tao_reduce.h"
+#include "tao_gemv.h"
 
 namespace tao {
 
@@ -91,87 +90,91 @@ __global__ __launch_bounds__(512) void int8wo_gemv_kernel(
     for (int m = 0; m < MT; ++m) v[r * MT + m] = acc[r][m];
   wave_reduce_scatter<V>(v, lane);
 
-  constexpr int T = Log2<V>::value;
-  const bool owner = (lane & ((64 >> T) - 1)) == 0;
-  const int idx = lane >> (6 - T);
-  float total = v[0];
-  bool writer = owner;
-  int widx = idx;
-  if (Wk > 1) {
-    if (owner) red[(rg * Wk + wk) * V + idx] = v[0];
-    __syncthreads();
-    writer = (wk == 0) && (lane < V);
-    widx = lane;
-    if (writer) {
-      total = 0.f;
-      for (int kk = 0; kk < Wk; ++kk) total += red[(rg * Wk + kk) * V + widx];
-    }
-  }
-  if (writer) {
-    const int r = widx / MT, m = widx % MT;
+  const WgTotal<float> t = wg_combine<V>(v[0], red, lane, wk, rg, Wk);
+  if (t.writer) {
+    const int r = t.widx / MT, m = t.widx % MT;
     const int n = row0 + r;
     if (n < N && m < M) {
       // bf16 mm output, then bf16 * scale, then + bias: the reference's three roundings.
-      float o = round_bf16(round_bf16(total) * bf16_to_f32(scale[n]));
+      float o = round_bf16(round_bf16(t.total) * bf16_to_f32(scale[n]));
       if (bias != nullptr) o = round_bf16(o + bf16_to_f32(bias[n]));
       y[(size_t)m * N + n] = f32_to_bf16(o);
     }
   }
 }
 
-template <int MT, int RPW>
-int launch_gemv(const uint16_t* x, const int8_t* w, const uint16_t* scale, const uint16_t* bias,
-                uint16_t* y, int M, int N, int K, hipStream_t stream, int wk = 0, int g = 0) {
-  const int nchunk = K / 16;
-  const int S = (nchunk + 63) / 64;
-  int Wk = S < 8 ? S : 8;
-  int G = (8 / Wk) > 0 ? 8 / Wk : 1;
-  if (wk > 0) Wk = wk < S ? wk : S;
-  if (g > 0) G = g;
-  const int rows_per_wg = G * RPW;
-  const int grid = (N + rows_per_wg - 1) / rows_per_wg;
-  const size_t lds = (size_t)G * Wk * RPW * MT * sizeof(float);
-  launch((int8wo_gemv_kernel<MT, RPW>), dim3(grid), dim3(64 * Wk * G), lds, stream,
-                     x, reinterpret_cast<const uint4*>(w), scale, bias, y, M, N, K, Wk, G, S);
-  return check_launch("int8wo_gemv_kernel");
+struct Int8Gemv {  // what wo8_gemv launches
+  using scale_t = uint16_t;  // bf16
+  static constexpr const char* name = "int8wo_gemv_kernel";
+  template <int MT, int RPW>
+  static auto kernel() {
+    return int8wo_gemv_kernel<MT, RPW>;
+  }
+};
+
+// ---- pieces of int8wo_decode_kernel: the slice loader and the chunk arithmetic of int8wo_gemv_kernel
+// (written in place there: its M > 1 load schedule is sensitive to how the loop is written) ----
+// Slice s of rows row0 .. row0 + RPW: lane's chunk s * 64 + lane, row and chunk clamped in bounds.
+template <int RPW>
+__device__ __forceinline__ void load_w_slice(uint4 (&wv)[RPW], const uint4* __restrict__ w,
+                                             int row0, int N, int nchunk, int s, int lane) {
+  const int c = s * 64 + lane;
+  const int cc = c < nchunk ? c : nchunk - 1;
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int n = row0 + r;
+    wv[r] = ld_nt_u4(w + (size_t)(n < N ? n : N - 1) * nchunk + cc);
+  }
+}
+
+// 16 bf16 of x (two 16-B pieces; zeroed when !cval) as f32, and 128 * their sum
+struct I8ChunkX {
+  float xf[16];
+  float sx128;
+};
+__device__ __forceinline__ I8ChunkX i8_chunk_x(uint4 a, uint4 b, bool cval) {
+  const uint32_t d8[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  I8ChunkX x;
+  float t = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t di = cval ? d8[i] : 0u;
+    x.xf[2 * i] = bf16lo_to_f32(di);
+    x.xf[2 * i + 1] = bf16hi_to_f32(di);
+    t = dot2_bf16(di, 0x3F803F80u, t);
+  }
+  x.sx128 = 128.f * t;
+  return x;
+}
+// sum_k x[k] * w[k] over one chunk of int8 weights: the bytes are biased to unsigned (xor 0x80),
+// converted with v_cvt_f32_ubyte{0..3} and FMA'd against x in f32; the bias leaves as 128 * sum(x)
+__device__ __forceinline__ float i8_chunk_dot(const I8ChunkX& x, uint4 wv) {
+  const uint32_t wd[4] = {wv.x ^ 0x80808080u, wv.y ^ 0x80808080u, wv.z ^ 0x80808080u,
+                          wv.w ^ 0x80808080u};
+  float d = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    d = fmaf(x.xf[4 * j + 0], (float)(wd[j] & 0xFF), d);
+    d = fmaf(x.xf[4 * j + 1], (float)((wd[j] >> 8) & 0xFF), d);
+    d = fmaf(x.xf[4 * j + 2], (float)((wd[j] >> 16) & 0xFF), d);
+    d = fmaf(x.xf[4 * j + 3], (float)(wd[j] >> 24), d);
+  }
+  return d - x.sx128;
 }
 
 // ---- decode-step fusions of the M == 1 int8 weight-only GEMV (tao_int8wo_decode_bf16) -------
-// The int4 decode kernel's fusions (int4_gemv.hip) on the int8 weight stream, so
-// an int8wo Llama layer is 5 launches per token, as with int4 weights, instead of 9:
-//   PRO (NPT > 0)  x -> bf16(bf16(x * rsqrt(mean(x^2) + eps)) * norm_w), normalised once per
-//                  workgroup into LDS while the first weight slice is in flight;
-//   kI8EpiSwiGLU   rows (2i, 2i+1) = (w1_i, w3_i): y[i] = bf16(bf16(silu(a)) * b);
-//   kI8EpiRopeKV   rows = [q | k | v] heads: q rotated into y, k rotated and v stored into the
-//                  caches at pos[0] (a position outside [0, T) is reported, no cache row written).
-// a and b are the linear's own outputs bf16(bf16(sum) * scale[n]), so every result equals the
-// unfused chain (rmsnorm_kernel -> int8wo_gemv_kernel -> silu_mul / rope_kv) bit for bit, up to
-// the norm's fp32 sum order.
-enum { kI8EpiNone = 0, kI8EpiSwiGLU = 1, kI8EpiRopeKV = 2 };
-struct I8Fuse {
-  const uint16_t* norm_w;
-  float eps;
-  const float* freqs;  // [T][D/2] (cos, sin)
-  const int64_t* pos;
-  uint16_t* k_cache;  // [Hkv][T][D]
-  uint16_t* v_cache;
-  int H, Hkv, D, T;
-};
-
-__device__ __forceinline__ uint32_t i8_rmsnorm_pair(uint32_t xv, uint32_t wv, float r) {
-  const float lo = round_bf16(bf16lo_to_f32(xv) * r) * bf16lo_to_f32(wv);
-  const float hi = round_bf16(bf16hi_to_f32(xv) * r) * bf16hi_to_f32(wv);
-  return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
-}
+// The fusions of tao_gemv.h on the int8 weight stream, so an int8wo Llama layer
+// is 5 launches per token, as with int4 weights, instead of 9. NPT > 0: the RMSNorm prologue,
+// x normalised once per workgroup into LDS while the first weight slice is in flight. The
+// epilogues' a and b are the linear's own outputs bf16(bf16(sum) * scale[n]).
 
 template <int RPW, int NPT, int EPI>
 __global__ __launch_bounds__(512) void int8wo_decode_kernel(
     const uint16_t* __restrict__ x, const uint4* __restrict__ w,
     const uint16_t* __restrict__ scale, uint16_t* __restrict__ y, int N, int K, int Wk, int G,
-    int S, I8Fuse fu) {
+    int S, DecodeFuse fu) {
   constexpr bool PRO = NPT > 0;
   constexpr int V = RPW;
-  static_assert(RPW % 2 == 0, "row pairs stay inside one wave");
   // [G][Wk][V] partials | [16] wave sums of squares | (PRO) normalised x [K / 8] uint4
   extern __shared__ float red[];
   const int lane = threadIdx.x & 63;
@@ -197,28 +200,12 @@ __global__ __launch_bounds__(512) void int8wo_decode_kernel(
     }
   }
   uint4 wv[RPW];
-  auto load_w = [&](int s) __attribute__((always_inline)) {
-    const int c = s * 64 + lane;
-    const int cc = c < nchunk ? c : nchunk - 1;
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      const int n = row0 + r;
-      wv[r] = ld_nt_u4(w + (size_t)(n < N ? n : N - 1) * nchunk + cc);
-    }
-  };
-  load_w(wk);  // Wk <= S: every wave owns a slice
+  load_w_slice<RPW>(wv, w, row0, N, nchunk, wk, lane);  // Wk <= S: every wave owns a slice
   if constexpr (PRO) {
     float ss = 0.f;
 #pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const bool ok = threadIdx.x + u * (int)blockDim.x < nx;
-      const uint32_t d[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float a = ok ? bf16lo_to_f32(d[j]) : 0.f, b = ok ? bf16hi_to_f32(d[j]) : 0.f;
-        ss = fmaf(a, a, fmaf(b, b, ss));
-      }
-    }
+    for (int u = 0; u < NPT; ++u)
+      ss = sumsq_piece(xv[u], threadIdx.x + u * (int)blockDim.x < nx, ss);
     ss = wave_sum(ss);
     if (lane == 0) ssr[wave] = ss;
     __syncthreads();
@@ -230,10 +217,7 @@ __global__ __launch_bounds__(512) void int8wo_decode_kernel(
       const int i = threadIdx.x + u * (int)blockDim.x;
       // piece i of 16-k chunk c = i >> 1 lands at 2 c + ((i + (c >> 3)) & 1): consecutive lanes
       // read 32-B chunks, the rotation puts the two halves of a pass on distinct bank groups
-      if (i < nx)
-        xs[(i & ~1) | ((i + (i >> 4)) & 1)] =
-            make_uint4(i8_rmsnorm_pair(xv[u].x, gv[u].x, r), i8_rmsnorm_pair(xv[u].y, gv[u].y, r),
-                       i8_rmsnorm_pair(xv[u].z, gv[u].z, r), i8_rmsnorm_pair(xv[u].w, gv[u].w, r));
+      if (i < nx) xs[(i & ~1) | ((i + (i >> 4)) & 1)] = rmsnorm_piece(xv[u], gv[u], r);
     }
     __syncthreads();
   }
@@ -242,7 +226,7 @@ __global__ __launch_bounds__(512) void int8wo_decode_kernel(
 #pragma unroll
   for (int r = 0; r < RPW; ++r) acc[r] = 0.f;
   for (int s = wk; s < S; s += Wk) {
-    if (s != wk) load_w(s);
+    if (s != wk) load_w_slice<RPW>(wv, w, row0, N, nchunk, s, lane);
     const int c = s * 64 + lane;
     const bool cval = c < nchunk;
     const int cc = cval ? c : nchunk - 1;
@@ -256,127 +240,54 @@ __global__ __launch_bounds__(512) void int8wo_decode_kernel(
       a = xp[0];
       b = xp[1];
     }
-    const uint32_t d8[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    float xf[16];
-    float t = 0.f;
+    const I8ChunkX xc = i8_chunk_x(a, b, cval);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const uint32_t di = cval ? d8[i] : 0u;
-      xf[2 * i] = bf16lo_to_f32(di);
-      xf[2 * i + 1] = bf16hi_to_f32(di);
-      t = dot2_bf16(di, 0x3F803F80u, t);
-    }
-    const float sx128 = 128.f * t;
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      const uint32_t wd[4] = {wv[r].x ^ 0x80808080u, wv[r].y ^ 0x80808080u,
-                              wv[r].z ^ 0x80808080u, wv[r].w ^ 0x80808080u};
-      float d = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        d = fmaf(xf[4 * j + 0], (float)(wd[j] & 0xFF), d);
-        d = fmaf(xf[4 * j + 1], (float)((wd[j] >> 8) & 0xFF), d);
-        d = fmaf(xf[4 * j + 2], (float)((wd[j] >> 16) & 0xFF), d);
-        d = fmaf(xf[4 * j + 3], (float)(wd[j] >> 24), d);
-      }
-      acc[r] += d - sx128;
-    }
+    for (int r = 0; r < RPW; ++r) acc[r] += i8_chunk_dot(xc, wv[r]);
   }
 
   float v[V];
 #pragma unroll
   for (int r = 0; r < RPW; ++r) v[r] = acc[r];
   wave_reduce_scatter<V>(v, lane);
-  constexpr int T = Log2<V>::value;
-  const bool owner = (lane & ((64 >> T) - 1)) == 0;
-  float total = v[0];
-  int widx = lane >> (6 - T);  // the row this lane's total belongs to (owner lanes)
-  if (Wk > 1) {
-    if (owner) red[(rg * Wk + wk) * V + widx] = v[0];
-    __syncthreads();
-    widx = lane;
-    if (wk == 0 && lane < V) {
-      total = 0.f;
-      for (int kk = 0; kk < Wk; ++kk) total += red[(rg * Wk + kk) * V + lane];
-    }
-  }
-  // the linear's bf16 output of row widx (bf16 mm, then * scale, as int8wo_gemv_kernel)
-  const int nrow = row0 + (widx < V ? widx : 0);
-  const float o = round_bf16(round_bf16(total) * bf16_to_f32(scale[nrow < N ? nrow : N - 1]));
-  if constexpr (EPI == kI8EpiNone) {
-    const bool writer = Wk > 1 ? (wk == 0 && lane < V) : owner;
-    if (writer && row0 + widx < N) y[row0 + widx] = f32_to_bf16(o);
+  const WgTotal<float> t = wg_combine<V>(v[0], red, lane, wk, rg, Wk);
+  // the linear's bf16 output of row t.widx (bf16 mm, then * scale, as int8wo_gemv_kernel)
+  const int nrow = row0 + (t.widx < V ? t.widx : 0);
+  const float o = round_bf16(round_bf16(t.total) * bf16_to_f32(scale[nrow < N ? nrow : N - 1]));
+  if constexpr (EPI == kEpiNone) {
+    if (t.writer && row0 + t.widx < N) y[row0 + t.widx] = f32_to_bf16(o);
   } else {
-    // row pair (2p, 2p+1) meets in lane p (every lane takes part in the shuffles)
-    const int sh = Wk > 1 ? 0 : 6 - T;
-    const int pl = lane < RPW / 2 ? lane : 0;
-    const float ea = __shfl(o, (2 * pl) << sh);
-    const float eb = __shfl(o, (2 * pl + 1) << sh);
-    const int n = row0 + 2 * pl;
-    if ((Wk == 1 || wk == 0) && lane < RPW / 2 && n < N) {
-      if constexpr (EPI == kI8EpiSwiGLU) {
-        y[n >> 1] = f32_to_bf16(round_bf16(ea / (1.f + __expf(-ea))) * eb);
-      } else {
-        const int D = fu.D, HD = fu.H * fu.D, KD = fu.Hkv * fu.D;
-        int64_t p = fu.pos[0];
-        const bool pok = p >= 0 && p < fu.T;
-        if (!pok) {
-          flag_decode_error(kDecodeErrKvPos);
-          p = p < 0 ? 0 : fu.T - 1;
-        }
-        uint32_t ov = (uint32_t)f32_to_bf16(ea) | ((uint32_t)f32_to_bf16(eb) << 16);
-        if (n < HD + KD) {
-          const float2 cs = reinterpret_cast<const float2*>(fu.freqs)[p * (D >> 1) + ((n % D) >> 1)];
-          const float o0 = ea * cs.x - eb * cs.y, o1 = eb * cs.x + ea * cs.y;
-          ov = (uint32_t)f32_to_bf16(o0) | ((uint32_t)f32_to_bf16(o1) << 16);
-        }
-        if (n < HD) {
-          reinterpret_cast<uint32_t*>(y)[n >> 1] = ov;
-        } else if (pok) {
-          const int nk = n < HD + KD ? n - HD : n - HD - KD;
-          uint16_t* cache = n < HD + KD ? fu.k_cache : fu.v_cache;
-          const size_t off = ((size_t)(nk / D) * fu.T + p) * D + nk % D;
-          reinterpret_cast<uint32_t*>(cache)[off >> 1] = ov;
-        }
-      }
-    }
+    pair_epilogue<EPI, RPW>(o, lane, wk, Wk, row0, N, y, fu,
+                            [] { flag_decode_error(kDecodeErrKvPos); });
   }
 }
 
 template <int RPW, int NPT, int EPI>
 int launch_i8_decode(const uint16_t* x, const int8_t* w, const uint16_t* scale, uint16_t* y, int N,
-                     int K, int wk, int g, hipStream_t stream, const I8Fuse& fu) {
-  const int S = (K / 16 + 63) / 64;
-  const int Wk = wk < S ? wk : S;
-  const int threads = 64 * Wk * g;
-  const int grid = (N + g * RPW - 1) / (g * RPW);
-  const size_t lds = (((size_t)g * Wk * RPW + 16 + 3) & ~(size_t)3) * sizeof(float) +
+                     int K, GemvLaunchShape sh, hipStream_t stream, const DecodeFuse& fu) {
+  const int grid = (N + sh.G * RPW - 1) / (sh.G * RPW);
+  const size_t lds = (((size_t)sh.G * sh.Wk * RPW + 16 + 3) & ~(size_t)3) * sizeof(float) +
                      (NPT > 0 ? (size_t)K * 2 : 0);
-  launch((int8wo_decode_kernel<RPW, NPT, EPI>), dim3(grid), dim3(threads), lds, stream, x,
-         reinterpret_cast<const uint4*>(w), scale, y, N, K, Wk, g, S, fu);
+  launch((int8wo_decode_kernel<RPW, NPT, EPI>), dim3(grid), dim3(64 * sh.Wk * sh.G), lds, stream,
+         x, reinterpret_cast<const uint4*>(w), scale, y, N, K, sh.Wk, sh.G, sh.S, fu);
   return check_launch("int8wo_decode_kernel");
 }
 
 template <int EPI>
 int i8_decode(const uint16_t* x, const int8_t* w, const uint16_t* scale, uint16_t* y, int N, int K,
-              hipStream_t stream, const I8Fuse& fu) {
-  const int S = (K / 16 + 63) / 64;
-  // launch shape: Wk = min(S, 4) waves along K, G row groups, RPW rows per wave (tao_tune_int8_gemv
-  // overrides); the prologue needs K <= 8 x NPT x threads
+              hipStream_t stream, const DecodeFuse& fu) {
+  // launch shape: Wk = min(S, 4) waves along K, 2 row groups, RPW rows per wave (tao_tune_int8_gemv
+  // overrides); the prologue needs K <= 8 x NPT x threads and has 16 slots for the waves' sums
   const int trpw = tuning().i8_rpw, twk = tuning().i8_wk, tg = tuning().i8_g;
-  const int wk = twk > 0 ? twk : (S < 4 ? S : 4);
-  int g = tg > 0 ? tg : 2;
-  const int wke = wk < S ? wk : S;
-  while (wke * g < 8 && 64 * wke * g * 8 * 4 < K) g *= 2;
-  while (g > 1 && wke * g > 8) g /= 2;  // __launch_bounds__(512) and the prologue's 16 slots
-  const int threads = 64 * wke * g;
+  GemvLaunchShape sh = gemv_launch_shape(K / 16, twk > 0 ? twk : 4, tg > 0 ? tg : 2);
+  while (sh.Wk * sh.G * 2 <= 8 && 64 * sh.Wk * sh.G * 8 * 4 < K) sh.G *= 2;
+  const int threads = 64 * sh.Wk * sh.G;
   if (threads > 512)
-    return set_error(TAO_ERR_INVALID_ARGUMENT, "int8 decode: %d waves along K exceed 8", wke);
+    return set_error(TAO_ERR_INVALID_ARGUMENT, "int8 decode: %d waves along K exceed 8", sh.Wk);
   const bool pro = fu.norm_w != nullptr;
   if (pro && threads * 8 * 4 < K)
     return set_error(TAO_ERR_INVALID_ARGUMENT, "int8 decode: K (%d) too long for the RMSNorm prologue", K);
   const int npt = !pro ? 0 : (threads * 8 >= K ? 1 : threads * 8 * 2 >= K ? 2 : 4);
-#define TAO_I8D(R, P) return launch_i8_decode<R, P, EPI>(x, w, scale, y, N, K, wk, g, stream, fu)
+#define TAO_I8D(R, P) return launch_i8_decode<R, P, EPI>(x, w, scale, y, N, K, sh, stream, fu)
   if (trpw == 8) {
     if (npt == 0) TAO_I8D(8, 0);
     if (npt == 1) TAO_I8D(8, 1);
@@ -400,22 +311,8 @@ int i8_decode(const uint16_t* x, const int8_t* w, const uint16_t* scale, uint16_
 
 int int8wo_gemv(const uint16_t* x, const int8_t* w, const uint16_t* scale, const uint16_t* bias,
                 uint16_t* y, int64_t M, int64_t N, int64_t K, hipStream_t stream) {
-  if (M <= 1) {
-    const int rpw = tao::tuning().i8_rpw;
-    // one row group per workgroup at M == 1 (experiments/sweep_int8.py,
-    // profiles/r1_sweep_int8.jsonl: 4 rows per wave, Wk = min(S, 8), G = 1 is within 1% of the
-    // per-shape best on every Llama-3-8B linear; the head 77.8 -> 72.7 us)
-    const int wk = tao::tuning().i8_wk;
-    const int tg = tao::tuning().i8_g, g = tg > 0 ? tg : 1;
-    if (rpw == 2)
-      return launch_gemv<1, 2>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream, wk, g);
-    if (rpw == 8)
-      return launch_gemv<1, 8>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream, wk, g);
-    return launch_gemv<1, 4>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream, wk, g);
-  }
-  if (M <= 2) return launch_gemv<2, 4>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream);
-  if (M <= 4) return launch_gemv<4, 2>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream);
-  return launch_gemv<8, 1>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream);
+  return wo8_gemv<Int8Gemv>(x, w, scale, bias, y, (int)M, (int)N, (int)K, stream,
+                             tuning().i8_rpw, tuning().i8_wk, tuning().i8_g);
 }
 
 }  // namespace tao
@@ -429,41 +326,21 @@ extern "C" int tao_int8wo_decode_bf16(const uint16_t* x, const int8_t* w, const 
   using namespace tao;
   TAO_CHECK_ARG(N >= 0 && K > 0 && K % 16 == 0 && N < (1LL << 31) && K < (1LL << 31),
                 "int8 decode: K (%lld) must be a positive multiple of 16", (long long)K);
-  TAO_CHECK_ARG(epilogue >= kI8EpiNone && epilogue <= kI8EpiRopeKV,
-                "int8 decode: epilogue must be 0 (none), 1 (swiglu) or 2 (rope_kv)");
-  TAO_CHECK_ARG(epilogue == kI8EpiNone || N % 2 == 0, "int8 decode: N (%lld) must be even",
-                (long long)N);
+  int rc = check_decode_epilogue("int8 decode", epilogue, N);
+  if (rc != TAO_OK) return rc;
   TAO_CHECK_ALIGN(x, 16, "x");
   TAO_CHECK_ALIGN(w, 16, "w");
   TAO_CHECK_ALIGN(y, 2, "y");
-  I8Fuse fu{};
-  fu.norm_w = norm_weight;
-  fu.eps = eps;
   if (norm_weight != nullptr) TAO_CHECK_ALIGN(norm_weight, 16, "norm_weight");
-  if (epilogue == kI8EpiRopeKV) {
-    TAO_CHECK_ARG(n_head > 0 && n_kv_head > 0 && head_dim > 0 && head_dim % 2 == 0 &&
-                      max_seq > 0 && N == (n_head + 2 * n_kv_head) * head_dim,
-                  "int8 decode rope_kv: N (%lld) must be (n_head + 2 n_kv_head) * head_dim",
-                  (long long)N);
-    TAO_CHECK_ARG(freqs != nullptr && pos != nullptr && k_cache != nullptr && v_cache != nullptr,
-                  "int8 decode rope_kv: freqs, pos and caches are required");
-    TAO_CHECK_ALIGN(k_cache, 4, "k_cache");
-    TAO_CHECK_ALIGN(v_cache, 4, "v_cache");
-    TAO_CHECK_ALIGN(y, 4, "y");
-    fu.freqs = freqs;
-    fu.pos = pos;
-    fu.k_cache = k_cache;
-    fu.v_cache = v_cache;
-    fu.H = (int)n_head;
-    fu.Hkv = (int)n_kv_head;
-    fu.D = (int)head_dim;
-    fu.T = (int)max_seq;
-  }
+  DecodeFuse fu{};
+  rc = check_decode_fuse("int8 decode", epilogue, N, norm_weight, eps, y, freqs, pos, k_cache,
+                         v_cache, n_head, n_kv_head, head_dim, max_seq, &fu);
+  if (rc != TAO_OK) return rc;
   if (N == 0) return TAO_OK;
   const hipStream_t st = as_stream(stream);
   switch (epilogue) {
-    case kI8EpiSwiGLU: return i8_decode<kI8EpiSwiGLU>(x, w, scale, y, (int)N, (int)K, st, fu);
-    case kI8EpiRopeKV: return i8_decode<kI8EpiRopeKV>(x, w, scale, y, (int)N, (int)K, st, fu);
-    default: return i8_decode<kI8EpiNone>(x, w, scale, y, (int)N, (int)K, st, fu);
+    case kEpiSwiGLU: return i8_decode<kEpiSwiGLU>(x, w, scale, y, (int)N, (int)K, st, fu);
+    case kEpiRopeKV: return i8_decode<kEpiRopeKV>(x, w, scale, y, (int)N, (int)K, st, fu);
+    default: return i8_decode<kEpiNone>(x, w, scale, y, (int)N, (int)K, st, fu);
   }
 }
