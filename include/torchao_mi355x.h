@@ -164,6 +164,30 @@ int tao_fp8_quantize_rows_bf16(const uint16_t* w, uint8_t* q, float* scale, int6
 int tao_fp8_dequant_bf16(const uint8_t* q, const float* scale, uint16_t* w, int64_t N, int64_t K,
                          void* stream);
 
+/* ---- float8 (e4m3fn) dynamic activation x float8 weight, per-row scales --------------------- */
+
+/* y[m][n] = bf16( fp32(fp32(acc * xs[m]) * ws[n]) + fp32(bias[n]) ),
+ * acc[m][n] = sum_k f(xq[m][k]) * f(wq[n][k]) in fp32 (every product of two e4m3fn values is an
+ * fp32 number): one rounding to bf16, with or without bias, as a row-wise _scaled_mm epilogue is
+ * specified. xq uint8 [M][K] and wq uint8 [N][K] are OCP e4m3fn codes, xs f32 [M] the per-token
+ * and ws f32 [N] the per-row scales, bias bf16 [N] or NULL. A NaN code (an all-zero token or
+ * weight row quantises to scale 0.0 and NaN codes) makes its output row / column NaN.
+ * Replaces the torch._scaled_mm call of _linear_fp8_act_fp8_weight_impl at
+ * torchao/dtypes/floatx/float8_layout.py:329-367. K % 16 == 0 (the reference's _fp8_mm_compat),
+ * any N, M >= 0 (M == 0 is a no-op); xq, wq: 16-B aligned, each operand below 4 GiB. */
+int tao_fp8_scaled_mm_bf16(const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                           const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                           void* stream);
+
+/* One token (M <= 1): tao_fp8_quantize_rows_bf16 of the bf16 token x [K] and the product above in
+ * one launch, bit-identical to the two calls. Replaces _input_activation_quant_func_fp8
+ * (torchao/quantization/quant_api.py:1533-1571) followed by _linear_fp8_act_fp8_weight_impl
+ * (torchao/dtypes/floatx/float8_layout.py:329-367). More tokens are the two calls, the caller
+ * owning the code buffer between them (as for the int8 dynamic path). K % 16 == 0, K <= 65536. */
+int tao_fp8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const float* ws,
+                            const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                            void* stream);
+
 /* ---- int8 dynamic activation x int8 weight -------------------------------------------------- */
 
 /* Per-token symmetric reduced-range int8 quantization of x [M][K] bf16:

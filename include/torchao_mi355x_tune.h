@@ -195,8 +195,13 @@ int tao_tune_int4_norm(int mode);
 int tao_tune_int8_gemv(int rows_per_wave, int waves_k, int row_groups);
 /* Tuning hook: M == 1 launch shape of the fp8 weight-only GEMV (rows per wave 2/4/8, waves along
  * K, row groups per workgroup; waves_k * row_groups <= 8; 0 = built-in, the int8 GEMV's choice).
- * Calling thread only; for sweeps. */
+ * Also steers the M == 1 launches of the float8 dynamic-activation GEMV (tao_fp8_scaled_mm_bf16,
+ * tao_fp8_dyn_linear_bf16). Calling thread only; for sweeps. */
 int tao_tune_fp8_gemv(int rows_per_wave, int waves_k, int row_groups);
+/* Route of tao_fp8_scaled_mm_bf16: 0 = built-in (GEMV up to the crossover that
+ * tao_tune_linear_crossover moves, the MFMA kernel above it), 1 = the MFMA kernel at every M, so
+ * that tests and A/B runs reach it below the crossover too. Calling thread only. */
+int tao_tune_fp8dyn_mfma(int on);
 /* Per-token int8 quantisation kernel (A/B only): 0 = one wave per token, the token held in
  * registers (default, K <= 8192); 1 = one 256-thread workgroup per token. Bit-identical. */
 int tao_tune_int8_quant(int block);

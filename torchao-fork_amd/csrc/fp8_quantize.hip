@@ -15,8 +15,7 @@
 // reduction is a workgroup per row. hipcc keeps fp32 division correctly rounded by default
 // (v_div_scale / v_div_fmas / v_div_fixup; the Makefile passes no fast-math flag), which the
 // byte-for-byte match with the torch ops needs.
-#include "fp8_convert.h"
-#include "tao_common.h"
+#include "fp8_quant_row.h"
 #include "tao_reduce.h"
 
 namespace tao {
@@ -30,31 +29,15 @@ __global__ __launch_bounds__(256) void fp8_quantize_rows_kernel(const uint4* __r
   __shared__ float red[4];
   const uint4* row = w + (size_t)blockIdx.x * K8;
   float amax = 0.f;
-  for (int i = threadIdx.x; i < K8; i += 256) {
-    const uint4 v = row[i];
-    const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      amax = fmaxf(amax, fmaxf(fabsf(bf16lo_to_f32(d[j])), fabsf(bf16hi_to_f32(d[j]))));
-  }
+  for (int i = threadIdx.x; i < K8; i += 256) amax = fp8_amax8(row[i], amax);
   amax = wave_max(amax);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
   __syncthreads();
   amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float s = round_bf16(amax / 448.0f);
+  const float s = fp8_row_scale(amax);
   if (threadIdx.x == 0) scale[blockIdx.x] = s;
   uint2* qr = q + (size_t)blockIdx.x * K8;
-  for (int i = threadIdx.x; i < K8; i += 256) {
-    const uint4 v = row[i];
-    const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-    uint32_t o[2] = {0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float x = (j & 1) ? bf16hi_to_f32(d[j >> 1]) : bf16lo_to_f32(d[j >> 1]);
-      o[j >> 2] |= (uint32_t)f32_to_e4m3fn_rne(clamp_e4m3fn(x / s)) << (8 * (j & 3));
-    }
-    qr[i] = make_uint2(o[0], o[1]);
-  }
+  for (int i = threadIdx.x; i < K8; i += 256) qr[i] = fp8_quant8(row[i], s);
 }
 
 // One thread per 8 codes: 8-B load, 16-B store.

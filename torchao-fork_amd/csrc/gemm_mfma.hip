@@ -1,13 +1,15 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// four weight/activation formats share one kernel template:
+// five weight/activation formats share one kernel template:
 //   Int4WO  : bf16 x, int4 group-quant W (gfx950 row-stream layout), v_mfma_f32_16x16x32_bf16
 //   Int8WO  : bf16 x, int8 per-channel W,                            v_mfma_f32_16x16x32_bf16
 //   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
 //   Int8Dyn : int8 x (per-token scale), int8 W (per-channel scale),   v_mfma_i32_16x16x64_i8
+//   Fp8Dyn  : e4m3fn x (per-token scale), e4m3fn W (per-row scale),   v_mfma_scale_f32_16x16x128_f8f6f4
 // Replaces aten._weight_int4pack_mm (tensor_core_tiled_layout.py:104), mm(x, w.to(bf16)) * s
 // (plain_layout.py:256-266), int_scaled_matmul + scales (plain_layout.py:294-315,
-// kernel/intmm.py:108-143) and F.linear(x, w.dequantize()) (floatx/float8_layout.py:391-396).
+// kernel/intmm.py:108-143), F.linear(x, w.dequantize()) (floatx/float8_layout.py:391-396) and the
+// row-wise torch._scaled_mm of the float8 dynamic path (floatx/float8_layout.py:329-367).
 //
 // Tile: 4 waves x 16 output columns (BN = 64) x BM rows per k-group; each wave owns 16 columns
 // and all BM rows. K advances in macro-steps (256 bf16 k for int4, 128 bf16 k for int8-WO,
@@ -24,6 +26,7 @@
 #include <tuple>
 #include <type_traits>
 
+#include "fp8_dyn_host.h"
 #include "tao_common.h"
 
 // Experiment switch: ring depth override (experiments/gemm_depth.sh; 0 = the policy below).
@@ -456,6 +459,101 @@ struct Int8Dyn {
   }
 };
 
+// Fp8Dyn: e4m3fn x (per-token fp32 scale), e4m3fn W (per-row fp32 scale) on the block-scaled
+// v_mfma_scale_f32_16x16x128_f8f6f4 with E8M0 scale bytes 127 (2^0): a plain fp8 x fp8 MFMA with
+// K = 128, at twice the bf16 rate. Int8Dyn's tile structure (1-byte x, 256-k steps, full-line
+// weight loads through the per-wave stage, the same x image); an MFMA takes 32 B per lane of each
+// operand, two of the template's 16-B slots (kASlots = 2): MFMA u of a step reads slots 2u and
+// 2u + 1, i.e. lane (n, kq) holds k 128 u + 16 kq .. +16 and 128 u + 64 + 16 kq .. +16 on both
+// sides. Any such assignment is correct as long as A and B agree per lane group kq, because the
+// instruction pairs byte b of lane group kq of A with byte b of lane group kq of B
+// (tests/test_gpu_exact_fp8dyn.py settles it with asymmetric exact data). Either operand can hold
+// NaN codes (an all-zero token or weight row), so the weights past a K tail are zeroed as Fp8WO
+// does; x past the tail is zeroed at the LDS store.
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+struct Fp8Dyn {
+  static constexpr int kPathId = 4;  // no measured table entries: the heuristic shapes
+  static constexpr bool kMaskTail = true;
+  static constexpr int kABytes = 1;  // e4m3fn x
+  static constexpr int kKStep = 256;
+  static constexpr int kMfma = 2;
+  static constexpr int kASlots = 2;  // 16-B x slots per MFMA
+  static constexpr int kMaxBM = 128;
+  static constexpr int kPrefKG = 1;
+  static constexpr int kMaxKG = 2;
+  static constexpr int kMinSlice = 4;
+  typedef f32x4_t Acc;
+  const uint4* w;        // [N][K/16] e4m3fn codes
+  const float* wscale;   // [N] fp32
+  const float* xscale;   // [M] fp32
+  static constexpr int kStage = Int8Dyn::kStage;
+  typedef Int8Dyn::Lane Lane;
+  typedef Int8Dyn::Chunk Chunk;
+  typedef Int8Dyn::Prep Prep;  // v[s]: bytes 64 s + 16 kq of row n
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    return Int8Dyn{w, nullptr, nullptr}.setup(bn, lane, N, K);
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    return Int8Dyn{w, nullptr, nullptr}.load(L, st);
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    return Int8Dyn{w, nullptr, nullptr}.prep(ch, stage, lane);
+  }
+  // K % 16 == 0: each 16-B piece is wholly inside or wholly past the row (AND masks, no select)
+  static __device__ __forceinline__ void mask_tail(Prep& p, int st, int kq, int K) {
+    const int k0 = st * kKStep + 16 * kq;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const uint32_t k = k0 + 64 * s < K ? ~0u : 0u;
+      p.v[s] = make_uint4(p.v[s].x & k, p.v[s].y & k, p.v[s].z & k, p.v[s].w & k);
+    }
+  }
+  static __device__ __forceinline__ i32x8_t pair(const uint4& a, const uint4& b) {
+    return i32x8_t{(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y, (int)b.z, (int)b.w};
+  }
+  __device__ __forceinline__ i32x8_t frag(const Prep& p, int u) const {
+    return u == 0 ? pair(p.v[0], p.v[1]) : pair(p.v[2], p.v[3]);
+  }
+  static __device__ __forceinline__ int slot(int s, int kq) { return Int8Dyn::slot(s, kq); }
+  static __device__ __forceinline__ int xswz(int row) { return row & 15; }
+  static __device__ __forceinline__ Acc mfma2(const uint4& a0, const uint4& a1, const i32x8_t& b,
+                                              Acc c) {
+    // cbsz 0 / blgp 0: both operands e4m3; scale bytes 127 = 2^0
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(pair(a0, a1), b, c, 0, 0, 0,
+                                                            0x7F7F7F7F, 0, 0x7F7F7F7F);
+  }
+  // fp32(fp32(acc * xs) * ws); the bias add and the one bf16 rounding follow in the kernel. No
+  // contraction: the product must be rounded to fp32 before the bias is added (fp8_dyn.hip).
+  static constexpr bool kRowF = true, kColF = true;
+  __device__ __forceinline__ const float* row_factor() const { return xscale; }
+  __device__ __forceinline__ const float* col_factor() const { return wscale; }
+  __device__ __forceinline__ float epi(float acc, float xs, float ws) const {
+#pragma clang fp contract(off)
+    return (acc * xs) * ws;
+  }
+};
+
+// 16-B x slots one MFMA of the policy reads per lane (1 unless the policy says otherwise)
+template <class P, class = void>
+struct ASlots {
+  static constexpr int value = 1;
+};
+template <class P>
+struct ASlots<P, std::void_t<decltype(P::kASlots)>> {
+  static constexpr int value = P::kASlots;
+};
+
+// k-groups per workgroup the policy is built for (4 unless the policy says otherwise: Fp8Dyn's
+// 8 fragment registers per operand spill under the 1024-thread register cap)
+template <class P, class = void>
+struct MaxKG {
+  static constexpr int value = 4;
+};
+template <class P>
+struct MaxKG<P, std::void_t<decltype(P::kMaxKG)>> {
+  static constexpr int value = P::kMaxKG;
+};
+
 // LDS image of one x tile: [BM rows][16 slots of 16 B], slot XOR-swizzled with row & 15 so the
 // 16 rows of an A fragment read spread over all banks (cdna guide §5.5 T2).
 template <int SLOTS>
@@ -621,6 +719,19 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
         decltype(pol.frag(pw[0], s)) bfrag[NW];
 #pragma unroll
         for (int c = 0; c < NW; ++c) bfrag[c] = pol.frag(pw[c], s);
+        if constexpr (ASlots<P>::value == 2) {
+          // a 32-B A fragment: the two 16-B slots that hold the k of B fragment s
+          const int slot0 = P::slot(2 * s, kq), slot1 = P::slot(2 * s + 1, kq);
+#pragma unroll
+          for (int t = 0; t < MT; ++t) {
+            const int row = t * 16 + (lane & 15);
+            const uint4 a0 = xb[x_slot<SLOTS, P>(row, slot0)];
+            const uint4 a1 = xb[x_slot<SLOTS, P>(row, slot1)];
+#pragma unroll
+            for (int c = 0; c < NW; ++c)
+              acc[t * NW + c] = P::mfma2(a0, a1, bfrag[c], acc[t * NW + c]);
+          }
+        } else {
         const int slot = P::slot(s, kq);
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
@@ -629,6 +740,7 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
           const uint4 a = xb[x_slot<SLOTS, P>(row, slot)];
 #pragma unroll
           for (int c = 0; c < NW; ++c) acc[t * NW + c] = P::mfma(a, bfrag[c], acc[t * NW + c]);
+        }
         }
       }
     }
@@ -643,9 +755,23 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
   // (the int4 policy has neither factor; its bias stays an epilogue load: prefetching that too
   // measured 1.3 µs slower at M = 128, 4096², profiles/r2_ab_epi.txt)
   constexpr bool kPre = P::kRowF || P::kColF;
+  // (an fp32 row factor, Fp8Dyn's, is kept as floats)
+  constexpr bool kRowF32 =
+      P::kRowF && std::is_same_v<decltype(pol.row_factor()), const float*>;
   uint2 rowf[P::kRowF ? MT : 1];
+  float rowff[kRowF32 ? MT * 4 : 1];
   float colf[NW], biasf[NW];
-  if constexpr (P::kRowF) {
+  if constexpr (kRowF32) {
+    const float* rp = pol.row_factor();
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = m_blk + t * 16 + 4 * (lane >> 4) + i;
+        rowff[t * 4 + i] = rp[m < M ? m : M - 1];
+      }
+    }
+  } else if constexpr (P::kRowF) {
     const uint16_t* rp = pol.row_factor();
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -767,7 +893,9 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
           const int m = m_blk + t * 16 + 4 * (lane >> 4) + i;
           if (m < M) {
             float rf = 1.f;
-            if constexpr (P::kRowF) {
+            if constexpr (kRowF32) {
+              rf = rowff[t * 4 + i];
+            } else if constexpr (P::kRowF) {
               const uint32_t w = (i < 2) ? rowf[t].x : rowf[t].y;
               rf = (i & 1) ? bf16hi_to_f32(w) : bf16lo_to_f32(w);
             }
@@ -862,7 +990,7 @@ template <int BM, int KG, int NW, class P>
 void launch_one(dim3 grid, hipStream_t stream, const uint8_t* xb, const P& pol,
                 const uint16_t* bias, uint16_t* y, int M, int N, int K, int sps,
                 typename P::Acc* slab, unsigned* cnt) {
-  if constexpr (BM <= P::kMaxBM) {
+  if constexpr (BM <= P::kMaxBM && KG <= MaxKG<P>::value) {
     // ring depth: 4 steps, 3 where the per-stage registers grow (int8-dyn's 64-B pieces,
     // int4's 512-B x rows), 2 at BM >= 64
     constexpr bool big = sizeof(typename P::Chunk) > 32 || P::kABytes * P::kKStep > 256;
@@ -890,6 +1018,7 @@ int launch_gemm(const void* x, const P& pol, const uint16_t* bias, uint16_t* y, 
                       nw);
   }
   if (sh.nw == 32) sh.nw = 1;  // (the 32x32x16 kernel's entries are dispatched before this)
+  if (sh.kg > MaxKG<P>::value) sh.kg = MaxKG<P>::value;
   if (sh.nw == 2) {  // instantiated: BM <= 64, KG <= 2 (registers)
     if (sh.bm > 64) sh.bm = 64;
     if (sh.kg > 2) sh.kg = 2;
@@ -1524,6 +1653,21 @@ int gshift_of(int64_t g) {
 // shapes the plain linear runs on the single-fetch kernel
 bool int4_linear_takes_gemv(int64_t M, int64_t N, int64_t K) { return use_gemv(M, N, K); }
 
+// the float8 dynamic-activation route's crossover (rule and measurements: fp8_dyn_host.h)
+bool fp8dyn_takes_gemv(int64_t M, int64_t N, int64_t K) {
+  return fp8dyn_route_gemv(M, N, K, tuning().fp8dyn_mfma, tuning().max_gemv_m);
+}
+
+int fp8_scaled_mm_launch(const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                         const uint16_t* bias, uint16_t* y, int M, int N, int K,
+                         hipStream_t stream) {
+  Fp8Dyn pol;
+  pol.w = reinterpret_cast<const uint4*>(wq);
+  pol.wscale = ws;
+  pol.xscale = xs;
+  return launch_gemm(xq, pol, bias, y, M, N, K, stream);
+}
+
 int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq,
                           const uint16_t* ws, const uint16_t* bias, uint16_t* y, int M, int N,
                           int K, hipStream_t stream) {
@@ -1626,6 +1770,12 @@ extern "C" int tao_fp8wo_linear_bf16(const uint16_t* x, const uint8_t* w, const 
 extern "C" int tao_tune_linear_crossover(int max_gemv_m) {
   TAO_CHECK_ARG(max_gemv_m >= 0 && max_gemv_m <= 8, "tune: max_gemv_m must be in [0, 8]");
   tao::tuning().max_gemv_m = max_gemv_m;
+  return TAO_OK;
+}
+
+extern "C" int tao_tune_fp8dyn_mfma(int on) {
+  TAO_CHECK_ARG(on == 0 || on == 1, "tune: fp8dyn mfma must be 0 (built-in route) or 1");
+  tao::tuning().fp8dyn_mfma = on;
   return TAO_OK;
 }
 

@@ -1,7 +1,8 @@
 // torch dispatcher kernels (CUDA key = HIP on PyTorch-ROCm) for the quantized-linear ops that run
 // once per linear per forward: int4_weight_only_linear, int8_weight_only_linear,
-// int8_quantize_per_token, int8_scaled_mm, int8_dyn_linear, and the float8 weight-only set
-// fp8_weight_only_linear, fp8_quantize_rows, fp8_dequantize.
+// int8_quantize_per_token, int8_scaled_mm, int8_dyn_linear, the float8 weight-only set
+// fp8_weight_only_linear, fp8_quantize_rows, fp8_dequantize, and the float8 dynamic-activation set
+// fp8_scaled_mm, fp8_dyn_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -261,6 +262,70 @@ Tensor fp8_dequantize(const Tensor& q, const Tensor& scale) {
   return w;
 }
 
+// ---- float8 dynamic activation x float8 weight (ops.py _fp8_scaled_mm_cuda & co) ---------------
+Tensor fp8_scaled_mm(const Tensor& xq, const Tensor& x_scale, const Tensor& w_fp8,
+                     const Tensor& w_scale, const std::optional<Tensor>& bias) {
+  check_fp8_weight(w_fp8, w_scale);
+  const int64_t N = w_fp8.size(0), K = w_fp8.size(1);
+  TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn, "xq must be float8_e4m3fn");
+  TORCH_CHECK(xq.size(-1) == K, "x last dim ", xq.size(-1), " != K ", K);
+  TORCH_CHECK(K % 16 == 0, "K (", K, ") must be a multiple of 16");
+  check_device(xq, x_scale, "x_scale");
+  check_device(xq, w_fp8, "w_fp8");
+  check_device(xq, w_scale, "w_scale");
+  check_device(xq, bias, "bias");
+  const Tensor x2 = xq.reshape({-1, K}).contiguous();
+  const int64_t M = x2.size(0);
+  const Tensor xs = x_scale.reshape({-1}).to(at::kFloat).contiguous();
+  TORCH_CHECK(xs.numel() == M, "x_scale must have one entry per row");
+  const Tensor ws = w_scale.reshape({-1}).to(at::kFloat).contiguous();
+  const Tensor w = w_fp8.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(xq.device());
+  Tensor y = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
+  check_rc(tao_fp8_scaled_mm_bf16(cptr<uint8_t>(x2), cptr<float>(xs), cptr<uint8_t>(w),
+                                  cptr<float>(ws), b ? cptr<uint16_t>(*b) : nullptr,
+                                  mptr<uint16_t>(y), M, N, K, stream_of(xq)),
+           "tao_fp8_scaled_mm_bf16");
+  return y.reshape(out_shape(xq, N));
+}
+
+Tensor fp8_dyn_linear(const Tensor& x, const Tensor& w_fp8, const Tensor& w_scale,
+                      const std::optional<Tensor>& bias) {
+  check_fp8_weight(w_fp8, w_scale);
+  const int64_t N = w_fp8.size(0), K = w_fp8.size(1);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "fp8_dyn_linear (HIP) needs bf16 x");
+  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
+  TORCH_CHECK(K % 16 == 0, "K (", K, ") must be a multiple of 16");
+  check_device(x, w_fp8, "w_fp8");
+  check_device(x, w_scale, "w_scale");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const Tensor ws = w_scale.reshape({-1}).to(at::kFloat).contiguous();
+  const Tensor w = w_fp8.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  const uint16_t* bp = b ? cptr<uint16_t>(*b) : nullptr;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  if (M == 1 && K <= 65536) {
+    check_rc(tao_fp8_dyn_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(w), cptr<float>(ws), bp,
+                                     mptr<uint16_t>(y), 1, N, K, stream_of(x)),
+             "tao_fp8_dyn_linear_bf16");
+  } else if (M > 0) {
+    // the codes live in a buffer of the caching allocator between the two launches
+    Tensor q = at::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+    Tensor s = at::empty({M}, x.options().dtype(at::kFloat));
+    check_rc(tao_fp8_quantize_rows_bf16(cptr<uint16_t>(x2), mptr<uint8_t>(q), mptr<float>(s), M, K,
+                                        stream_of(x)),
+             "tao_fp8_quantize_rows_bf16");
+    check_rc(tao_fp8_scaled_mm_bf16(cptr<uint8_t>(q), cptr<float>(s), cptr<uint8_t>(w),
+                                    cptr<float>(ws), bp, mptr<uint16_t>(y), M, N, K, stream_of(x)),
+             "tao_fp8_scaled_mm_bf16");
+  }
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
@@ -272,6 +337,8 @@ TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
   m.impl("fp8_weight_only_linear", &fp8_weight_only_linear);
   m.impl("fp8_quantize_rows", &fp8_quantize_rows);
   m.impl("fp8_dequantize", &fp8_dequantize);
+  m.impl("fp8_scaled_mm", &fp8_scaled_mm);
+  m.impl("fp8_dyn_linear", &fp8_dyn_linear);
 }
 
 // Probe for torchao.ops (which ops this library serves).
@@ -283,4 +350,9 @@ extern "C" const char* tao_torch_ops_served(void) {
 // The float8 weight-only ops served here, listed apart from the integer per-linear set above.
 extern "C" const char* tao_torch_ops_served_float8(void) {
   return "fp8_weight_only_linear,fp8_quantize_rows,fp8_dequantize";
+}
+
+// The float8 dynamic-activation ops served here, a set of their own for the same reason.
+extern "C" const char* tao_torch_ops_served_float8_dyn(void) {
+  return "fp8_scaled_mm,fp8_dyn_linear";
 }

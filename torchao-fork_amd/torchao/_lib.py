@@ -87,6 +87,9 @@ _SIGNATURES = {
     "tao_fp8_quantize_rows_bf16": [_p, _p, _p, _i64, _i64, _p],
     "tao_fp8_dequant_bf16": [_p, _p, _p, _i64, _i64, _p],
     "tao_tune_fp8_gemv": [_int, _int, _int],
+    "tao_fp8_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_fp8_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_tune_fp8dyn_mfma": [_int],
     "tao_rmsnorm_bf16": [_p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_bf16": [_p, _p, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_partials_bf16": [_p, _p, _i64, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],

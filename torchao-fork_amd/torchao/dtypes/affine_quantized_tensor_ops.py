@@ -19,6 +19,8 @@ from torch.utils._python_dispatch import return_and_correct_aliasing
 
 from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
 from torchao.dtypes.floatx.float8_layout import (
+    _linear_fp8_act_fp8_weight_check,
+    _linear_fp8_act_fp8_weight_impl,
     _linear_fp_act_fp8_weight_check,
     _linear_fp_act_fp8_weight_impl,
 )
@@ -75,6 +77,7 @@ for _cond, _impl in [
     (_linear_fp_act_int8_weight_check, _linear_fp_act_int8_weight_impl),
     (_linear_bf16_act_uint4_weight_check, _linear_bf16_act_uint4_weight_impl),
     (_linear_fp_act_fp8_weight_check, _linear_fp_act_fp8_weight_impl),
+    (_linear_fp8_act_fp8_weight_check, _linear_fp8_act_fp8_weight_impl),
 ]:
     register_aqt_quantized_linear_dispatch(_cond, _impl)
 

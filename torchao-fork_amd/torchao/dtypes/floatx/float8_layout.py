@@ -5,18 +5,23 @@ float8 data and its fp32 scale as plain tensors plus a ``transposed`` flag; attr
 flatten order and module path are the reference's, so a ``state_dict`` it saved with
 ``Float8WeightOnlyConfig(version=1)`` loads here with ``torch.load(weights_only=True)``.
 
-One quantized-linear pair is registered from here (affine_quantized_tensor_ops.py), the float
-activation x float8 weight one (:370-396). The reference runs
-``F.linear(x, weight.dequantize(), bias)``: a bf16 copy of W is written and read back on every
-call. Here ``torch.ops.torchao.fp8_weight_only_linear`` reads the e4m3fn codes once (HIP GEMV up
-to the GEMV crossover, bf16-MFMA tiles above) and applies the per-row scale once per output.
+Two quantized-linear pairs are registered from here (affine_quantized_tensor_ops.py):
 
-Only per-row (per-output-channel) scaled e4m3fn weights are served; the float8 activation pair
-(``Float8DynamicActivationFloat8WeightConfig``), e5m2 and per-tensor scales are out of scope.
+* float activation x float8 weight (:370-396). The reference runs
+  ``F.linear(x, weight.dequantize(), bias)``: a bf16 copy of W is written and read back on every
+  call. Here ``torch.ops.torchao.fp8_weight_only_linear`` reads the e4m3fn codes once (HIP GEMV up
+  to the GEMV crossover, bf16-MFMA tiles above) and applies the per-row scale once per output.
+* float8 activation x float8 weight (:313-367, ``Float8DynamicActivationFloat8WeightConfig``).
+  The reference calls ``torch._scaled_mm`` with row-wise scales; here
+  ``torch.ops.torchao.fp8_scaled_mm`` runs the product on the fp8 matrix cores (HIP GEMV up to the
+  crossover) with both fp32 scales and the bias in one epilogue, rounded to bf16 once.
+
+Only per-row scaled e4m3fn operands are served; e5m2 and per-tensor scales are out of scope and
+raise.
 """
 
 from dataclasses import dataclass
-from typing import NamedTuple, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch.utils._python_dispatch import (
@@ -26,21 +31,13 @@ from torch.utils._python_dispatch import (
 
 from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor, register_layout
 from torchao.dtypes.utils import AQTTensorImpl, Layout
+from torchao.float8.inference import Float8MMConfig
 from torchao.quantization.quant_primitives import FP8_TYPES
 from torchao.utils import fill_defaults
 
 aten = torch.ops.aten
 
 __all__ = ["Float8MMConfig", "Float8Layout", "Float8AQTTensorImpl"]
-
-
-class Float8MMConfig(NamedTuple):
-    """Options of the reference's scaled-mm (float8 activation) path; carried for API and
-    checkpoint compatibility, unused by the weight-only linear."""
-
-    emulate: bool = False
-    use_fast_accum: bool = False
-    pad_inner_dim: bool = False
 
 
 @dataclass(frozen=True)
@@ -205,4 +202,40 @@ def _linear_fp_act_fp8_weight_impl(input_tensor, weight_tensor, bias):
     impl = weight_tensor.tensor_impl
     return torch.ops.torchao.fp8_weight_only_linear(
         input_tensor, impl.float8_data, impl.scale.reshape(-1), bias
+    )
+
+
+def _is_rowwise_scaled_nd(aqt) -> bool:
+    """One scale per row of a tensor of any rank (an activation [..., K]): block (1, ..., 1, K)."""
+    return tuple(aqt.block_size) == (1,) * (len(aqt.shape) - 1) + (aqt.shape[-1],)
+
+
+def _linear_fp8_act_fp8_weight_check(input_tensor, weight_tensor, bias) -> bool:
+    def check_aqt(aqt) -> bool:
+        return (
+            isinstance(aqt, AffineQuantizedTensor)
+            and isinstance(aqt._layout, Float8Layout)
+            and aqt.tensor_impl.dtype in FP8_TYPES
+            and (tuple(aqt.shape) == tuple(aqt.block_size) or _is_rowwise_scaled_nd(aqt))
+        )
+
+    return check_aqt(input_tensor) and check_aqt(weight_tensor)
+
+
+def _linear_fp8_act_fp8_weight_impl(input_tensor, weight_tensor, bias):
+    """y = bf16(((f(xq) @ f(wq)^T) * x_scale[m]) * w_scale[n] + bias) (reference :329-367, its
+    row-wise ``torch._scaled_mm``). Only per-row scaled e4m3fn operands with an untransposed
+    weight; anything else the check lets through raises (no quiet dequantize -> F.linear)."""
+    assert weight_tensor._layout.mm_config is not None
+    x_impl, w_impl = input_tensor.tensor_impl, weight_tensor.tensor_impl
+    if w_impl.transposed or x_impl.transposed:
+        raise NotImplementedError("float8 x float8 linear: a transposed operand is not supported")
+    if not (_is_rowwise_scaled_nd(input_tensor) and _is_rowwise_scaled(weight_tensor)):
+        raise NotImplementedError(
+            "float8 x float8 linear: only per-row scales (granularity=PerRow()) are supported"
+        )
+    if x_impl.dtype != torch.float8_e4m3fn or w_impl.dtype != torch.float8_e4m3fn:
+        raise NotImplementedError("float8 x float8 linear: only torch.float8_e4m3fn is supported")
+    return torch.ops.torchao.fp8_scaled_mm(
+        x_impl.float8_data, x_impl.scale, w_impl.float8_data, w_impl.scale.reshape(-1), bias
     )

@@ -28,6 +28,11 @@ Operators:
     ``F.linear(x, weight.dequantize(), bias)`` (floatx/float8_layout.py:391-396).
   * ``fp8_quantize_rows`` / ``fp8_dequantize`` — the per-row e4m3fn quantizer of
     ``from_hp_to_floatx`` and its dequant (quant_primitives.py:2175-2312), byte for byte.
+  * ``fp8_scaled_mm`` — e4m3fn x e4m3fn product with per-row scales on both operands; replaces
+    the ``torch._scaled_mm`` call of ``_linear_fp8_act_fp8_weight_impl``
+    (floatx/float8_layout.py:329-367).
+  * ``fp8_dyn_linear`` — the activation quantisation and that product from a bf16 input (one
+    token: one launch), bit-identical to ``fp8_quantize_rows`` -> ``fp8_scaled_mm``.
 """
 
 import ctypes
@@ -87,6 +92,17 @@ lib_float8.define(
 )
 lib_float8.define("fp8_quantize_rows(Tensor w) -> (Tensor, Tensor)")
 lib_float8.define("fp8_dequantize(Tensor q, Tensor scale) -> Tensor")
+
+# The float8 dynamic-activation ops, again on a fragment of their own (the two sets above are
+# enumerated by existing tests); opchecked in tests/test_gpu_float8_dyn.py.
+lib_float8_dyn = torch.library.Library("torchao", "FRAGMENT")
+lib_float8_dyn.define(
+    "fp8_scaled_mm(Tensor xq, Tensor x_scale, Tensor w_fp8, Tensor w_scale, "
+    "Tensor? bias=None) -> Tensor"
+)
+lib_float8_dyn.define(
+    "fp8_dyn_linear(Tensor x, Tensor w_fp8, Tensor w_scale, Tensor? bias=None) -> Tensor"
+)
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -691,6 +707,77 @@ def _fp8_dequantize_cuda(q: Tensor, scale: Tensor):
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# float8 (e4m3fn) dynamic activation x float8 weight, per-row scales
+# ---------------------------------------------------------------------------------------------
+@torch.library.register_fake("torchao::fp8_scaled_mm")
+def _(xq, x_scale, w_fp8, w_scale, bias=None):
+    N, K = _check_fp8_weight(w_fp8, w_scale)
+    torch._check(xq.size(-1) == K, lambda: f"x last dim {xq.size(-1)} != K {K}")
+    return xq.new_empty(_linear_out_shape(xq, N), dtype=torch.bfloat16)
+
+
+def _fp8_scaled_mm_cuda(xq, x_scale, w_fp8, w_scale, bias=None):
+    """y = bf16(((f(xq) @ f(w)^T) * x_scale[m]) * w_scale[n] + bias), fp32 up to the one
+    rounding (include/torchao_mi355x.h tao_fp8_scaled_mm_bf16)."""
+    N, K = _check_fp8_weight(w_fp8, w_scale)
+    torch._check(xq.dtype is torch.float8_e4m3fn, lambda: "xq must be float8_e4m3fn")
+    torch._check(xq.size(-1) == K, lambda: f"x last dim {xq.size(-1)} != K {K}")
+    torch._check(K % 16 == 0, lambda: f"K ({K}) must be a multiple of 16")
+    _same_device(xq, x_scale=x_scale, w_fp8=w_fp8, w_scale=w_scale, bias=bias)
+    x2 = xq.reshape(-1, K).contiguous()
+    M = x2.size(0)
+    xs = x_scale.reshape(-1).to(torch.float32).contiguous()
+    torch._check(xs.numel() == M, lambda: "x_scale must have one entry per row")
+    ws = w_scale.reshape(-1).to(torch.float32).contiguous()
+    w_fp8 = w_fp8.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    with torch.cuda.device(xq.device):
+        _lib.call("tao_fp8_scaled_mm_bf16", _ptr(x2), _ptr(xs), _ptr(w_fp8), _ptr(ws),
+                  _ptr(bias), _ptr(y), M, N, K, _stream(xq))
+    return y.reshape(_linear_out_shape(xq, N))
+
+
+@torch.library.register_fake("torchao::fp8_dyn_linear")
+def _(x, w_fp8, w_scale, bias=None):
+    N, K = _check_fp8_weight(w_fp8, w_scale)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N), dtype=torch.bfloat16)
+
+
+def _fp8_dyn_linear_cuda(x, w_fp8, w_scale, bias=None):
+    """The whole linear from a bf16 activation. One token: quantisation + GEMV in one launch.
+    More: fp8_quantize_rows (rows = tokens) into a buffer of the caching allocator, then
+    fp8_scaled_mm; bit-identical to calling the two ops."""
+    N, K = _check_fp8_weight(w_fp8, w_scale)
+    torch._check(x.dtype is torch.bfloat16, lambda: "fp8_dyn_linear (HIP) needs bf16 x")
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    torch._check(K % 16 == 0, lambda: f"K ({K}) must be a multiple of 16")
+    _same_device(x, w_fp8=w_fp8, w_scale=w_scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    ws = w_scale.reshape(-1).to(torch.float32).contiguous()
+    w_fp8 = w_fp8.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if M == 1 and K <= 65536:
+            _lib.call("tao_fp8_dyn_linear_bf16", _ptr(x2), _ptr(w_fp8), _ptr(ws), _ptr(bias),
+                      _ptr(y), 1, N, K, _stream(x))
+        elif M > 0:
+            q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+            s = torch.empty((M,), dtype=torch.float32, device=x.device)
+            _lib.call("tao_fp8_quantize_rows_bf16", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+            _lib.call("tao_fp8_scaled_mm_bf16", _ptr(q), _ptr(s), _ptr(w_fp8), _ptr(ws),
+                      _ptr(bias), _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
 # ---- register device impls ------------------------------------------------------------------
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
@@ -700,6 +787,7 @@ def _fp8_dequantize_cuda(q: Tensor, scale: Tensor):
 _OPS_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtorchao_ops.so")
 _native_served: frozenset = frozenset()
 _native_served_float8: frozenset = frozenset()
+_native_served_float8_dyn: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -713,6 +801,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_float8
         _served.restype = ctypes.c_char_p
         _native_served_float8 = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_float8_dyn
+        _served.restype = ctypes.c_char_p
+        _native_served_float8_dyn = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -726,6 +817,11 @@ def native_dispatch() -> frozenset:
 def native_dispatch_float8() -> frozenset:
     """The float8 weight-only ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_float8
+
+
+def native_dispatch_float8_dyn() -> frozenset:
+    """The float8 dynamic-activation ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_float8_dyn
 
 
 for _name, _fn in [
@@ -753,6 +849,12 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_float8:
         lib_float8.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("fp8_scaled_mm", _fp8_scaled_mm_cuda),
+    ("fp8_dyn_linear", _fp8_dyn_linear_cuda),
+]:
+    if _name not in _native_served_float8_dyn:
+        lib_float8_dyn.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")

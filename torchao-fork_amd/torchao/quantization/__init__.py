@@ -1,16 +1,19 @@
 """Quantization workflows on the MI355X weight-only linear path."""
 
 from torchao.quantization.fuse import fuse_gate_up_
+from torchao.quantization.granularity import PerRow, PerTensor
 from torchao.quantization.linear_activation_quantized_tensor import (
     LinearActivationQuantizedTensor,
     to_linear_activation_quantized,
 )
 from torchao.quantization.quant_api import (
+    Float8DynamicActivationFloat8WeightConfig,
     Float8WeightOnlyConfig,
     Int4WeightOnlyConfig,
     Int8DynamicActivationInt8WeightConfig,
     Int8WeightOnlyConfig,
     ModuleFqnToConfig,
+    float8_dynamic_activation_float8_weight,
     float8_weight_only,
     int4_weight_only,
     int8_dynamic_activation_int8_weight,
@@ -34,11 +37,15 @@ __all__ = [
     "Int8WeightOnlyConfig",
     "Int8DynamicActivationInt8WeightConfig",
     "Float8WeightOnlyConfig",
+    "Float8DynamicActivationFloat8WeightConfig",
+    "PerRow",
+    "PerTensor",
     "ModuleFqnToConfig",
     "int4_weight_only",
     "int8_weight_only",
     "int8_dynamic_activation_int8_weight",
     "float8_weight_only",
+    "float8_dynamic_activation_float8_weight",
     "LinearActivationQuantizedTensor",
     "to_linear_activation_quantized",
     "MappingType",

@@ -59,9 +59,10 @@ class LinearActivationQuantizedTensor(TorchAOBaseTensor):
     def _quantized_linear_op(input_tensor, weight_tensor, bias):
         if input_tensor.numel() == 0:
             return input_tensor
-        y = _fused_int8_dyn_decode(input_tensor, weight_tensor, bias)
-        if y is not None:
-            return y
+        for fused in _FUSED_ONE_TOKEN:
+            y = fused(input_tensor, weight_tensor, bias)
+            if y is not None:
+                return y
         qx = weight_tensor.input_quant_func(input_tensor, **weight_tensor.quant_kwargs)
         return torch.nn.functional.linear(qx, weight_tensor.original_weight_tensor, bias)
 
@@ -109,6 +110,40 @@ def _fused_int8_dyn_decode(x, weight_tensor, bias):
     impl = w.tensor_impl
     return torch.ops.torchao.int8_dyn_linear(x, impl.int_data, impl.scale.reshape(-1), bias)
 
+
+def _fused_fp8_dyn_decode(x, weight_tensor, bias):
+    """The same for Float8DynamicActivationFloat8WeightConfig(granularity=PerRow()): one bf16 token
+    on the GPU goes through ``torch.ops.torchao.fp8_dyn_linear`` (per-row e4m3fn quantisation +
+    fp8 x fp8 GEMV in one launch) without materialising the activation tensor, bit-identical to
+    quantising the input and dispatching to ``_linear_fp8_act_fp8_weight_impl``."""
+    from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
+    from torchao.dtypes.floatx.float8_layout import Float8Layout, _is_rowwise_scaled
+    from torchao.quantization.granularity import PerRow
+    from torchao.quantization.quant_api import _input_activation_quant_func_fp8
+
+    if weight_tensor.input_quant_func is not _input_activation_quant_func_fp8:
+        return None
+    kw = weight_tensor.quant_kwargs
+    if not (set(kw) == {"activation_granularity", "activation_dtype"}
+            and isinstance(kw["activation_granularity"], PerRow)
+            and kw["activation_dtype"] == torch.float8_e4m3fn and type(x) is torch.Tensor):
+        return None
+    K = x.shape[-1]
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and K % 16 == 0 and x.numel() == K
+            and K <= 65536):
+        return None
+    w = weight_tensor.original_weight_tensor
+    if not (isinstance(w, AffineQuantizedTensor) and isinstance(w._layout, Float8Layout)
+            and w._layout.mm_config is not None and w.tensor_impl.dtype == torch.float8_e4m3fn
+            and not w.tensor_impl.transposed and _is_rowwise_scaled(w) and w.shape[1] == K
+            and w.tensor_impl.float8_data.is_cuda):
+        return None
+    impl = w.tensor_impl
+    return torch.ops.torchao.fp8_dyn_linear(x, impl.float8_data, impl.scale.reshape(-1), bias)
+
+
+# the one-token recipes tried before the reference path, in order
+_FUSED_ONE_TOKEN = (_fused_int8_dyn_decode, _fused_fp8_dyn_decode)
 
 implements = LinearActivationQuantizedTensor.implements
 

@@ -21,7 +21,7 @@ Other workflows of the reference (float8 dynamic activation, ``Float8Tensor``, H
 import logging
 import types
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -33,10 +33,11 @@ from torchao.dtypes.affine_quantized_tensor import (
     to_affine_quantized_floatx,
     to_affine_quantized_intx,
 )
-from torchao.dtypes.floatx.float8_layout import Float8Layout
+from torchao.dtypes.floatx.float8_layout import Float8Layout, Float8MMConfig
 from torchao.dtypes.uintx.plain_layout import PlainAQTTensorImpl
 from torchao.dtypes.uintx.tensor_core_tiled_layout import TensorCoreTiledLayout
 from torchao.dtypes.utils import Layout, PlainLayout
+from torchao.quantization.granularity import Granularity, PerRow, PerTensor
 from torchao.quantization.linear_activation_quantized_tensor import (
     LinearActivationQuantizedTensor,
     to_linear_activation_quantized,
@@ -60,6 +61,8 @@ __all__ = [
     "int8_dynamic_activation_int8_weight",
     "Float8WeightOnlyConfig",
     "float8_weight_only",
+    "Float8DynamicActivationFloat8WeightConfig",
+    "float8_dynamic_activation_float8_weight",
     "ModuleFqnToConfig",
     "LAYOUT_TO_ZERO_POINT_DOMAIN",
     "LAYOUT_TO_PRESERVE_ZEROS",
@@ -460,3 +463,178 @@ def _float8_weight_only_transform(module: nn.Module, config: Float8WeightOnlyCon
         torchao.quantization.utils.recommended_inductor_config_setter()
     assert hasattr(module, "weight"), "float8 weight-only quant requires a module with a weight"
     return _swap_weight(module, _float8_weight_only_quant_tensor(module.weight, config))
+
+
+# ---------------------------------------------------------------------------------------------
+# float8 dynamic activation x float8 weight
+# ---------------------------------------------------------------------------------------------
+_FP8_DYN_SUPPORTED = (
+    "supported: granularity=PerRow() for both operands, torch.float8_e4m3fn activations and "
+    "weights, version=1 (AffineQuantizedTensor + Float8Layout), no activation value bounds"
+)
+
+
+def _normalize_granularity(granularity) -> Tuple[Granularity, Granularity]:
+    """``None`` -> per-tensor for both (the reference's default), one granularity -> both, a pair
+    -> (activation, weight), which must be of one kind."""
+    if granularity is None:
+        return PerTensor(), PerTensor()
+    if isinstance(granularity, (PerTensor, PerRow)):
+        return granularity, granularity
+    if isinstance(granularity, (tuple, list)) and len(granularity) == 2:
+        act, weight = granularity
+        if not all(isinstance(g, (PerTensor, PerRow)) for g in (act, weight)):
+            raise ValueError(f"Invalid granularity types: {granularity}, only PerTensor or PerRow")
+        if type(act) is not type(weight):
+            raise ValueError(
+                f"Different granularities for activation and weight are not supported: {granularity}"
+            )
+        return act, weight
+    raise ValueError(f"Invalid granularity specification: {granularity}, only PerTensor or PerRow")
+
+
+def _per_row_block_size(shape) -> Tuple[int, ...]:
+    return (1,) * (len(shape) - 1) + (shape[-1],)
+
+
+def _input_activation_quant_func_fp8(
+    x: torch.Tensor,
+    activation_granularity: Granularity,
+    activation_dtype: torch.dtype,
+    scale: Optional[torch.Tensor] = None,
+    zero_point: Optional[torch.Tensor] = None,
+):
+    """Dynamic per-row float8 quantization of a linear's input (reference quant_api.py:1533-1571):
+    an ``AffineQuantizedTensor`` with ``Float8Layout(mm_config=None)`` and block size
+    (1, ..., K). bf16 activations on the GPU run the fused HIP quantizer
+    (``torchao::fp8_quantize_rows``, rows = tokens) inside ``to_affine_quantized_floatx``."""
+    assert zero_point is None, "Zero point is not supported for dynamic FP8 quantization"
+    if not isinstance(activation_granularity, PerRow) or scale is not None:
+        raise NotImplementedError(
+            f"float8 activation quantization with {activation_granularity} / a static scale is "
+            f"out of scope; {_FP8_DYN_SUPPORTED}"
+        )
+    assert x.dtype == torch.bfloat16, (
+        "PerRow quantization only works for bfloat16 precision input activation"
+    )
+    return to_affine_quantized_floatx(
+        input_float=x,
+        block_size=_per_row_block_size(x.shape),
+        target_dtype=activation_dtype,
+        scale_dtype=torch.float32,
+        _layout=Float8Layout(mm_config=None),  # the mm config is stored on the weight
+    )
+
+
+def _fp8_mm_compat(weight: torch.Tensor) -> bool:
+    """Both weight dimensions multiples of 16, as the reference's scaled mm requires
+    (quant_api.py:1574-1598); an incompatible weight is left unquantized and logged."""
+    assert weight.dim() in (2, 3), (
+        f"float8 quantization only works for 2/3-D tensors, got {weight.dim()}D tensor"
+    )
+    out_dim, in_dim = weight.shape[-2:]
+    ok = in_dim % 16 == 0 and out_dim % 16 == 0
+    if not ok:
+        logger.info(
+            f"Skipping float8 quantization: weight shape {weight.shape} is not compatible with "
+            f"the scaled mm. Both input dimension ({in_dim}) and output dimension ({out_dim}) "
+            "must be multiples of 16."
+        )
+    return ok
+
+
+@dataclass
+class Float8DynamicActivationFloat8WeightConfig(AOBaseConfig):
+    """float8 (e4m3fn) dynamic per-row activation x float8 per-row weight (reference
+    :1601-1738): the activation is quantized per token on every call, the product runs on the
+    fp8 matrix cores (``torchao::fp8_scaled_mm``) and both fp32 scales are applied in the epilogue.
+
+    Fields are the reference's, in its order, without ``kernel_preference`` (this package has
+    one kernel). In scope: ``granularity=PerRow()`` (or a pair of them), e4m3fn for both operands,
+    ``version=1``. Everything else raises ``NotImplementedError`` when the config is applied:
+    ``PerTensor`` (which ``granularity=None`` means, as in the reference), ``version=2``
+    (``Float8Tensor``), e5m2 and ``activation_value_lb`` / ``activation_value_ub``.
+
+    Deviation from the reference: ``version`` defaults to **1**, for the reason given at
+    ``Float8WeightOnlyConfig``. The working spelling is
+    ``Float8DynamicActivationFloat8WeightConfig(granularity=PerRow())``.
+    """
+
+    activation_dtype: torch.dtype = torch.float8_e4m3fn
+    weight_dtype: torch.dtype = torch.float8_e4m3fn
+    granularity: Optional[Union[Granularity, List[Granularity]]] = None
+    mm_config: Optional[Float8MMConfig] = None
+    activation_value_lb: Optional[float] = None
+    activation_value_ub: Optional[float] = None
+    set_inductor_config: bool = True
+    version: int = 1
+
+    def __post_init__(self):
+        torch._C._log_api_usage_once(
+            "torchao.quantization.Float8DynamicActivationFloat8WeightConfig"
+        )
+        if self.mm_config is None:
+            self.mm_config = Float8MMConfig(use_fast_accum=True)
+        self.granularity = list(_normalize_granularity(self.granularity))
+
+
+float8_dynamic_activation_float8_weight = Float8DynamicActivationFloat8WeightConfig
+
+
+def _float8_dynamic_activation_float8_weight_quantize_tensor(weight, config):
+    activation_granularity, weight_granularity = config.granularity
+    refused = None
+    if config.version != 1:
+        refused = f"version={config.version} (Float8Tensor)"
+    elif not (isinstance(activation_granularity, PerRow) and isinstance(weight_granularity, PerRow)):
+        refused = f"granularity={config.granularity}"
+    elif config.activation_dtype != torch.float8_e4m3fn:
+        refused = f"activation_dtype={config.activation_dtype}"
+    elif config.weight_dtype != torch.float8_e4m3fn:
+        refused = f"weight_dtype={config.weight_dtype}"
+    elif config.activation_value_lb is not None or config.activation_value_ub is not None:
+        refused = "activation_value_lb / activation_value_ub"
+    if refused is not None:
+        raise NotImplementedError(
+            f"Float8DynamicActivationFloat8WeightConfig({refused}) is out of scope; "
+            f"{_FP8_DYN_SUPPORTED}"
+        )
+    if not _fp8_mm_compat(weight):
+        return weight
+    assert weight.dtype == torch.bfloat16, (
+        "PerRow quantization only works for bfloat16 precision input weight"
+    )
+    quantized_weight = to_affine_quantized_floatx(
+        input_float=weight,
+        block_size=_per_row_block_size(weight.shape),
+        target_dtype=config.weight_dtype,
+        scale_dtype=torch.float32,
+        _layout=Float8Layout(mm_config=config.mm_config),
+    )
+    return to_linear_activation_quantized(
+        quantized_weight,
+        _input_activation_quant_func_fp8,
+        quant_kwargs={
+            "activation_granularity": activation_granularity,
+            "activation_dtype": config.activation_dtype,
+        },
+    )
+
+
+@register_quantize_module_handler(Float8DynamicActivationFloat8WeightConfig)
+def _float8_dynamic_activation_float8_weight_transform(
+    module: nn.Module, config: Float8DynamicActivationFloat8WeightConfig
+) -> nn.Module:
+    assert hasattr(module, "weight"), (
+        "applying float8 dynamic activation quant requires module to have weight attribute"
+    )
+    # refusals and the bf16 requirement are raised before anything is touched
+    new_weight = _float8_dynamic_activation_float8_weight_quantize_tensor(module.weight, config)
+    if config.set_inductor_config:
+        torchao.quantization.utils.recommended_inductor_config_setter()
+    if new_weight is module.weight:
+        return module  # _fp8_mm_compat: left as it is
+    return _swap_weight(module, new_weight)
+
+
+torch.serialization.add_safe_globals([_input_activation_quant_func_fp8, Float8MMConfig])
