@@ -52,6 +52,29 @@ int main() {
               if (K <= 65536 && L.threads == 512) CHECK(L.per <= 16);
             }
           }
+  // the decode kernel's launches (tao_fp8dq_decode_bf16): at most 8 token pieces per thread, 4
+  // with the RMSNorm; row groups are added up to 8 waves before a K is refused
+  for (int K : Ks)
+    for (int N : Ns)
+      for (const auto& s : shapes)
+        for (int max_per : {4, 8}) {
+          const int rpw = s[0];
+          const Fp8DynLaunch L = fp8dyn_launch_shape(N, K, rpw, 1, s[1], s[2], true, max_per);
+          const Fp8DynLaunch L16 = fp8dyn_launch_shape(N, K, rpw, 1, s[1], s[2], true);
+          ++cases;
+          CHECK(L.Wk >= 1 && L.G >= 1 && L.Wk * L.G <= 8 && L.threads == 64 * L.Wk * L.G);
+          CHECK(L.S == (K / 16 + 63) / 64 && L.Wk == L16.Wk && L.G >= L16.G);
+          CHECK((long long)L.grid * L.G * rpw >= N && (long long)(L.grid - 1) * L.G * rpw < N);
+          CHECK(L.per >= 1 && (long long)L.per * L.threads * 8 >= K);
+          // a thread holds more than max_per pieces only where no further row group fits
+          if (L.per > max_per) CHECK(L.Wk * L.G * 2 > 8);
+          // the entry's K limits are served by the built-in shape (8 rows, 4 waves, 2 groups)
+          if (s[0] == 8 && s[1] == 4 && s[2] == 2 && K <= 4096 * max_per) CHECK(L.per <= max_per);
+          std::vector<unsigned char> lds(L.lds);
+          const size_t off = (((size_t)L.Wk * L.G * rpw + 8 + 3) & ~(size_t)3) * 4;
+          CHECK(off % 16 == 0 && off + (size_t)K == L.lds);
+          lds[off + K - 1] = 1;
+        }
   for (long long M : {0LL, 1LL, 2LL, 4LL, 5LL, 8LL, 9LL, 2147483647LL})
     for (long long N : {1LL, 4096LL, 14336LL, 2147483647LL})
       for (long long K : {16LL, 4096LL, 14336LL, 268435456LL})

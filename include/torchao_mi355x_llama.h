@@ -172,6 +172,40 @@ int tao_int8dq_decode_bf16(const uint16_t* x, const int8_t* w, const uint16_t* s
                            uint16_t* v_cache, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
                            int64_t max_seq, void* stream);
 
+/* One token through a float8 (e4m3fn) weight-only linear with its decode-step neighbours fused
+ * (the float8 counterpart of tao_int8wo_decode_bf16; csrc/fp8_gemv.hip). Operands of
+ * tao_fp8wo_linear_bf16 at M == 1 (x [K] bf16, w [N][K] e4m3fn codes, scale [N] fp32, no bias);
+ * norm_weight, eps, epilogue, freqs, pos, the caches and the head sizes as in
+ * tao_int8wo_decode_bf16. The linear's output is bf16(fp32(sum_k x'[k] * f(w[n][k])) * scale[n]),
+ * x' the (normalised) token, f the exact code decode, the sum in fp32: one rounding, as
+ * tao_fp8wo_linear_bf16 without bias; the epilogues act on that bf16 value. Each result equals
+ * rmsnorm -> tao_fp8wo_linear_bf16 -> silu_mul / rope_kv up to the fp32 sum orders.
+ * K % 32 == 0; K <= 16384 with norm_weight (the prologue holds the token in registers).
+ * Replaces, at decode, the RMSNorm / SiLU-mul / RoPE + KVCache.update ops around the reference's
+ * float8 weight-only linears (torchao/_models/llama/model.py; the linear itself is
+ * torchao/dtypes/floatx/float8_layout.py:391-396). */
+int tao_fp8wo_decode_bf16(const uint16_t* x, const uint8_t* w, const float* scale, int64_t N,
+                          int64_t K, const uint16_t* norm_weight, float eps, int epilogue,
+                          uint16_t* y, const float* freqs, const int64_t* pos, uint16_t* k_cache,
+                          uint16_t* v_cache, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
+                          int64_t max_seq, void* stream);
+
+/* The same decode-step fusions on the float8 dynamic-activation linear
+ * (Float8DynamicActivationFloat8WeightConfig, PerRow; one token; csrc/fp8_dyn.hip): the per-row
+ * e4m3fn quantisation of the (normalised) token inside the kernel, as tao_fp8_dyn_linear_bf16
+ * does for the plain token. Operands and epilogues as tao_fp8wo_decode_bf16. The linear's output
+ * is bf16(fp32(fp32(acc * xs) * scale[n])), acc = sum_k f(xq[k]) * f(w[n][k]) in fp32 and
+ * (xq, xs) the token's codes and scale (xs = float(bf16(amax / 448)), no eps): one rounding, as
+ * tao_fp8_dyn_linear_bf16 without bias. Equals rmsnorm -> tao_fp8_dyn_linear_bf16 -> silu_mul /
+ * rope_kv up to the fp32 sum orders. K % 16 == 0; K <= 32768, <= 16384 with norm_weight.
+ * Replaces, at decode, the ops around the reference's float8 dynamic-activation linears
+ * (model.py; the quantizer and the scaled mm are float8_layout.py:329-367). */
+int tao_fp8dq_decode_bf16(const uint16_t* x, const uint8_t* w, const float* scale, int64_t N,
+                          int64_t K, const uint16_t* norm_weight, float eps, int epilogue,
+                          uint16_t* y, const float* freqs, const int64_t* pos, uint16_t* k_cache,
+                          uint16_t* v_cache, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
+                          int64_t max_seq, void* stream);
+
 /* Decode-step fused int4 linear, M = 1: y = epilogue(rmsnorm(x) W^T) in one launch, with the
  * operands of tao_int4wo_linear_bf16 (x [K] bf16, packed [N][K/8], scales_and_zeros [N][K/g]).
  *   norm_weight  NULL: x is used as is; else [K] bf16 and x -> bf16(bf16(x * rsqrt(mean(x^2) +

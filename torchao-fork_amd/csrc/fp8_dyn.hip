@@ -23,6 +23,9 @@
 //      the GEMV on the codes. Bit-identical to tao_fp8_quantize_rows_bf16 -> tao_fp8_scaled_mm_bf16.
 //      More than one token is those two calls; the caller owns the code buffer between them (the
 //      convention of the int8 dynamic path: no scratch is allocated here).
+//   3. tao_fp8dq_decode_bf16 (one token, the Llama decode harness): 2 with an optional RMSNorm of
+//      the token before its quantisation and a SwiGLU or RoPE + KV-write row-pair epilogue
+//      (fp8dq_decode_kernel below).
 //
 // fp8dyn_gemv_kernel: the byte-weight decomposition of tao_gemv.h (a slice is 1024 k of one row).
 // Both code streams are decoded in hardware: v_cvt_scalef32_pk_bf16_fp8 with scale 1.0 is exact
@@ -38,6 +41,8 @@
 #pragma clang fp contract(off)
 
 namespace tao {
+
+TAO_DECODE_ERROR_WORD(fp8dyn_decode_status)
 
 int fp8_scaled_mm_launch(const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
                          const uint16_t* bias, uint16_t* y, int M, int N, int K,
@@ -248,6 +253,173 @@ int fp8dyn_gemv(Fp8DynGemvArgs a, hipStream_t stream) {
   return launch_gemv<8, 1, false>(a, 8, 8, stream);
 }
 
+// ---- decode-step fusions of the one-token launch (tao_fp8dq_decode_bf16) ---------------------
+// fp8dyn_gemv_kernel's FQ path (one token, quantised per row inside every workgroup) as a sibling
+// kernel with the fusions of tao_gemv.h: NORM, the RMSNorm of the token
+// before its quantisation (rmsnorm_kernel's two roundings, then amax / scale / codes on the
+// normalised bf16 values: the bytes tao_rmsnorm_bf16 -> tao_fp8_quantize_rows_bf16 produce up to
+// the norm's fp32 sum order), and the row-pair epilogues on the linear's own bf16 output
+// bf16((sum * xs) * ws[n]). NPT 16-B pieces of the token per thread (K <= 8 NPT threads), with
+// NORM as many of the norm weight beside them.
+struct Fp8DqDecodeArgs {
+  const uint16_t* x;  // the bf16 token [K]
+  const uint4* w;     // [N][K/16] e4m3fn codes
+  const float* ws;    // [N] fp32
+  uint16_t* y;
+  int N, K, Wk, G, S;
+  DecodeFuse fu;
+};
+
+template <int RPW, int NPT, int EPI, bool NORM>
+__global__ __launch_bounds__(512) void fp8dq_decode_kernel(Fp8DqDecodeArgs a) {
+  constexpr int V = RPW;
+  // [G][Wk][V] fp32 partials | [8] wave sums of squares, then wave maxima | the token's codes [K]
+  extern __shared__ float lds_f[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
+  const int wk = wave % a.Wk;
+  const int rg = wave / a.Wk;
+  const int row0 = (blockIdx.x * a.G + rg) * RPW;
+  const int K = a.K, N = a.N, S = a.S, Wk = a.Wk;
+  const int nchunk = K >> 4;  // 16-B (16-k) chunks per row
+  const int nvec = K >> 3;    // 16-B pieces of the bf16 token
+  const int nw = a.G * a.Wk;
+  float* wred = lds_f + nw * V;
+  uint4* xl = reinterpret_cast<uint4*>(lds_f + ((nw * V + 8 + 3) & ~3));
+
+  uint4 wv[RPW];
+  auto load_w = [&](int s) __attribute__((always_inline)) {
+    const int c = s * 64 + lane;
+    const int cc = c < nchunk ? c : nchunk - 1;
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      const int n = row0 + r;
+      wv[r] = ld_nt_u4(a.w + (size_t)(n < N ? n : N - 1) * nchunk + cc);
+    }
+  };
+
+  // The token's (and the norm weight's) pieces are loaded BEFORE the first slice's weights:
+  // vector loads retire in issue order, so the wait for x does not wait for the weights, and the
+  // norm, the amax, the barriers and the quantisation into LDS run under the weight loads' latency.
+  const uint4* xr = reinterpret_cast<const uint4*>(a.x);
+  uint4 xv[NPT], gv[NORM ? NPT : 1];
+#pragma unroll
+  for (int u = 0; u < NPT; ++u) {
+    const int i = threadIdx.x + u * (int)blockDim.x;
+    const int ic = i < nvec ? i : nvec - 1;  // clamped duplicates do not change the max
+    xv[u] = xr[ic];
+    if constexpr (NORM) gv[u] = reinterpret_cast<const uint4*>(a.fu.norm_w)[ic];
+  }
+  load_w(wk);  // Wk <= S: every wave owns a slice
+  if constexpr (NORM) {
+    float ss = 0.f;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u)
+      ss = sumsq_piece(xv[u], threadIdx.x + u * (int)blockDim.x < nvec, ss);
+    ss = wave_sum(ss);
+    if (lane == 0) wred[wave] = ss;
+    __syncthreads();
+    float t = 0.f;
+    for (int q = 0; q < nw; ++q) t += wred[q];
+    const float rn = rsqrtf(t / (float)K + a.fu.eps);
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) xv[u] = rmsnorm_piece(xv[u], gv[u], rn);
+    __syncthreads();  // wred is reused for the amax below
+  }
+  float m = 0.f;
+#pragma unroll
+  for (int u = 0; u < NPT; ++u) m = fp8_amax8(xv[u], m);
+  m = wave_max(m);
+  if (lane == 0) wred[wave] = m;
+  __syncthreads();
+  float amax = wred[0];
+  for (int q = 1; q < nw; ++q) amax = fmaxf(amax, wred[q]);
+  const float st = fp8_row_scale(amax);
+  uint2* xq = reinterpret_cast<uint2*>(xl);
+#pragma unroll
+  for (int u = 0; u < NPT; ++u) {
+    const int i = threadIdx.x + u * (int)blockDim.x;
+    if (i < nvec) xq[i] = fp8_quant8(xv[u], st);
+  }
+  __syncthreads();
+
+  float acc[RPW];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) acc[r] = 0.f;
+  for (int s = wk; s < S; s += Wk) {
+    if (s != wk) load_w(s);
+    const int c = s * 64 + lane;
+    if (c < nchunk) {  // tail lanes skip the math: clamped codes may be NaN
+      uint32_t xp[8];
+      fp8_chunk_bf16(xl[c], xp);
+#pragma unroll
+      for (int r = 0; r < RPW; ++r) {
+        uint32_t wp[8];
+        fp8_chunk_bf16(wv[r], wp);
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d = dot2_bf16(xp[i], wp[i], d);
+        acc[r] += d;
+      }
+    }
+  }
+
+  float v[V];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) v[r] = acc[r];
+  wave_reduce_scatter<V>(v, lane);
+  const WgTotal<float> t = wg_combine<V>(v[0], lds_f, lane, wk, rg, Wk);
+  // the linear's bf16 output of row t.widx: tao_fp8_dyn_linear_bf16's fp32 epilogue without bias
+  const int nrow = row0 + (t.widx < V ? t.widx : 0);
+  const float o = round_bf16((t.total * st) * a.ws[nrow < N ? nrow : N - 1]);
+  if constexpr (EPI == kEpiNone) {
+    if (t.writer && row0 + t.widx < N) a.y[row0 + t.widx] = f32_to_bf16(o);
+  } else {
+    pair_epilogue<EPI, RPW>(o, lane, wk, Wk, row0, N, a.y, a.fu,
+                            [] { flag_decode_error(kDecodeErrKvPos); });
+  }
+}
+
+template <int RPW, int NPT, int EPI, bool NORM>
+int launch_dq_decode_npt(const Fp8DqDecodeArgs& a, const Fp8DynLaunch& L, hipStream_t stream) {
+  launch((fp8dq_decode_kernel<RPW, NPT, EPI, NORM>), dim3(L.grid), dim3(L.threads), L.lds, stream,
+         a);
+  return check_launch("fp8dq_decode_kernel");
+}
+
+template <int RPW, int EPI>
+int launch_dq_decode(Fp8DqDecodeArgs a, int wk, int g, hipStream_t stream) {
+  const bool norm = a.fu.norm_w != nullptr;
+  const Fp8DynLaunch L = fp8dyn_launch_shape(a.N, a.K, RPW, 1, wk, g, true, norm ? 4 : 8);
+  a.S = L.S;
+  a.Wk = L.Wk;
+  a.G = L.G;
+  if (norm) {
+    if (L.per <= 1) return launch_dq_decode_npt<RPW, 1, EPI, true>(a, L, stream);
+    if (L.per <= 2) return launch_dq_decode_npt<RPW, 2, EPI, true>(a, L, stream);
+    if (L.per <= 4) return launch_dq_decode_npt<RPW, 4, EPI, true>(a, L, stream);
+  } else {
+    if (L.per <= 1) return launch_dq_decode_npt<RPW, 1, EPI, false>(a, L, stream);
+    if (L.per <= 2) return launch_dq_decode_npt<RPW, 2, EPI, false>(a, L, stream);
+    if (L.per <= 4) return launch_dq_decode_npt<RPW, 4, EPI, false>(a, L, stream);
+    if (L.per <= 8) return launch_dq_decode_npt<RPW, 8, EPI, false>(a, L, stream);
+  }
+  TAO_CHECK_ARG(false, "fp8dq decode: K (%d) too long for the token prologue of %d threads", a.K,
+                L.threads);
+  return TAO_OK;
+}
+
+// the fused launch's shape (gemv_m1<true>): 8 rows per wave, 4 waves along K, 2 row groups
+template <int EPI>
+int dq_decode(const Fp8DqDecodeArgs& a, hipStream_t stream) {
+  const int rpw = tuning().fp8_rpw > 0 ? tuning().fp8_rpw : 8;
+  const int wk = tuning().fp8_wk > 0 ? tuning().fp8_wk : 4;
+  const int g = tuning().fp8_g > 0 ? tuning().fp8_g : 2;
+  if (rpw == 2) return launch_dq_decode<2, EPI>(a, wk, g, stream);
+  if (rpw == 4) return launch_dq_decode<4, EPI>(a, wk, g, stream);
+  return launch_dq_decode<8, EPI>(a, wk, g, stream);
+}
+
 }  // namespace
 }  // namespace tao
 
@@ -295,6 +467,38 @@ int tao_fp8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const float* w
   Fp8DynGemvArgs a{x, nullptr, reinterpret_cast<const uint4*>(wq), ws, bias, y,
                    1, (int)N, (int)K, 0, 0, 0};
   return gemv_m1<true>(a, as_stream(stream));
+}
+
+int tao_fp8dq_decode_bf16(const uint16_t* x, const uint8_t* wq, const float* ws, int64_t N,
+                          int64_t K, const uint16_t* norm_weight, float eps, int epilogue,
+                          uint16_t* y, const float* freqs, const int64_t* pos, uint16_t* k_cache,
+                          uint16_t* v_cache, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
+                          int64_t max_seq, void* stream) {
+  int rc = check_decode_epilogue("fp8dq decode", epilogue, N);
+  if (rc != TAO_OK) return rc;
+  TAO_CHECK_ARG(N >= 0 && N < (1LL << 31) && K > 0 && K < (1LL << 31),
+                "fp8dq decode: K (%lld) must be positive and N, K below 2^31", (long long)K);
+  TAO_CHECK_ARG(K % 16 == 0, "fp8dq decode: K (%lld) must be a multiple of 16", (long long)K);
+  TAO_CHECK_ALIGN(x, 16, "x");
+  TAO_CHECK_ALIGN(wq, 16, "wq");
+  TAO_CHECK_ALIGN(y, 2, "y");
+  if (norm_weight != nullptr) TAO_CHECK_ALIGN(norm_weight, 16, "norm_weight");
+  TAO_CHECK_ALIGN(ws, 4, "ws");
+  TAO_CHECK_ARG(K <= (norm_weight != nullptr ? 16384 : 32768),
+                "fp8dq decode: K (%lld) must be <= 32768, <= 16384 with norm_weight (the token "
+                "prologue holds the token in registers)",
+                (long long)K);
+  Fp8DqDecodeArgs a{x, reinterpret_cast<const uint4*>(wq), ws, y, (int)N, (int)K, 0, 0, 0, {}};
+  rc = check_decode_fuse("fp8dq decode", epilogue, N, norm_weight, eps, y, freqs, pos, k_cache,
+                         v_cache, n_head, n_kv_head, head_dim, max_seq, &a.fu);
+  if (rc != TAO_OK) return rc;
+  if (N == 0) return TAO_OK;
+  const hipStream_t st = as_stream(stream);
+  switch (epilogue) {
+    case kEpiSwiGLU: return dq_decode<kEpiSwiGLU>(a, st);
+    case kEpiRopeKV: return dq_decode<kEpiRopeKV>(a, st);
+    default: return dq_decode<kEpiNone>(a, st);
+  }
 }
 
 }  // extern "C"

@@ -14,13 +14,16 @@ struct Fp8DynLaunch {
 };
 
 // rpw rows per wave, mt tokens per lane set, (wk, g) the wanted waves along K and row groups;
-// fq: the fused one-token launch (the token's codes live in LDS behind the partials)
+// fq: the fused one-token launch (the token's codes live in LDS behind the partials); max_per:
+// the most token pieces a thread of the kernel to be launched holds (fp8dyn_gemv_kernel 16; the
+// decode kernel 8, and 4 with the RMSNorm, whose weight pieces sit beside the token's)
 static inline Fp8DynLaunch fp8dyn_launch_shape(int N, int K, int rpw, int mt, int wk, int g,
-                                               bool fq) {
+                                               bool fq, int max_per = 16) {
   const GemvLaunchShape sh = gemv_launch_shape(K / 16, wk, g);
   Fp8DynLaunch L{sh.S, sh.Wk, sh.G, 0, 0, 0, 0};
-  // fq: the token must fit the workgroup's registers (K <= 8 x 16 pieces x threads)
-  while (fq && 64 * L.Wk * L.G * 8 * 16 < K && L.Wk * L.G * 2 <= 8) L.G *= 2;
+  // fq: the token must fit the workgroup's registers (K <= 8 x max_per pieces x threads); row
+  // groups are added while they fit 8 waves
+  while (fq && (int64_t)64 * L.Wk * L.G * 8 * max_per < K && L.Wk * L.G * 2 <= 8) L.G *= 2;
   const int rows_per_wg = L.G * rpw;
   L.grid = (int)(((int64_t)N + rows_per_wg - 1) / rows_per_wg);  // (N up to 2^31 - 1)
   const int nw = L.G * L.Wk;

@@ -1,7 +1,9 @@
 """End-to-end greedy decode harness: quantize_ a Llama model, prefill a prompt, decode tokens.
 
 Mirrors the reference's gpt-fast harness (torchao/_models/llama/generate.py: ``-q int4wo-<g>``
-/ ``int8wo`` / ``int8dq`` quantization at :395-430, prefill + one-token decode loop at
+/ ``int8wo`` / ``int8dq`` quantization at :395-430, ``float8wo`` / ``float8dq-row`` at :588-608
+(``float8dq`` / ``float8dq-tensor`` mean per-tensor scales there, which this package's config
+refuses with ``NotImplementedError``), prefill + one-token decode loop at
 :111-142, tokens/s and memory-bandwidth accounting at :985-1047) with the MI355X execution
 model in place of ``torch.compile(mode="reduce-overhead")`` (:865-875): the one-token decode
 step is captured once in a HIP graph and replayed, the next token and position advancing on
@@ -68,13 +70,19 @@ def build_model(name: str, device, dtype=torch.bfloat16, checkpoint_path: Option
 
 
 def apply_quantization(model: nn.Module, quantization: Optional[str]) -> nn.Module:
-    """``-q`` strings of the reference harness: int4wo-<g>, int8wo, int8dq (or none)."""
+    """``-q`` strings of the reference harness: int4wo-<g>, int8wo, int8dq, float8wo,
+    float8dq-row (or none). float8dq and float8dq-tensor are the reference's spellings of
+    per-tensor scales: the config's own NotImplementedError (it names PerRow) propagates."""
     if not quantization:
         return model
     from torchao.quantization import (
+        Float8DynamicActivationFloat8WeightConfig,
+        Float8WeightOnlyConfig,
         Int4WeightOnlyConfig,
         Int8DynamicActivationInt8WeightConfig,
         Int8WeightOnlyConfig,
+        PerRow,
+        PerTensor,
         quantize_,
     )
 
@@ -86,6 +94,12 @@ def apply_quantization(model: nn.Module, quantization: Optional[str]) -> nn.Modu
         quantize_(model, Int8WeightOnlyConfig())
     elif quantization == "int8dq":
         quantize_(model, Int8DynamicActivationInt8WeightConfig())
+    elif quantization == "float8wo":
+        quantize_(model, Float8WeightOnlyConfig())
+    elif quantization in ("float8dq", "float8dq-tensor", "float8dq-row"):
+        # the reference's parsing (generate.py:598-604): "-row" is PerRow, anything else PerTensor
+        granularity = PerRow() if quantization.endswith("-row") else PerTensor()
+        quantize_(model, Float8DynamicActivationFloat8WeightConfig(granularity=granularity))
     else:
         raise ValueError(f"unsupported quantization {quantization!r}")
     return model

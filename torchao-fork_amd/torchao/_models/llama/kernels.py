@@ -9,8 +9,8 @@ import torch
 from torchao import _lib
 
 __all__ = ["rmsnorm", "rope_kv", "attn_decode", "silu_mul", "int4_linear_swiglu",
-           "int4_linear_rope_kv", "int4_decode", "int8wo_decode", "int8dq_decode", "argmax",
-           "argmax_advance", "check_decode_status"]
+           "int4_linear_rope_kv", "int4_decode", "int8wo_decode", "int8dq_decode", "fp8wo_decode",
+           "fp8dq_decode", "argmax", "argmax_advance", "check_decode_status"]
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -518,6 +518,70 @@ def int8dq_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_we
     the (normalised) token is quantised per token inside the kernel (tao_int8dq_decode_bf16)."""
     return int8wo_decode(x, w, scale, norm_weight, eps, epilogue, rope,
                          _entry="tao_int8dq_decode_bf16")
+
+
+# The RMSNorm prologue of the float8 decode kernels holds the token and the norm weight in
+# registers: K <= FP8_NORM_MAX_K (tao_fp8wo_decode_bf16, tao_fp8dq_decode_bf16); the
+# dynamic-activation kernel holds the token there with or without the norm: K <= FP8DQ_MAX_K.
+FP8_NORM_MAX_K = 16384
+FP8DQ_MAX_K = 32768
+
+
+def fp8wo_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
+                 eps: float = 0.0, epilogue: str = "none", rope=None,
+                 _entry: str = "tao_fp8wo_decode_bf16") -> torch.Tensor:
+    """One token through a float8 weight-only linear (w [N, K] float8_e4m3fn, scale [N] fp32)
+    with the int4_decode fusions (tao_fp8wo_decode_bf16): optional RMSNorm of x; epilogue "none",
+    "swiglu" or "rope_kv" as in int4_decode.
+
+    Where the norm runs (experiments/bench_decode_fp8.py, profiles/fp8_decode_bench.jsonl; norm
+    inside the GEMV vs RMSNorm launch + GEMV, us): the weight-only kernel takes it inside at every
+    shape: wqkv 6144x4096 7.5 vs 9.1, w1||w3 28672x4096 20.4 vs 21.4, the 128256x4096 head 79.0 vs
+    79.3, 70B wqkv 10240x8192 17.7 vs 19.1, 70B w1||w3 57344x8192 74.3 vs 76.4. The
+    dynamic-activation kernel follows prologue_pays row for row: 10.5 vs 12.2, 25.4 vs 26.0 and
+    19.6 vs 21.2 (inside); the head 93.7 vs 86.0 and 70B w1||w3 80.2 vs 77.5 (own launch: every
+    workgroup also re-quantises the token). Past FP8_NORM_MAX_K the RMSNorm is its own launch."""
+    what = "fp8wo_decode" if _entry == "tao_fp8wo_decode_bf16" else "fp8dq_decode"
+    _check(x, torch.bfloat16, f"{what} x")
+    _check(w, torch.float8_e4m3fn, f"{what} w")
+    if w.dim() != 2:
+        raise RuntimeError(f"{what}: w must be [N, K], got {tuple(w.shape)}")
+    N, K = w.shape
+    if x.numel() != K:
+        raise RuntimeError(f"{what} takes one token, got x of shape {tuple(x.shape)}")
+    _check(scale, torch.float32, f"{what} scale")
+    if scale.numel() != N:
+        raise RuntimeError(f"{what}: {scale.numel()} scales for {N} rows")
+    if norm_weight is not None:
+        _check(norm_weight, torch.bfloat16, f"{what} norm_weight")
+        pays = _entry == "tao_fp8wo_decode_bf16" or prologue_pays(N, K)
+        if K > FP8_NORM_MAX_K or not pays:  # normalise in its own launch instead
+            x, norm_weight = rmsnorm(x, norm_weight, eps), None
+    epi = _EPILOGUES[epilogue]
+    freqs = pos = kc = vc = None
+    H = Hkv = D = T = 0
+    if epi == 2:
+        freqs, pos, kc, vc, H = rope
+        _, Hkv, T, D = kc.shape
+        y = torch.empty(1, H, 1, D, dtype=x.dtype, device=x.device)
+    elif epi == 1:
+        y = torch.empty(*x.shape[:-1], N // 2, dtype=x.dtype, device=x.device)
+    else:
+        y = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.call(_entry, x.data_ptr(), w.data_ptr(), scale.data_ptr(), N, K,
+              ptr(norm_weight), float(eps), epi, y.data_ptr(), ptr(freqs), ptr(pos), ptr(kc),
+              ptr(vc), H, Hkv, D, T, _stream(x))
+    return y
+
+
+def fp8dq_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
+                 eps: float = 0.0, epilogue: str = "none", rope=None) -> torch.Tensor:
+    """fp8wo_decode for the float8 dynamic-activation linear
+    (Float8DynamicActivationFloat8WeightConfig, PerRow): the (normalised) token is quantised per
+    row to e4m3fn inside the kernel (tao_fp8dq_decode_bf16)."""
+    return fp8wo_decode(x, w, scale, norm_weight, eps, epilogue, rope,
+                        _entry="tao_fp8dq_decode_bf16")
 
 
 def argmax(logits: torch.Tensor) -> torch.Tensor:

@@ -13,9 +13,9 @@ Decode-time structure for one process per GPU and HIP graphs (no tracing compile
   * ``enable_fused_kernels()`` (bf16, head_dim 128, GPU) switches one-token steps to the fused
     gfx950 kernels of csrc/decode_ops.hip: RMSNorm, RoPE + KV-cache write, flash-decoding
     attention, SiLU-mul, and the residual add folded into the wo / w2 linears as their bias
-    (bf16(x + bf16(W a)) is exactly the bias epilogue at M = 1); with int4 weights the norms,
-    RoPE + KV write and SwiGLU ride inside the wqkv / w13 / output GEMVs
-    (tao_int4wo_decode_bf16) — 6 launches per layer;
+    (bf16(x + bf16(W a)) is exactly the bias epilogue at M = 1); with int4, int8 or float8
+    weights the norms, RoPE + KV write and SwiGLU ride inside the wqkv / w13 / output GEMVs
+    (tao_int4wo_decode_bf16, tao_int8{wo,dq}_decode_bf16, tao_fp8{wo,dq}_decode_bf16);
   * fused prefill (S > 1 tokens): the linears on the MFMA GEMMs, RMSNorm, RoPE + KV-cache write
     and SiLU-mul on the same kernels (S rows each), ``F.scaled_dot_product_attention`` over the
     caches; ``prefill_next`` runs the output head at the last position only;
@@ -255,9 +255,71 @@ def _int8dq_parts(lin: Optional[nn.Linear]):
     return inner.tensor_impl.int_data, inner.tensor_impl.scale.reshape(-1)
 
 
+def _fp8_operands(aqt, k_multiple: int):
+    """(float8_data [N, K], scale [N]) of a per-row scaled e4m3fn AffineQuantizedTensor as the
+    float8 decode kernels read them, or None where that would take a per-call copy or cast (the
+    scale is not fp32 and contiguous, the codes are not contiguous) or K is no multiple of
+    ``k_multiple`` (the kernel's K rule)."""
+    impl = aqt.tensor_impl
+    data, scale = impl.float8_data, impl.scale
+    if not (data.is_cuda and data.dim() == 2 and data.is_contiguous()
+            and data.shape[1] % k_multiple == 0
+            and aqt.dtype == torch.bfloat16 and scale.dtype == torch.float32
+            and scale.is_contiguous() and scale.numel() == data.shape[0]):
+        return None
+    return data, scale.reshape(-1)
+
+
+def _fp8wo_parts(lin: Optional[nn.Linear]):
+    """(float8_data [N, K] e4m3fn, scale [N] fp32) of a float8 weight-only linear
+    (Float8WeightOnlyConfig) on the GPU, else None: the weight criteria of the F.linear dispatch
+    (_linear_fp_act_fp8_weight_check)."""
+    w = getattr(lin, "weight", None)
+    if w is None or lin.bias is not None or not w.is_cuda:
+        return None
+    from torchao.dtypes.floatx.float8_layout import _linear_fp_act_fp8_weight_check
+
+    if not _linear_fp_act_fp8_weight_check(torch.empty(0, dtype=torch.bfloat16), w, None):
+        return None
+    return _fp8_operands(w, 32)
+
+
+def _fp8dq_parts(lin: Optional[nn.Linear]):
+    """(float8_data [N, K] e4m3fn, scale [N] fp32) of a
+    Float8DynamicActivationFloat8WeightConfig(granularity=PerRow()) linear on the GPU, else None:
+    the recipe and weight criteria of the one-token dispatch (_fused_fp8_dyn_decode)."""
+    w = getattr(lin, "weight", None)
+    if w is None or lin.bias is not None or not w.is_cuda:
+        return None
+    from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
+    from torchao.dtypes.floatx.float8_layout import Float8Layout, _is_rowwise_scaled
+    from torchao.quantization.granularity import PerRow
+    from torchao.quantization.linear_activation_quantized_tensor import (
+        LinearActivationQuantizedTensor,
+    )
+    from torchao.quantization.quant_api import _input_activation_quant_func_fp8
+
+    if not (isinstance(w, LinearActivationQuantizedTensor)
+            and w.input_quant_func is _input_activation_quant_func_fp8):
+        return None
+    kw = w.quant_kwargs
+    if not (set(kw) == {"activation_granularity", "activation_dtype"}
+            and isinstance(kw["activation_granularity"], PerRow)
+            and kw["activation_dtype"] == torch.float8_e4m3fn):
+        return None
+    inner = w.original_weight_tensor
+    if not (isinstance(inner, AffineQuantizedTensor) and isinstance(inner._layout, Float8Layout)
+            and inner._layout.mm_config is not None
+            and inner.tensor_impl.dtype == torch.float8_e4m3fn
+            and not inner.tensor_impl.transposed and _is_rowwise_scaled(inner)):
+        return None
+    return _fp8_operands(inner, 16)
+
+
 def _fused_decode(x, lin, norm=None, epilogue="none", rope=None):
     """One token through ``lin`` with the decode fusions, on whichever fused kernel its weight
-    format has (int4 weight-only, int8 weight-only); None if neither applies."""
+    format has (int4 / int8 / float8 weight-only, int8 / float8 dynamic activation); None if
+    none applies."""
     from torchao._models.llama import kernels
 
     if x.numel() != x.shape[-1]:
@@ -273,6 +335,15 @@ def _fused_decode(x, lin, norm=None, epilogue="none", rope=None):
     pq = _int8dq_parts(lin)
     if pq is not None and (nw is None or x.shape[-1] <= 8192):
         return kernels.int8dq_decode(x, *pq, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
+    # float8: a normed linear past the prologue's K limit, or a dynamic-activation one past the
+    # kernel's own, takes the unfused path (as the int8dq branch above)
+    f8 = x.dtype == torch.bfloat16 and (nw is None or x.shape[-1] <= kernels.FP8_NORM_MAX_K)
+    pf = _fp8wo_parts(lin) if f8 else None
+    if pf is not None:
+        return kernels.fp8wo_decode(x, *pf, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
+    pf = _fp8dq_parts(lin) if f8 else None
+    if pf is not None and x.shape[-1] <= kernels.FP8DQ_MAX_K:
+        return kernels.fp8dq_decode(x, *pf, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
     return None
 
 
@@ -356,7 +427,7 @@ class Attention(nn.Module):
             y = kernels.int4_qkv_attn(x, *pq, norm.weight, norm.eps, freqs_table, input_pos,
                                       kv.k_cache, kv.v_cache, self.n_head, scale)
             return _linear_plus(y, self.wo, residual)
-        # RMSNorm -> wqkv -> RoPE + KV-cache write in one launch (int4 / int8 weight-only)
+        # RMSNorm -> wqkv -> RoPE + KV-cache write in one launch (int4 / int8 / float8 weights)
         q = None if norm is None else _fused_decode(
             x, self.wqkv, norm, "rope_kv", (freqs_table, input_pos, kv.k_cache, kv.v_cache,
                                             self.n_head))
@@ -434,7 +505,7 @@ class FeedForward(nn.Module):
                     and kernels.ffn_engine_supported(x.shape[-1], p13[0].shape[0] // 2, p13[2])):
                 return kernels.int4_ffn_engine(x, norm.weight, norm.eps, p13, p2)
         if norm is not None:
-            # RMSNorm -> w13 -> SwiGLU in one launch (int4 / int8 weight-only)
+            # RMSNorm -> w13 -> SwiGLU in one launch (int4 / int8 / float8 weights)
             g = None if self.w13 is None else _fused_decode(x, self.w13, norm, "swiglu")
             if g is not None:
                 return _linear_plus(g, self.w2, residual)
