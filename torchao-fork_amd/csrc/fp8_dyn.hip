@@ -494,11 +494,8 @@ int tao_fp8dq_decode_bf16(const uint16_t* x, const uint8_t* wq, const float* ws,
   if (rc != TAO_OK) return rc;
   if (N == 0) return TAO_OK;
   const hipStream_t st = as_stream(stream);
-  switch (epilogue) {
-    case kEpiSwiGLU: return dq_decode<kEpiSwiGLU>(a, st);
-    case kEpiRopeKV: return dq_decode<kEpiRopeKV>(a, st);
-    default: return dq_decode<kEpiNone>(a, st);
-  }
+  return dispatch_epilogue(
+      epilogue, [&](auto epi) { return dq_decode<decltype(epi)::value>(a, st); });
 }
 
 }  // extern "C"

@@ -923,20 +923,11 @@ extern "C" int tao_int4wo_decode_bf16(const uint16_t* x, const uint32_t* packed,
   // the experiment that separates the RMSNorm's cost from the LDS staging's
   const bool pro =
       norm_weight != nullptr || tao::tuning().xlds == 1;
-#define TAO_DEC(P, E) \
-  return tao::launch_decode<P, E>(x, packed, scales_and_zeros, y, iN, iK, gs, st, fu)
-  switch (epilogue) {
-    case tao::kEpiSwiGLU:
-      if (pro) TAO_DEC(true, tao::kEpiSwiGLU);
-      TAO_DEC(false, tao::kEpiSwiGLU);
-    case tao::kEpiRopeKV:
-      if (pro) TAO_DEC(true, tao::kEpiRopeKV);
-      TAO_DEC(false, tao::kEpiRopeKV);
-    default:
-      if (pro) TAO_DEC(true, tao::kEpiNone);
-      TAO_DEC(false, tao::kEpiNone);
-  }
-#undef TAO_DEC
+  return tao::dispatch_epilogue(epilogue, [&](auto epi) {
+    constexpr int E = decltype(epi)::value;
+    if (pro) return tao::launch_decode<true, E>(x, packed, scales_and_zeros, y, iN, iK, gs, st, fu);
+    return tao::launch_decode<false, E>(x, packed, scales_and_zeros, y, iN, iK, gs, st, fu);
+  });
 }
 
 extern "C" int tao_int4wo_attn_out_bf16(const float* partial, int64_t splits, int64_t n_head,

@@ -496,11 +496,8 @@ int tao_int8dq_decode_bf16(const uint16_t* x, const int8_t* wq, const uint16_t* 
   if (rc != TAO_OK) return rc;
   if (N == 0) return TAO_OK;
   const hipStream_t st = as_stream(stream);
-  switch (epilogue) {
-    case kEpiSwiGLU: return dyn_gemv_m1<true, kEpiSwiGLU>(a, st);
-    case kEpiRopeKV: return dyn_gemv_m1<true, kEpiRopeKV>(a, st);
-    default: return dyn_gemv_m1<true>(a, st);
-  }
+  return dispatch_epilogue(
+      epilogue, [&](auto epi) { return dyn_gemv_m1<true, decltype(epi)::value>(a, st); });
 }
 
 int tao_tune_int8_gemv(int rows_per_wave, int waves_k, int row_groups) {

@@ -11,11 +11,20 @@
 //     cross-wave: LDS, wave wk == 0 of each row group finishes and writes (wg_combine);
 //   * the M == 1 decode entries fuse the RMSNorm of x as a prologue (staged once per workgroup
 //     in LDS under the first slice's load latency) and SwiGLU or RoPE + KV-cache write as a
-//     row-pair epilogue (DecodeFuse, pair_epilogue).
-// Each file keeps what is its own: the per-slice arithmetic, the prologue's LDS layout and the
-// launch-shape defaults. The byte-weight (int8 / fp8) weight-only GEMVs share launcher and M
-// dispatcher (wo8_gemv).
+//     row-pair epilogue (DecodeFuse, pair_epilogue); all five entries pick the
+//     epilogue's instantiation through dispatch_epilogue.
+// Each file keeps what is its own: the per-slice arithmetic, the prologue's LDS layout and its
+// entries' argument checks. The byte-weight (int8 / fp8) weight-only kernels share
+//   * at M >= 1 the launcher and M dispatcher of the plain GEMVs (wo8_gemv; one __global__
+//     function per format, see there);
+//   * at M == 1 with the decode fusions one kernel and one host path: wo8_decode_kernel over a
+//     format policy (Int8Decode in int8_gemv.hip, Fp8Decode in fp8_gemv.hip: the chunk arithmetic,
+//     whether tail lanes skip it, the scale type and the final rounding), wo8_decode_shape (the
+//     launch shape as a plain function of N, K, the format's wanted shape and the norm; the two
+//     formats' rules are int8_decode_want / fp8_decode_want) and wo8_decode (checks, dispatch).
 #pragma once
+
+#include <type_traits>
 
 #include "tao_common.h"
 #include "tao_reduce.h"
@@ -79,6 +88,17 @@ static inline int check_decode_fuse(const char* what, int epilogue, int64_t N,
   fu->D = (int)head_dim;
   fu->T = (int)max_seq;
   return TAO_OK;
+}
+
+// The one switch over the epilogue: f is called with the epilogue as a compile-time constant,
+//   dispatch_epilogue(epilogue, [&](auto epi) { return launch<decltype(epi)::value>(...); });
+template <typename F>
+static inline int dispatch_epilogue(int epilogue, F&& f) {
+  switch (epilogue) {
+    case kEpiSwiGLU: return f(std::integral_constant<int, kEpiSwiGLU>{});
+    case kEpiRopeKV: return f(std::integral_constant<int, kEpiRopeKV>{});
+    default: return f(std::integral_constant<int, kEpiNone>{});
+  }
 }
 
 // ---- launch shape --------------------------------------------------------------------------------
@@ -241,6 +261,209 @@ static int wo8_gemv(const uint16_t* x, const void* w, const typename Kernel::sca
   if (M <= 2) return wo8_launch<Kernel, 2, 4>(x, w, scale, bias, y, M, N, K, stream);
   if (M <= 4) return wo8_launch<Kernel, 4, 2>(x, w, scale, bias, y, M, N, K, stream);
   return wo8_launch<Kernel, 8, 1>(x, w, scale, bias, y, M, N, K, stream);
+}
+
+// ---- byte-weight weight-only decode (M == 1 with the fusions): one kernel, one host path -------
+// The fusions above on a 1-B-per-weight stream, so an int8wo / float8wo Llama layer is 5 launches
+// per token, as with int4 weights, instead of 9. A format policy F brings
+//   scale_t                 the per-row scale's type;
+//   X, prep(a, b, cval)     one 16-k chunk of x (two 16-B pieces) as the arithmetic wants it;
+//   dot(x, wv)              sum_k x[k] * w[k] over the chunk;
+//   kSkipTail               a lane past the row's last chunk skips the math (true) or runs it on
+//                           an x that prep zeroed (false);
+//   out(total, scale)       the linear's bf16 output, as float;
+//   flag_bad_kv_pos()       flag_decode_error(kDecodeErrKvPos) on its file's error word;
+//   name, what              what check_launch records; the prefix of error messages.
+// Unlike the M > 1 GEMVs (above), the shared body costs nothing here: against the two kernels
+// written out, every int8 instantiation compiles to the same VGPRs, scratch and occupancy, and
+// the fp8 ones differ by a few VGPRs at unchanged occupancy (DESIGN.md §4.11 lists them).
+
+// Slice s of rows row0 .. row0 + RPW: lane's chunk s * 64 + lane, row and chunk clamped in bounds.
+template <int RPW>
+__device__ __forceinline__ void load_w_slice(uint4 (&wv)[RPW], const uint4* __restrict__ w,
+                                             int row0, int N, int nchunk, int s, int lane) {
+  const int c = s * 64 + lane;
+  const int cc = c < nchunk ? c : nchunk - 1;
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int n = row0 + r;
+    wv[r] = ld_nt_u4(w + (size_t)(n < N ? n : N - 1) * nchunk + cc);
+  }
+}
+
+// NPT > 0: the RMSNorm prologue, x normalised once per workgroup into LDS while the first weight
+// slice is in flight (NPT 16-B pieces of x and of the norm weight per thread: K <= 8 NPT threads).
+template <typename F, int RPW, int NPT, int EPI>
+__global__ __launch_bounds__(512) void wo8_decode_kernel(
+    const uint16_t* __restrict__ x, const uint4* __restrict__ w,
+    const typename F::scale_t* __restrict__ scale, uint16_t* __restrict__ y, int N, int K, int Wk,
+    int G, int S, DecodeFuse fu) {
+  constexpr bool PRO = NPT > 0;
+  constexpr int V = RPW;
+  // [G][Wk][V] partials | [16] wave sums of squares | (PRO) normalised x [K / 8] uint4
+  extern __shared__ float red[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wk = wave % Wk;
+  const int rg = wave / Wk;
+  const int row0 = (blockIdx.x * G + rg) * RPW;
+  const int nchunk = K >> 4;
+  const int nx = K >> 3;
+  float* ssr = red + G * Wk * V;
+  uint4* xs = reinterpret_cast<uint4*>(red + ((G * Wk * V + 16 + 3) & ~3));
+
+  uint4 xv[PRO ? NPT : 1], gv[PRO ? NPT : 1];
+  if constexpr (PRO) {  // x and the norm weight first: their vmcnt wait does not wait for W
+    const uint4* xr = reinterpret_cast<const uint4*>(x);
+    const uint4* gr = reinterpret_cast<const uint4*>(fu.norm_w);
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) {
+      const int i = threadIdx.x + u * (int)blockDim.x;
+      const int ic = i < nx ? i : nx - 1;
+      xv[u] = xr[ic];
+      gv[u] = gr[ic];
+    }
+  }
+  uint4 wv[RPW];
+  load_w_slice<RPW>(wv, w, row0, N, nchunk, wk, lane);  // Wk <= S: every wave owns a slice
+  if constexpr (PRO) {
+    float ss = 0.f;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u)
+      ss = sumsq_piece(xv[u], threadIdx.x + u * (int)blockDim.x < nx, ss);
+    ss = wave_sum(ss);
+    if (lane == 0) ssr[wave] = ss;
+    __syncthreads();
+    float t = 0.f;
+    for (int q = 0; q < G * Wk; ++q) t += ssr[q];
+    const float r = rsqrtf(t / (float)K + fu.eps);
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) {
+      const int i = threadIdx.x + u * (int)blockDim.x;
+      // piece i of 16-k chunk c = i >> 1 lands at 2 c + ((i + (c >> 3)) & 1): consecutive lanes
+      // read 32-B chunks, the rotation puts the two halves of a pass on distinct bank groups
+      if (i < nx) xs[(i & ~1) | ((i + (i >> 4)) & 1)] = rmsnorm_piece(xv[u], gv[u], r);
+    }
+    __syncthreads();
+  }
+
+  float acc[RPW];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) acc[r] = 0.f;
+  for (int s = wk; s < S; s += Wk) {
+    if (s != wk) load_w_slice<RPW>(wv, w, row0, N, nchunk, s, lane);
+    const int c = s * 64 + lane;
+    const bool cval = c < nchunk;
+    const int cc = cval ? c : nchunk - 1;
+    uint4 a, b;
+    if constexpr (PRO) {
+      const int rot = (cc >> 3) & 1;
+      a = xs[2 * cc + rot];
+      b = xs[2 * cc + (rot ^ 1)];
+    } else {
+      const uint4* xp = reinterpret_cast<const uint4*>(x + (size_t)cc * 16);
+      a = xp[0];
+      b = xp[1];
+    }
+    const typename F::X xc = F::prep(a, b, cval);
+    if (!F::kSkipTail || cval) {
+#pragma unroll
+      for (int r = 0; r < RPW; ++r) acc[r] += F::dot(xc, wv[r]);
+    }
+  }
+
+  float v[V];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) v[r] = acc[r];
+  wave_reduce_scatter<V>(v, lane);
+  const WgTotal<float> t = wg_combine<V>(v[0], red, lane, wk, rg, Wk);
+  // the linear's bf16 output of row t.widx
+  const int nrow = row0 + (t.widx < V ? t.widx : 0);
+  const float o = F::out(t.total, scale[nrow < N ? nrow : N - 1]);
+  if constexpr (EPI == kEpiNone) {
+    if (t.writer && row0 + t.widx < N) y[row0 + t.widx] = f32_to_bf16(o);
+  } else {
+    pair_epilogue<EPI, RPW>(o, lane, wk, Wk, row0, N, y, fu, [] { F::flag_bad_kv_pos(); });
+  }
+}
+
+// The launch shape a format wants: rows per wave (2, 4 or 8), waves along K, row groups, and
+// whether row groups are added for a long K without the norm too (with it they always are).
+struct Wo8Want {
+  int rpw, wk, g;
+  bool grow_plain;
+};
+// int8 (tao_tune_int8_gemv overrides each of the three): 4 rows per wave, Wk = min(S, 4), G = 2.
+static inline Wo8Want int8_decode_want(int trpw, int twk, int tg) {
+  return {trpw == 2 || trpw == 8 ? trpw : 4, twk > 0 ? twk : 4, tg > 0 ? tg : 2, true};
+}
+// fp8 (tao_tune_fp8_gemv overrides): without the norm, fp8wo_gemv_kernel's M == 1 shape: 4 rows
+// per wave, Wk = min(S, 8) waves along K, one row group. With it every workgroup re-normalises
+// the token, so fewer, larger workgroups pay: 8 rows per wave, 4 waves along K (fused, 4 x 8 x 1
+// vs 8 x 4 x 1, us: 6144 x 4096 7.9 vs 7.5, 28672 x 4096 25.3 vs 20.8, the 128256 x 4096 head
+// 93.2 vs 75.4, 10240 x 8192 20.2 vs 17.1, 57344 x 8192 93.2 vs 72.5;
+// profiles/fp8_decode_shape_ab.jsonl).
+static inline Wo8Want fp8_decode_want(int trpw, int twk, int tg, bool pro) {
+  const int rpw = trpw > 0 ? trpw : (pro ? 8 : 4);
+  return {rpw == 2 || rpw == 8 ? rpw : 4, twk > 0 ? twk : (pro ? 4 : 8), tg > 0 ? tg : 1, false};
+}
+
+// The prologue needs K <= 8 x NPT x threads, NPT <= 4, and has 16 slots for the waves' sums: row
+// groups are added while they fit 8 waves. npt: 0 without the norm, -1 where K is too long.
+struct Wo8DecodeLaunch {
+  int rpw, S, Wk, G, threads, npt, grid;
+  size_t lds;
+};
+static inline Wo8DecodeLaunch wo8_decode_shape(int N, int K, Wo8Want want, bool pro) {
+  GemvLaunchShape sh = gemv_launch_shape(K / 16, want.wk, want.g);
+  while ((pro || want.grow_plain) && sh.Wk * sh.G * 2 <= 8 && 64 * sh.Wk * sh.G * 8 * 4 < K)
+    sh.G *= 2;
+  Wo8DecodeLaunch L{want.rpw, sh.S, sh.Wk, sh.G, 64 * sh.Wk * sh.G, 0, 0, 0};
+  const int64_t t8 = (int64_t)L.threads * 8;
+  if (pro) L.npt = t8 >= K ? 1 : t8 * 2 >= K ? 2 : t8 * 4 >= K ? 4 : -1;
+  const int rows_per_wg = L.G * L.rpw;
+  L.grid = (int)(((int64_t)N + rows_per_wg - 1) / rows_per_wg);
+  L.lds = (((size_t)L.G * L.Wk * L.rpw + 16 + 3) & ~(size_t)3) * sizeof(float) +
+          (pro ? (size_t)K * 2 : 0);
+  return L;
+}
+
+template <typename F, int RPW, int NPT, int EPI>
+static int launch_wo8_decode(const uint16_t* x, const void* w, const typename F::scale_t* scale,
+                             uint16_t* y, int N, int K, const Wo8DecodeLaunch& L,
+                             hipStream_t stream, const DecodeFuse& fu) {
+  launch((wo8_decode_kernel<F, RPW, NPT, EPI>), dim3(L.grid), dim3(L.threads), L.lds, stream, x,
+         reinterpret_cast<const uint4*>(w), scale, y, N, K, L.Wk, L.G, L.S, fu);
+  return check_launch(F::name);
+}
+
+template <typename F, int EPI>
+static int wo8_decode(const uint16_t* x, const void* w, const typename F::scale_t* scale,
+                      uint16_t* y, int N, int K, Wo8Want want, hipStream_t stream,
+                      const DecodeFuse& fu) {
+  const Wo8DecodeLaunch L = wo8_decode_shape(N, K, want, fu.norm_w != nullptr);
+  if (L.threads > 512)
+    return set_error(TAO_ERR_INVALID_ARGUMENT, "%s: %d waves along K exceed 8", F::what, L.Wk);
+  if (L.npt < 0)
+    return set_error(TAO_ERR_INVALID_ARGUMENT,
+                     "%s: K (%d) too long for the RMSNorm prologue of %d threads", F::what, K,
+                     L.threads);
+#define TAO_WO8D(R, P) \
+  return launch_wo8_decode<F, R, P, EPI>(x, w, scale, y, N, K, L, stream, fu)
+#define TAO_WO8D_NPT(R)         \
+  switch (L.npt) {              \
+    case 0: TAO_WO8D(R, 0);     \
+    case 1: TAO_WO8D(R, 1);     \
+    case 2: TAO_WO8D(R, 2);     \
+    default: TAO_WO8D(R, 4);    \
+  }
+  switch (L.rpw) {
+    case 8: TAO_WO8D_NPT(8)
+    case 2: TAO_WO8D_NPT(2)
+    default: TAO_WO8D_NPT(4)
+  }
+#undef TAO_WO8D_NPT
+#undef TAO_WO8D
 }
 
 }  // namespace tao

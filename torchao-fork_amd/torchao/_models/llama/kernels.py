@@ -2,7 +2,7 @@
 include/torchao_mi355x.h). Outputs are allocated with torch (graph-capture safe: inside a
 capture they come from the graph's private pool); launches go on torch's current stream."""
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -394,6 +394,93 @@ def prologue_pays(N: int, K: int) -> bool:
     return K <= 4096 or N < 16384
 
 
+class DecodeFormat(NamedTuple):
+    """One weight format of the fused decode path: how model._fused_decode routes a linear of
+    that format and where its wrapper below runs the RMSNorm.
+
+    name: model._DECODE_PARTS[name] extracts the operands and <name>_decode here is the wrapper
+    (looked up per call, so that it can be patched); entry: the C entry; norm_max_k: the largest
+    K with the norm inside the kernel; max_k: the largest K at all (None: no limit), past it the
+    harness takes the unfused path; norm_inside: up to norm_max_k "always", or "pays" (where
+    prologue_pays says so); past_norm_max: a normed call past norm_max_k runs rmsnorm and then the
+    fused kernel without the norm ("own launch"), or the harness takes the unfused path
+    ("unfused"); bf16_x_only: the harness takes the unfused path for another x dtype (else the
+    wrapper raises)."""
+    name: str
+    entry: str
+    norm_max_k: int
+    max_k: Optional[int]
+    norm_inside: str
+    past_norm_max: str
+    bf16_x_only: bool = False
+
+    def norm_placement(self, N: int, K: int) -> Optional[str]:
+        """Where a normed one-token call of this format runs its RMSNorm: "inside" the GEMV,
+        "outside" in its own launch before it, or None where the call is not fused at all."""
+        if self.max_k is not None and K > self.max_k:
+            return None
+        if K > self.norm_max_k:
+            return "outside" if self.past_norm_max == "own launch" else None
+        return "inside" if self.norm_inside == "always" or prologue_pays(N, K) else "outside"
+
+
+# The RMSNorm prologues hold the token (and the norm weight) in registers: K <= 16384 = 512
+# threads x 4 pieces x 8 (tao_int4wo / int8wo / fp8wo / fp8dq _decode_bf16); the float8
+# dynamic-activation kernel holds the token there with or without the norm: K <= FP8DQ_MAX_K.
+FP8_NORM_MAX_K = 16384
+FP8DQ_MAX_K = 32768
+
+# Where the norm runs, measured (norm inside the GEMV vs RMSNorm launch + GEMV, us):
+#   int4     prologue_pays (its docstring).
+#   int8wo   inside at every shape the harness has.
+#   int8dq   inside whenever the call is fused; a normed linear past K = 8192 takes the unfused
+#            path (the token is quantised from registers: tao_int8dq_decode_bf16).
+#   fp8wo    (experiments/bench_decode_fp8.py, profiles/fp8_decode_bench.jsonl) inside at every
+#            shape: wqkv 6144x4096 7.5 vs 9.1, w1||w3 28672x4096 20.4 vs 21.4, the 128256x4096
+#            head 79.0 vs 79.3, 70B wqkv 10240x8192 17.7 vs 19.1, 70B w1||w3 57344x8192 74.3 vs
+#            76.4.
+#   fp8dq    follows prologue_pays row for row: 10.5 vs 12.2, 25.4 vs 26.0 and 19.6 vs 21.2
+#            (inside); the head 93.7 vs 86.0 and 70B w1||w3 80.2 vs 77.5 (own launch: every
+#            workgroup also re-quantises the token).
+# The order is the order model._fused_decode tries the formats in.
+DECODE_FORMATS = {f.name: f for f in (
+    DecodeFormat("int4", "tao_int4wo_decode_bf16", 16384, None, "pays", "own launch"),
+    DecodeFormat("int8wo", "tao_int8wo_decode_bf16", 16384, None, "always", "own launch"),
+    DecodeFormat("int8dq", "tao_int8dq_decode_bf16", 8192, 32768, "always", "unfused"),
+    DecodeFormat("fp8wo", "tao_fp8wo_decode_bf16", FP8_NORM_MAX_K, None, "always", "own launch",
+                 bf16_x_only=True),
+    DecodeFormat("fp8dq", "tao_fp8dq_decode_bf16", FP8_NORM_MAX_K, FP8DQ_MAX_K, "pays",
+                 "own launch", bf16_x_only=True),
+)}
+
+
+def _decode_call(fmt: str, x: torch.Tensor, weight_args: tuple, N: int, K: int, norm_weight,
+                 eps: float, epilogue: str, rope) -> torch.Tensor:
+    """The call behind the <fmt>_decode wrappers, after their dtype and shape checks: places the
+    norm (DecodeFormat.norm_placement; a call the table does not fuse keeps its norm and is the C
+    entry's to refuse), allocates the epilogue's output and calls the format's entry with
+    ``weight_args`` (tensors, and int4's group size) between x and N."""
+    f = DECODE_FORMATS[fmt]
+    if norm_weight is not None and f.norm_placement(N, K) == "outside":
+        x, norm_weight = rmsnorm(x, norm_weight, eps), None
+    epi = _EPILOGUES[epilogue]
+    freqs = pos = kc = vc = None
+    H = Hkv = D = T = 0
+    if epi == 2:
+        freqs, pos, kc, vc, H = rope
+        _, Hkv, T, D = kc.shape
+        y = torch.empty(1, H, 1, D, dtype=x.dtype, device=x.device)
+    elif epi == 1:
+        y = torch.empty(*x.shape[:-1], N // 2, dtype=x.dtype, device=x.device)
+    else:
+        y = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    wargs = [a.data_ptr() if isinstance(a, torch.Tensor) else int(a) for a in weight_args]
+    _lib.call(f.entry, x.data_ptr(), *wargs[:2], N, K, *wargs[2:], ptr(norm_weight), float(eps),
+              epi, y.data_ptr(), ptr(freqs), ptr(pos), ptr(kc), ptr(vc), H, Hkv, D, T, _stream(x))
+    return y
+
+
 # Decode feed-forward (RMSNorm -> w1||w3 -> SwiGLU -> w2 -> + residual) in ONE persistent launch
 # on the LDS-DMA engine (tao_int4wo_ffn_engine_bf16, csrc/decode_engine.hip) instead of the two
 # fused GEMV launches, for int4 g32 at the shapes the engine serves (Llama-3-8B).
@@ -457,32 +544,11 @@ def int4_decode(x: torch.Tensor, packed: torch.Tensor, scale_and_zero: torch.Ten
         raise RuntimeError(f"int4_decode takes one token, got x of shape {tuple(x.shape)}")
     if norm_weight is not None:
         _check(norm_weight, torch.bfloat16, "int4_decode norm_weight")
-        if not prologue_pays(N, K):  # normalise once in its own launch instead
-            x, norm_weight = rmsnorm(x, norm_weight, eps), None
-    epi = _EPILOGUES[epilogue]
-    freqs = pos = kc = vc = None
-    H = Hkv = D = T = 0
-    if epi == 2:
-        freqs, pos, kc, vc, H = rope
-        _, Hkv, T, D = kc.shape
-        y = torch.empty(1, H, 1, D, dtype=x.dtype, device=x.device)
-    elif epi == 1:
-        y = torch.empty(*x.shape[:-1], N // 2, dtype=x.dtype, device=x.device)
-    else:
-        y = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.call("tao_int4wo_decode_bf16", x.data_ptr(), packed.data_ptr(), scale_and_zero.data_ptr(),
-              N, K, int(group_size), ptr(norm_weight), float(eps), epi, y.data_ptr(), ptr(freqs),
-              ptr(pos), ptr(kc), ptr(vc), H, Hkv, D, T, _stream(x))
-    return y
+    return _decode_call("int4", x, (packed, scale_and_zero, group_size), N, K, norm_weight, eps,
+                        epilogue, rope)
 
 
-def int8wo_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
-                  eps: float = 0.0, epilogue: str = "none", rope=None,
-                  _entry: str = "tao_int8wo_decode_bf16") -> torch.Tensor:
-    """One token through an int8 weight-only linear (w [N, K] int8, scale [N] bf16) with the
-    int4_decode fusions (tao_int8wo_decode_bf16): optional RMSNorm of x; epilogue "none",
-    "swiglu" or "rope_kv" as in int4_decode."""
+def _int8_decode(fmt: str, x, w, scale, norm_weight, eps, epilogue, rope) -> torch.Tensor:
     _check(x, torch.bfloat16, "int8wo_decode x")
     _check(w, torch.int8, "int8wo_decode w")
     N, K = w.shape
@@ -494,54 +560,26 @@ def int8wo_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_we
         raise RuntimeError(f"int8 decode: {scale.numel()} scales for {N} rows")
     if norm_weight is not None:
         _check(norm_weight, torch.bfloat16, "int8wo_decode norm_weight")
-    epi = _EPILOGUES[epilogue]
-    freqs = pos = kc = vc = None
-    H = Hkv = D = T = 0
-    if epi == 2:
-        freqs, pos, kc, vc, H = rope
-        _, Hkv, T, D = kc.shape
-        y = torch.empty(1, H, 1, D, dtype=x.dtype, device=x.device)
-    elif epi == 1:
-        y = torch.empty(*x.shape[:-1], N // 2, dtype=x.dtype, device=x.device)
-    else:
-        y = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.call(_entry, x.data_ptr(), w.data_ptr(), scale.data_ptr(), N, K,
-              ptr(norm_weight), float(eps), epi, y.data_ptr(), ptr(freqs), ptr(pos), ptr(kc),
-              ptr(vc), H, Hkv, D, T, _stream(x))
-    return y
+    return _decode_call(fmt, x, (w, scale), N, K, norm_weight, eps, epilogue, rope)
+
+
+def int8wo_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
+                  eps: float = 0.0, epilogue: str = "none", rope=None) -> torch.Tensor:
+    """One token through an int8 weight-only linear (w [N, K] int8, scale [N] bf16) with the
+    int4_decode fusions (tao_int8wo_decode_bf16): optional RMSNorm of x; epilogue "none",
+    "swiglu" or "rope_kv" as in int4_decode."""
+    return _int8_decode("int8wo", x, w, scale, norm_weight, eps, epilogue, rope)
 
 
 def int8dq_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
                   eps: float = 0.0, epilogue: str = "none", rope=None) -> torch.Tensor:
     """int8wo_decode for the int8 dynamic-activation linear (Int8DynamicActivationInt8Weight):
     the (normalised) token is quantised per token inside the kernel (tao_int8dq_decode_bf16)."""
-    return int8wo_decode(x, w, scale, norm_weight, eps, epilogue, rope,
-                         _entry="tao_int8dq_decode_bf16")
+    return _int8_decode("int8dq", x, w, scale, norm_weight, eps, epilogue, rope)
 
 
-# The RMSNorm prologue of the float8 decode kernels holds the token and the norm weight in
-# registers: K <= FP8_NORM_MAX_K (tao_fp8wo_decode_bf16, tao_fp8dq_decode_bf16); the
-# dynamic-activation kernel holds the token there with or without the norm: K <= FP8DQ_MAX_K.
-FP8_NORM_MAX_K = 16384
-FP8DQ_MAX_K = 32768
-
-
-def fp8wo_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
-                 eps: float = 0.0, epilogue: str = "none", rope=None,
-                 _entry: str = "tao_fp8wo_decode_bf16") -> torch.Tensor:
-    """One token through a float8 weight-only linear (w [N, K] float8_e4m3fn, scale [N] fp32)
-    with the int4_decode fusions (tao_fp8wo_decode_bf16): optional RMSNorm of x; epilogue "none",
-    "swiglu" or "rope_kv" as in int4_decode.
-
-    Where the norm runs (experiments/bench_decode_fp8.py, profiles/fp8_decode_bench.jsonl; norm
-    inside the GEMV vs RMSNorm launch + GEMV, us): the weight-only kernel takes it inside at every
-    shape: wqkv 6144x4096 7.5 vs 9.1, w1||w3 28672x4096 20.4 vs 21.4, the 128256x4096 head 79.0 vs
-    79.3, 70B wqkv 10240x8192 17.7 vs 19.1, 70B w1||w3 57344x8192 74.3 vs 76.4. The
-    dynamic-activation kernel follows prologue_pays row for row: 10.5 vs 12.2, 25.4 vs 26.0 and
-    19.6 vs 21.2 (inside); the head 93.7 vs 86.0 and 70B w1||w3 80.2 vs 77.5 (own launch: every
-    workgroup also re-quantises the token). Past FP8_NORM_MAX_K the RMSNorm is its own launch."""
-    what = "fp8wo_decode" if _entry == "tao_fp8wo_decode_bf16" else "fp8dq_decode"
+def _fp8_decode(fmt: str, x, w, scale, norm_weight, eps, epilogue, rope) -> torch.Tensor:
+    what = f"{fmt}_decode"
     _check(x, torch.bfloat16, f"{what} x")
     _check(w, torch.float8_e4m3fn, f"{what} w")
     if w.dim() != 2:
@@ -554,25 +592,16 @@ def fp8wo_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_wei
         raise RuntimeError(f"{what}: {scale.numel()} scales for {N} rows")
     if norm_weight is not None:
         _check(norm_weight, torch.bfloat16, f"{what} norm_weight")
-        pays = _entry == "tao_fp8wo_decode_bf16" or prologue_pays(N, K)
-        if K > FP8_NORM_MAX_K or not pays:  # normalise in its own launch instead
-            x, norm_weight = rmsnorm(x, norm_weight, eps), None
-    epi = _EPILOGUES[epilogue]
-    freqs = pos = kc = vc = None
-    H = Hkv = D = T = 0
-    if epi == 2:
-        freqs, pos, kc, vc, H = rope
-        _, Hkv, T, D = kc.shape
-        y = torch.empty(1, H, 1, D, dtype=x.dtype, device=x.device)
-    elif epi == 1:
-        y = torch.empty(*x.shape[:-1], N // 2, dtype=x.dtype, device=x.device)
-    else:
-        y = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.call(_entry, x.data_ptr(), w.data_ptr(), scale.data_ptr(), N, K,
-              ptr(norm_weight), float(eps), epi, y.data_ptr(), ptr(freqs), ptr(pos), ptr(kc),
-              ptr(vc), H, Hkv, D, T, _stream(x))
-    return y
+    return _decode_call(fmt, x, (w, scale), N, K, norm_weight, eps, epilogue, rope)
+
+
+def fp8wo_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
+                 eps: float = 0.0, epilogue: str = "none", rope=None) -> torch.Tensor:
+    """One token through a float8 weight-only linear (w [N, K] float8_e4m3fn, scale [N] fp32)
+    with the int4_decode fusions (tao_fp8wo_decode_bf16): optional RMSNorm of x; epilogue "none",
+    "swiglu" or "rope_kv" as in int4_decode. Where the norm runs: DECODE_FORMATS; past
+    FP8_NORM_MAX_K the RMSNorm is its own launch."""
+    return _fp8_decode("fp8wo", x, w, scale, norm_weight, eps, epilogue, rope)
 
 
 def fp8dq_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_weight=None,
@@ -580,8 +609,7 @@ def fp8dq_decode(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_wei
     """fp8wo_decode for the float8 dynamic-activation linear
     (Float8DynamicActivationFloat8WeightConfig, PerRow): the (normalised) token is quantised per
     row to e4m3fn inside the kernel (tao_fp8dq_decode_bf16)."""
-    return fp8wo_decode(x, w, scale, norm_weight, eps, epilogue, rope,
-                        _entry="tao_fp8dq_decode_bf16")
+    return _fp8_decode("fp8dq", x, w, scale, norm_weight, eps, epilogue, rope)
 
 
 def argmax(logits: torch.Tensor) -> torch.Tensor:

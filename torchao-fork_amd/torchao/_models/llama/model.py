@@ -211,11 +211,18 @@ def _int4_parts(lin: Optional[nn.Linear]):
     return packed, impl.scale_and_zero, w.block_size[-1]
 
 
+def _gpu_weight(lin: Optional[nn.Linear]):
+    """The weight of a bias-free linear on the GPU, else None: what every fused decode kernel
+    past int4 asks first."""
+    w = getattr(lin, "weight", None)
+    return None if w is None or lin.bias is not None or not w.is_cuda else w
+
+
 def _int8wo_parts(lin: Optional[nn.Linear]):
     """(int_data [N, K] int8, scale [N]) of an int8 weight-only linear (Int8WeightOnlyConfig,
     PlainLayout) on the GPU, else None: the fused int8 decode kernels read those operands."""
-    w = getattr(lin, "weight", None)
-    if w is None or lin.bias is not None or not w.is_cuda:
+    w = _gpu_weight(lin)
+    if w is None:
         return None
     from torchao.dtypes.uintx.plain_layout import _linear_fp_act_int8_weight_check
 
@@ -232,8 +239,8 @@ def _int8wo_parts(lin: Optional[nn.Linear]):
 def _int8dq_parts(lin: Optional[nn.Linear]):
     """(int_data [N, K] int8, scale [N]) of an Int8DynamicActivationInt8WeightConfig linear with
     the default per-token activation recipe on the GPU, else None."""
-    w = getattr(lin, "weight", None)
-    if w is None or lin.bias is not None or not w.is_cuda:
+    w = _gpu_weight(lin)
+    if w is None:
         return None
     from torchao.quantization.linear_activation_quantized_tensor import (
         LinearActivationQuantizedTensor,
@@ -274,8 +281,8 @@ def _fp8wo_parts(lin: Optional[nn.Linear]):
     """(float8_data [N, K] e4m3fn, scale [N] fp32) of a float8 weight-only linear
     (Float8WeightOnlyConfig) on the GPU, else None: the weight criteria of the F.linear dispatch
     (_linear_fp_act_fp8_weight_check)."""
-    w = getattr(lin, "weight", None)
-    if w is None or lin.bias is not None or not w.is_cuda:
+    w = _gpu_weight(lin)
+    if w is None:
         return None
     from torchao.dtypes.floatx.float8_layout import _linear_fp_act_fp8_weight_check
 
@@ -288,8 +295,8 @@ def _fp8dq_parts(lin: Optional[nn.Linear]):
     """(float8_data [N, K] e4m3fn, scale [N] fp32) of a
     Float8DynamicActivationFloat8WeightConfig(granularity=PerRow()) linear on the GPU, else None:
     the recipe and weight criteria of the one-token dispatch (_fused_fp8_dyn_decode)."""
-    w = getattr(lin, "weight", None)
-    if w is None or lin.bias is not None or not w.is_cuda:
+    w = _gpu_weight(lin)
+    if w is None:
         return None
     from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
     from torchao.dtypes.floatx.float8_layout import Float8Layout, _is_rowwise_scaled
@@ -316,6 +323,12 @@ def _fp8dq_parts(lin: Optional[nn.Linear]):
     return _fp8_operands(inner, 16)
 
 
+# The operand extractor of each row of kernels.DECODE_FORMATS (they live here, with the tensor
+# subclasses they take apart).
+_DECODE_PARTS = {"int4": _int4_parts, "int8wo": _int8wo_parts, "int8dq": _int8dq_parts,
+                 "fp8wo": _fp8wo_parts, "fp8dq": _fp8dq_parts}
+
+
 def _fused_decode(x, lin, norm=None, epilogue="none", rope=None):
     """One token through ``lin`` with the decode fusions, on whichever fused kernel its weight
     format has (int4 / int8 / float8 weight-only, int8 / float8 dynamic activation); None if
@@ -326,24 +339,18 @@ def _fused_decode(x, lin, norm=None, epilogue="none", rope=None):
         return None
     nw = None if norm is None else norm.weight
     eps = 0.0 if norm is None else norm.eps
-    p4 = _int4_parts(lin)
-    if p4 is not None:
-        return kernels.int4_decode(x, *p4, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
-    p8 = _int8wo_parts(lin)
-    if p8 is not None:
-        return kernels.int8wo_decode(x, *p8, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
-    pq = _int8dq_parts(lin)
-    if pq is not None and (nw is None or x.shape[-1] <= 8192):
-        return kernels.int8dq_decode(x, *pq, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
-    # float8: a normed linear past the prologue's K limit, or a dynamic-activation one past the
-    # kernel's own, takes the unfused path (as the int8dq branch above)
-    f8 = x.dtype == torch.bfloat16 and (nw is None or x.shape[-1] <= kernels.FP8_NORM_MAX_K)
-    pf = _fp8wo_parts(lin) if f8 else None
-    if pf is not None:
-        return kernels.fp8wo_decode(x, *pf, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
-    pf = _fp8dq_parts(lin) if f8 else None
-    if pf is not None and x.shape[-1] <= kernels.FP8DQ_MAX_K:
-        return kernels.fp8dq_decode(x, *pf, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
+    K = x.shape[-1]
+    for fmt in kernels.DECODE_FORMATS.values():
+        parts = _DECODE_PARTS[fmt.name](lin)
+        if parts is None:
+            continue
+        # (N only matters to a normed call: the weight tensor's rows, packed or not)
+        if (fmt.bf16_x_only and x.dtype != torch.bfloat16
+                or fmt.max_k is not None and K > fmt.max_k
+                or nw is not None and fmt.norm_placement(parts[0].shape[0], K) is None):
+            return None
+        wrapper = getattr(kernels, f"{fmt.name}_decode")
+        return wrapper(x, *parts, norm_weight=nw, eps=eps, epilogue=epilogue, rope=rope)
     return None
 
 
