@@ -188,6 +188,38 @@ int tao_fp8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const float* w
                             const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                             void* stream);
 
+/* ---- MXFP8: e4m3fn codes with one E8M0 scale byte per 32-element block (csrc/mx_fp8.hip) ------ */
+
+/* Block quantizer of x [M][K] bf16, FLOOR mode: per block of 32 consecutive k,
+ *   byte = clamp((biased fp32 exponent field of amax|x|) - 8, 0, ..), 255 if the amax is NaN,
+ *   q    = e4m3fn_rne(clamp(float(x) / d, -448, 448)), d the fp32 number with `byte` as exponent
+ *          field, at least 2^-126 (an all-zero block: byte 0, codes 0).
+ * q uint8 [M][K] codes, scale uint8 [M][K/32] E8M0 bytes. Replaces to_mx
+ * (torchao/prototype/mx_formats/mx_tensor.py:133-326, elem_dtype float8_e4m3fn, block_size 32,
+ * ScaleCalculationMode.FLOOR), byte for byte. K % 32 == 0; M == 0 is a no-op; x, q 16-B aligned,
+ * M * K below 4 Gi. */
+int tao_mx_quantize_rows_bf16(const uint16_t* x, uint8_t* q, uint8_t* scale, int64_t M, int64_t K,
+                              void* stream);
+
+/* y[m][n] = bf16( acc[m][n] + fp32(bias[n]) ),
+ * acc[m][n] = sum_b 2^(xs[m][b]-127) 2^(ws[n][b]-127) sum_{k in block b} f(xq[m][k]) f(wq[n][k])
+ * in fp32: one rounding to bf16. xq uint8 [M][K], wq uint8 [N][K] e4m3fn codes; xs uint8 [M][K/32],
+ * ws uint8 [N][K/32] E8M0 bytes (255 is NaN); bias bf16 [N] or NULL. Replaces the block-scaled
+ * torch._scaled_mm call of _addmm_mx_dispatch (torchao/prototype/mx_formats/mx_ops.py), which the
+ * reference has for sm100 only. K % 32 == 0, any N, M >= 0 (M == 0 is a no-op); xq, wq: 16-B
+ * aligned, and xs, ws 8-B aligned where K % 256 == 0; each operand below 4 GiB. */
+int tao_mx_scaled_mm_bf16(const uint8_t* xq, const uint8_t* xs, const uint8_t* wq,
+                          const uint8_t* ws, const uint16_t* bias, uint16_t* y, int64_t M,
+                          int64_t N, int64_t K, void* stream);
+
+/* One token (M <= 1): tao_mx_quantize_rows_bf16 of the bf16 token x [K] and the product above in
+ * one launch, bit-identical to the two calls. Replaces MXTensor.to_mx on the activation followed by
+ * _addmm_mx_dispatch (torchao/prototype/mx_formats/mx_ops.py). More tokens are the two calls, the
+ * caller owning the code and scale buffers between them. K % 32 == 0, K <= 65536. */
+int tao_mx_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const uint8_t* ws,
+                           const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                           void* stream);
+
 /* ---- int8 dynamic activation x int8 weight -------------------------------------------------- */
 
 /* Per-token symmetric reduced-range int8 quantization of x [M][K] bf16:

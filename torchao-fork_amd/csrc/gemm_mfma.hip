@@ -1,15 +1,17 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// five weight/activation formats share one kernel template:
+// six weight/activation formats share one kernel template:
 //   Int4WO  : bf16 x, int4 group-quant W (gfx950 row-stream layout), v_mfma_f32_16x16x32_bf16
 //   Int8WO  : bf16 x, int8 per-channel W,                            v_mfma_f32_16x16x32_bf16
 //   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
 //   Int8Dyn : int8 x (per-token scale), int8 W (per-channel scale),   v_mfma_i32_16x16x64_i8
 //   Fp8Dyn  : e4m3fn x (per-token scale), e4m3fn W (per-row scale),   v_mfma_scale_f32_16x16x128_f8f6f4
+//   MxFp8   : e4m3fn x and W, one E8M0 scale byte per 32-k block,    v_mfma_scale_f32_16x16x128_f8f6f4
 // Replaces aten._weight_int4pack_mm (tensor_core_tiled_layout.py:104), mm(x, w.to(bf16)) * s
 // (plain_layout.py:256-266), int_scaled_matmul + scales (plain_layout.py:294-315,
 // kernel/intmm.py:108-143), F.linear(x, w.dequantize()) (floatx/float8_layout.py:391-396) and the
-// row-wise torch._scaled_mm of the float8 dynamic path (floatx/float8_layout.py:329-367).
+// row-wise torch._scaled_mm of the float8 dynamic path (floatx/float8_layout.py:329-367) and the
+// block-scaled torch._scaled_mm of the MX path (prototype/mx_formats/mx_ops.py _addmm_mx_dispatch).
 //
 // Tile: 4 waves x 16 output columns (BN = 64) x BM rows per k-group; each wave owns 16 columns
 // and all BM rows. K advances in macro-steps (256 bf16 k for int4, 128 bf16 k for int8-WO,
@@ -533,6 +535,133 @@ struct Fp8Dyn {
   }
 };
 
+// MxFp8: e4m3fn x and W with one E8M0 scale byte per 32-k block on both operands (MXFP8,
+// mx_fp8.hip), the scales applied inside v_mfma_scale_f32_16x16x128_f8f6f4. Fp8Dyn's tile
+// structure unchanged (1-byte x image, 256-k steps, full-line weight loads through the per-wave
+// stage, the same k order, weights past a K tail zeroed) plus the scales.
+// Layout of the instruction, as the exact-input test (tests/test_gpu_mx.py,
+// test_scale_mapping_exact) establishes it:
+//  * data: lane l = (i = l & 15, g = l >> 4) holds, in its first four operand VGPRs, k
+//    16 g .. + 16 of the MFMA's 128 and, in its last four, k 64 + 16 g .. + 16: Fp8Dyn's order
+//    (slots 2 u and 2 u + 1 of Int8Dyn::slot). A lane does NOT hold one whole 32-k block: its two
+//    halves lie in blocks g >> 1 and 2 + (g >> 1).
+//  * scales: the 32-k block j (k 32 j .. + 32) of row i (A: output row, B: output column) is
+//    scaled by the byte that lane i + 16 j supplies, in the byte of its scale VGPR that opsel
+//    names. (Giving lane group g the contiguous k 32 g .. + 32 instead scaled half of blocks 0
+//    and 3 and nothing of blocks 1 and 2.)
+// So lane (i, kq) supplies the scale of block 4 u + kq of the step for MFMA u, whatever k it
+// holds itself. It packs the bytes of its two MFMAs of a step into one VGPR (byte u) and MFMA u
+// selects byte u by opsel. W: two byte loads per lane and step, riding in the weight ring. x: the
+// step's BM x 8 bytes are loaded by the k-group's threads (thread t: row t >> 3 (+ 32 i), block
+// t & 7), ride in the x ring and are stored beside the x image, double-buffered like it, as
+// [row][kq][u]; an A fragment read takes its two bytes with one ds_read_u16. A block at or past
+// K / 32 is never read (the index is clamped) and its byte is replaced by 127 (2^0) against the
+// zeroed codes: a stray 0xFF would make 0 * w NaN.
+// AL (K % 256 == 0; tao_mx_scaled_mm_bf16 then wants both scale arrays 8-B aligned, so every
+// step's 8 bytes of a row are one aligned 8-B word, and there is no K tail): one 8-B load per lane
+// replaces the two byte loads of W, and thread t < BM loads the 8 bytes of x row t, permutes them
+// to [kq][u] with two v_perm_b32 and stores them with one ds_write_b64.
+// No row or column factor: the epilogue is the bias add and the one rounding.
+template <bool AL>
+struct MxFp8 {
+  static constexpr int kPathId = 5;  // no measured table entries: the heuristic shapes
+  static constexpr bool kMaskTail = !AL;
+  static constexpr bool kBlockScaled = true;
+  static constexpr bool kScaleAligned = AL;
+  static constexpr int kABytes = 1;  // e4m3fn x
+  static constexpr int kKStep = 256;
+  static constexpr int kMfma = 2;
+  static constexpr int kASlots = 2;  // 16-B x slots per MFMA
+  static constexpr int kMaxBM = 128;
+  static constexpr int kPrefKG = 1;
+  static constexpr int kMaxKG = 2;
+  static constexpr int kMinSlice = 4;
+  typedef f32x4_t Acc;
+  const uint4* w;          // [N][K/16] e4m3fn codes
+  const uint8_t* wscale;   // [N][K/32] E8M0 bytes
+  const uint8_t* xscale;   // [M][K/32] E8M0 bytes
+  static constexpr int kStage = Int8Dyn::kStage;
+  struct Lane {
+    Int8Dyn::Lane c;
+    const uint8_t* s;  // the lane's row of scale bytes
+    int nblk, kq;
+  };
+  struct Chunk {
+    Int8Dyn::Chunk c;
+    // scale bytes of blocks kq and 4 + kq of the step (clamped to the row); AL: the step's 8
+    // bytes of the row, blocks 0-3 and 4-7
+    uint32_t s0, s1;
+  };
+  struct Prep {
+    uint4 v[4];   // v[s]: bytes 64 s + 16 kq .. + 16 of row n
+    uint32_t sc;  // byte u: the scale of block 4 u + kq (s0 | s1 << 8; mask_tail: tails -> 127)
+  };
+  static __device__ __forceinline__ int slot(int s, int kq) { return Int8Dyn::slot(s, kq); }
+  static __device__ __forceinline__ int xswz(int row) { return row & 15; }
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    Lane L;
+    L.c = Int8Dyn{w, nullptr, nullptr}.setup(bn, lane, N, K);
+    L.nblk = K >> 5;
+    L.kq = lane >> 4;
+    L.s = wscale + (size_t)(bn < N ? bn : N - 1) * L.nblk;
+    return L;
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    Chunk ch;
+    ch.c = Int8Dyn{w, nullptr, nullptr}.load(L.c, st);
+    if constexpr (AL) {
+      const uint2 v = *reinterpret_cast<const uint2*>(L.s + st * 8);
+      ch.s0 = v.x;
+      ch.s1 = v.y;
+    } else {
+      const int b0 = st * 8 + L.kq, b1 = b0 + 4;
+      ch.s0 = L.s[b0 < L.nblk ? b0 : L.nblk - 1];
+      ch.s1 = L.s[b1 < L.nblk ? b1 : L.nblk - 1];
+    }
+    return ch;
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    const Int8Dyn::Prep q = Int8Dyn{w, nullptr, nullptr}.prep(ch.c, stage, lane);
+    Prep p;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) p.v[s] = q.v[s];
+    if constexpr (AL) {
+      const int sh = 8 * (lane >> 4);
+      p.sc = ((ch.s0 >> sh) & 0xFFu) | (((ch.s1 >> sh) & 0xFFu) << 8);
+    } else {
+      p.sc = ch.s0 | (ch.s1 << 8);
+    }
+    return p;
+  }
+  // the codes as Fp8Dyn masks them (16-B pieces); the scale bytes of blocks 4 u + kq past K / 32
+  static __device__ __forceinline__ void mask_tail(Prep& p, int st, int kq, int K) {
+    const int k0 = st * kKStep + 16 * kq;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const uint32_t k = k0 + 64 * s < K ? ~0u : 0u;
+      p.v[s] = make_uint4(p.v[s].x & k, p.v[s].y & k, p.v[s].z & k, p.v[s].w & k);
+    }
+    const int b0 = st * kKStep + 32 * kq;
+    p.sc = (b0 < K ? p.sc & 0xFFu : 127u) | (b0 + 128 < K ? p.sc & 0xFF00u : 127u << 8);
+  }
+  __device__ __forceinline__ i32x8_t frag(const Prep& p, int u) const {
+    return u == 0 ? Fp8Dyn::pair(p.v[0], p.v[1]) : Fp8Dyn::pair(p.v[2], p.v[3]);
+  }
+  // cbsz 0 / blgp 0: both operands e4m3; MFMA u takes byte u of both scale VGPRs
+  static __device__ __forceinline__ Acc mfma2s(const uint4& a0, const uint4& a1, const i32x8_t& b,
+                                               Acc c, int u, uint32_t asc, uint32_t bsc) {
+    const i32x8_t a = Fp8Dyn::pair(a0, a1);
+    return u == 0 ? __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, (int)asc, 0,
+                                                                      (int)bsc)
+                  : __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 1, (int)asc, 1,
+                                                                      (int)bsc);
+  }
+  static constexpr bool kRowF = false, kColF = false;
+  __device__ __forceinline__ const uint16_t* row_factor() const { return nullptr; }
+  __device__ __forceinline__ const uint16_t* col_factor() const { return nullptr; }
+  __device__ __forceinline__ float epi(float acc, float, float) const { return acc; }
+};
+
 // 16-B x slots one MFMA of the policy reads per lane (1 unless the policy says otherwise)
 template <class P, class = void>
 struct ASlots {
@@ -552,6 +681,26 @@ struct MaxKG {
 template <class P>
 struct MaxKG<P, std::void_t<decltype(P::kMaxKG)>> {
   static constexpr int value = P::kMaxKG;
+};
+
+// whether the policy's MFMAs take per-block scale bytes (MxFp8)
+template <class P, class = void>
+struct BlockScaled {
+  static constexpr bool value = false;
+};
+template <class P>
+struct BlockScaled<P, std::void_t<decltype(P::kBlockScaled)>> {
+  static constexpr bool value = P::kBlockScaled;
+};
+
+// ... and whether every step's 8 scale bytes of a row are one aligned 8-B word (MxFp8<true>)
+template <class P, class = void>
+struct ScaleAligned {
+  static constexpr bool value = false;
+};
+template <class P>
+struct ScaleAligned<P, std::void_t<decltype(P::kScaleAligned)>> {
+  static constexpr bool value = P::kScaleAligned;
 };
 
 // LDS image of one x tile: [BM rows][16 slots of 16 B], slot XOR-swizzled with row & 15 so the
@@ -624,8 +773,13 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
   constexpr int NA = MT * NW;                   // accumulator tiles per wave
   static_assert((KG - 1) * 4 * NA * 64 <= KG * 2 * TILE, "k-group reduction must fit in LDS");
   // one LDS array (a second __shared__ object can de-pipeline the loop, cdna guide §5 item 4a):
-  // [KG][2][x tile] then the per-wave weight stages (NW per wave)
-  __shared__ uint4 lds[KG * 2 * TILE + KG * 4 * NW * P::kStage + (P::kStage == 0)];
+  // [KG][2][x tile] then the per-wave weight stages (NW per wave), then (block-scaled policies)
+  // [KG][2][BM rows][8 scale bytes] of the x tiles
+  constexpr bool kBS = BlockScaled<P>::value;
+  constexpr bool kBSA = ScaleAligned<P>::value;  // whole 8-B words of scale bytes per row and step
+  constexpr int XSL = kBSA ? 2 : kBS ? (BM + 31) / 32 : 1;  // x scale registers per thread per step
+  constexpr int XSC = kBS ? BM / 2 : 0;          // uint4 per tile of x scale bytes
+  __shared__ uint4 lds[KG * 2 * TILE + KG * 4 * NW * P::kStage + (P::kStage == 0) + KG * 2 * XSC];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -668,6 +822,22 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
     xlds[i] = x_slot<SLOTS, P>(row0 + RPP * i, xslot);
   }
   const bool ragged = (row_bytes % XSB) != 0;
+  // block-scaled: this thread's x scale bytes, block ktid & 7 of rows (ktid >> 3) + 32 i
+  const int nblk = K >> 5;
+  const int xsblk = ktid & 7;
+  const uint8_t* xsrow[XSL];
+  uint8_t* xscl = reinterpret_cast<uint8_t*>(lds + KG * 2 * TILE + KG * 4 * NW * P::kStage +
+                                             (P::kStage == 0) + kg * 2 * XSC);
+  if constexpr (kBSA) {  // thread t: the step's 8 bytes of row t (t >= BM: row BM - 1, not stored)
+    const int gm = m_blk + (ktid < BM ? ktid : BM - 1);
+    xsrow[0] = pol.xscale + (size_t)(gm < M ? gm : M - 1) * nblk;
+  } else if constexpr (kBS) {
+#pragma unroll
+    for (int i = 0; i < XSL; ++i) {
+      const int gm = m_blk + (ktid >> 3) + 32 * i;
+      xsrow[i] = pol.xscale + (size_t)(gm < M ? gm : M - 1) * nblk;
+    }
+  }
 
   Acc acc[NA];  // [t][c]
 #pragma unroll
@@ -675,15 +845,26 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
 
   uint4 xr[D][XLOADS];
   typename P::Chunk wr[D][NW];
+  uint32_t xsr[D][XSL];
 
   // local step j of this k-group -> absolute step (may be >= s1: then inactive)
   auto abs_step = [&](int j) __attribute__((always_inline)) { return s0 + kg + j * KG; };
-  auto load_step = [&](int j, uint4 (&xdst)[XLOADS], typename P::Chunk (&wdst)[NW])
-      __attribute__((always_inline)) {
+  auto load_step = [&](int j, uint4 (&xdst)[XLOADS], typename P::Chunk (&wdst)[NW],
+                       uint32_t (&sdst)[XSL]) __attribute__((always_inline)) {
     const int st0 = abs_step(j);
     const int st = st0 < s1 ? st0 : s1 - 1;
 #pragma unroll
     for (int i = 0; i < XLOADS; ++i) xdst[i] = bload16(xrs, xv[i], st * XSB);
+    if constexpr (kBSA) {
+      const uint2 v = *reinterpret_cast<const uint2*>(xsrow[0] + st * 8);
+      sdst[0] = v.x;
+      sdst[1] = v.y;
+    } else if constexpr (kBS) {
+      const int b = st * 8 + xsblk;
+      const int bc = b < nblk ? b : nblk - 1;  // never past the row's K / 32 bytes
+#pragma unroll
+      for (int i = 0; i < XSL; ++i) sdst[i] = xsrow[i][bc];
+    }
 #pragma unroll
     for (int c = 0; c < NW; ++c) wdst[c] = pol.load(wl[c], st);
   };
@@ -702,10 +883,34 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
             make_uint4(src[i].x & keep, src[i].y & keep, src[i].z & keep, src[i].w & keep);
     }
   };
+  // block-scaled: the step's x scale bytes beside the image, [row][kq][u] for block 4 u + kq; a
+  // block past K / 32 (or an inactive step) gets 127 = 2^0 against its zeroed codes
+  auto store_xs = [&](const uint32_t (&src)[XSL], int j) __attribute__((always_inline)) {
+    if constexpr (kBSA) {
+      // bytes b0 .. b7 -> (b0 b4 b1 b5) (b2 b6 b3 b7); no K tail here, and an inactive step's
+      // bytes are never read
+      if (ktid < BM) {
+        uint8_t* dst = xscl + (j & 1) * (BM * 8);
+        *reinterpret_cast<uint2*>(dst + ktid * 8) =
+            make_uint2(__builtin_amdgcn_perm(src[1], src[0], 0x05010400u),
+                       __builtin_amdgcn_perm(src[1], src[0], 0x07030602u));
+      }
+    } else if constexpr (kBS) {
+      const int st = abs_step(j);
+      const bool in = st < s1 && st * 8 + xsblk < nblk;
+      uint8_t* dst = xscl + (j & 1) * (BM * 8);
+#pragma unroll
+      for (int i = 0; i < XSL; ++i) {
+        const int row = (ktid >> 3) + 32 * i;
+        if (row < BM)
+          dst[row * 8 + (xsblk & 3) * 2 + (xsblk >> 2)] = (uint8_t)(in ? src[i] : 127u);
+      }
+    }
+  };
   // local step j; u = j % D at compile time
   auto body = [&](auto uc, int j) __attribute__((always_inline)) {
     constexpr int u = decltype(uc)::value;
-    load_step(j + D - 1, xr[(u + D - 1) % D], wr[(u + D - 1) % D]);
+    load_step(j + D - 1, xr[(u + D - 1) % D], wr[(u + D - 1) % D], xsr[(u + D - 1) % D]);
     if (abs_step(j) < s1) {  // uniform: a k-group's idle tail iterations skip the math
       typename P::Prep pw[NW];
 #pragma unroll
@@ -714,6 +919,14 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
         if constexpr (P::kMaskTail) P::mask_tail(pw[c], abs_step(j), kq, K);
       }
       const uint4* xb = xs + (j & 1) * TILE;
+      // block-scaled: the step's two scale bytes of this lane's row of each M tile (byte u: MFMA u)
+      uint32_t asc[kBS ? MT : 1];
+      if constexpr (kBS) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+          asc[t] = reinterpret_cast<const uint16_t*>(
+              xscl + (j & 1) * (BM * 8))[(t * 16 + (lane & 15)) * 4 + kq];
+      }
 #pragma unroll
       for (int s = 0; s < P::kMfma; ++s) {
         decltype(pol.frag(pw[0], s)) bfrag[NW];
@@ -727,9 +940,16 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
             const int row = t * 16 + (lane & 15);
             const uint4 a0 = xb[x_slot<SLOTS, P>(row, slot0)];
             const uint4 a1 = xb[x_slot<SLOTS, P>(row, slot1)];
+            if constexpr (kBS) {
+#pragma unroll
+              for (int c = 0; c < NW; ++c)
+                acc[t * NW + c] =
+                    P::mfma2s(a0, a1, bfrag[c], acc[t * NW + c], s, asc[t], pw[c].sc);
+            } else {
 #pragma unroll
             for (int c = 0; c < NW; ++c)
               acc[t * NW + c] = P::mfma2(a0, a1, bfrag[c], acc[t * NW + c]);
+            }
           }
         } else {
         const int slot = P::slot(s, kq);
@@ -744,7 +964,10 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
         }
       }
     }
-    if (j + 1 < J) store_x(xr[(u + 1) % D], j + 1);
+    if (j + 1 < J) {
+      store_x(xr[(u + 1) % D], j + 1);
+      store_xs(xsr[(u + 1) % D], j + 1);
+    }
     __syncthreads();
   };
 
@@ -796,9 +1019,11 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
     biasf[c] = (kPre && bias != nullptr) ? bf16_to_f32(bias[nn]) : 0.f;
   }
   static_for<0, D - 1>([&](auto i) __attribute__((always_inline)) {
-    load_step(decltype(i)::value, xr[decltype(i)::value], wr[decltype(i)::value]);
+    load_step(decltype(i)::value, xr[decltype(i)::value], wr[decltype(i)::value],
+              xsr[decltype(i)::value]);
   });
   store_x(xr[0], 0);
+  store_xs(xsr[0], 0);
   __syncthreads();
 
   int j = 0;
@@ -1668,6 +1893,21 @@ int fp8_scaled_mm_launch(const uint8_t* xq, const float* xs, const uint8_t* wq, 
   return launch_gemm(xq, pol, bias, y, M, N, K, stream);
 }
 
+// the MX route's crossover: the float8 dynamic-activation rule (same GEMV decomposition, same MFMA
+// tile), with its own force switch (tao_tune_mx_mfma)
+bool mx_takes_gemv(int64_t M, int64_t N, int64_t K) {
+  return fp8dyn_route_gemv(M, N, K, tuning().mx_mfma, tuning().max_gemv_m);
+}
+
+int mx_scaled_mm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* wq, const uint8_t* ws,
+                        const uint16_t* bias, uint16_t* y, int M, int N, int K,
+                        hipStream_t stream) {
+  const uint4* w = reinterpret_cast<const uint4*>(wq);
+  if (K % 256 == 0)  // (the entry has checked the scale arrays' 8-B alignment)
+    return launch_gemm(xq, MxFp8<true>{w, ws, xs}, bias, y, M, N, K, stream);
+  return launch_gemm(xq, MxFp8<false>{w, ws, xs}, bias, y, M, N, K, stream);
+}
+
 int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq,
                           const uint16_t* ws, const uint16_t* bias, uint16_t* y, int M, int N,
                           int K, hipStream_t stream) {
@@ -1776,6 +2016,12 @@ extern "C" int tao_tune_linear_crossover(int max_gemv_m) {
 extern "C" int tao_tune_fp8dyn_mfma(int on) {
   TAO_CHECK_ARG(on == 0 || on == 1, "tune: fp8dyn mfma must be 0 (built-in route) or 1");
   tao::tuning().fp8dyn_mfma = on;
+  return TAO_OK;
+}
+
+extern "C" int tao_tune_mx_mfma(int on) {
+  TAO_CHECK_ARG(on == 0 || on == 1, "tune: mx mfma must be 0 (built-in route) or 1");
+  tao::tuning().mx_mfma = on;
   return TAO_OK;
 }
 

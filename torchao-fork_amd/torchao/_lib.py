@@ -90,6 +90,10 @@ _SIGNATURES = {
     "tao_fp8_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_fp8_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_tune_fp8dyn_mfma": [_int],
+    "tao_mx_quantize_rows_bf16": [_p, _p, _p, _i64, _i64, _p],
+    "tao_mx_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_mx_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_tune_mx_mfma": [_int],
     "tao_rmsnorm_bf16": [_p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_bf16": [_p, _p, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_partials_bf16": [_p, _p, _i64, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],

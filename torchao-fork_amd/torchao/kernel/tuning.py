@@ -32,6 +32,7 @@ _KNOBS = {
     "int8_quant": ("tao_tune_int8_quant", 1),
     "fp8_gemv": ("tao_tune_fp8_gemv", 3),
     "fp8dyn_mfma": ("tao_tune_fp8dyn_mfma", 1),
+    "mx_mfma": ("tao_tune_mx_mfma", 1),
     "attn": ("tao_tune_attn", 1),
     "splitk_fenced": ("tao_tune_splitk_fenced", 1),
     "gemm_tile": ("tao_tune_gemm_tile", 2),

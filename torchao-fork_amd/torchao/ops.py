@@ -33,6 +33,12 @@ Operators:
     (floatx/float8_layout.py:329-367).
   * ``fp8_dyn_linear`` — the activation quantisation and that product from a bf16 input (one
     token: one launch), bit-identical to ``fp8_quantize_rows`` -> ``fp8_scaled_mm``.
+  * ``mx_quantize_rows`` — the MXFP8 block quantizer (e4m3fn codes, one E8M0 byte per 32
+    elements); replaces ``to_mx`` (prototype/mx_formats/mx_tensor.py:133-326), byte for byte.
+  * ``mx_scaled_mm`` — the block-scaled e4m3fn x e4m3fn product; replaces the ``torch._scaled_mm``
+    call of ``_addmm_mx_dispatch`` (prototype/mx_formats/mx_ops.py).
+  * ``mx_dyn_linear`` — both from a bf16 input (one token: one launch), bit-identical to
+    ``mx_quantize_rows`` -> ``mx_scaled_mm``.
 """
 
 import ctypes
@@ -103,6 +109,16 @@ lib_float8_dyn.define(
 lib_float8_dyn.define(
     "fp8_dyn_linear(Tensor x, Tensor w_fp8, Tensor w_scale, Tensor? bias=None) -> Tensor"
 )
+
+# The MXFP8 ops (torchao.prototype.mx_formats), on a fragment of their own for the same reason;
+# opchecked in tests/test_gpu_mx.py. Codes cross as float8_e4m3fn, scale bytes as uint8.
+lib_mx = torch.library.Library("torchao", "FRAGMENT")
+lib_mx.define("mx_quantize_rows(Tensor x) -> (Tensor, Tensor)")
+lib_mx.define(
+    "mx_scaled_mm(Tensor xq, Tensor x_scale, Tensor wq, Tensor w_scale, Tensor? bias=None) "
+    "-> Tensor"
+)
+lib_mx.define("mx_dyn_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -778,6 +794,124 @@ def _fp8_dyn_linear_cuda(x, w_fp8, w_scale, bias=None):
     return y.reshape(_linear_out_shape(x, N))
 
 
+# ---------------------------------------------------------------------------------------------
+# MXFP8: e4m3fn codes with one E8M0 scale byte per 32-element block (csrc/mx_fp8.hip)
+# ---------------------------------------------------------------------------------------------
+def _check_mx_operand(q, scale, qn, sn):
+    torch._check(q.dtype is torch.float8_e4m3fn, lambda: f"{qn} must be float8_e4m3fn")
+    torch._check(scale.dtype is torch.uint8, lambda: f"{sn} must be uint8 (E8M0 bytes)")
+    K = q.size(-1)
+    torch._check(K % 32 == 0, lambda: f"K ({K}) must be a multiple of 32")
+    torch._check(
+        scale.numel() * 32 == q.numel() and (scale.dim() == 0 or scale.size(-1) == K // 32),
+        lambda: f"{sn} must hold one byte per 32-element block: [..., K/32] = [..., {K // 32}], "
+                f"got {tuple(scale.shape)}")
+    return K
+
+
+def _mx_scale_rows(s, K):
+    """Scale bytes as [rows, K/32], contiguous and 8-B aligned (the MFMA route's 8-B loads)."""
+    s2 = s.reshape(-1, K // 32)
+    return s2 if s2.is_contiguous() and s2.data_ptr() % 8 == 0 else s2.clone()
+
+
+def _check_mx_weight(wq, w_scale):
+    torch._check(wq.dim() == 2, lambda: "wq must be a 2D float8_e4m3fn tensor")
+    return wq.size(0), _check_mx_operand(wq, w_scale, "wq", "w_scale")
+
+
+@torch.library.register_fake("torchao::mx_quantize_rows")
+def _(x):
+    K = x.size(-1)
+    torch._check(K % 32 == 0, lambda: f"K ({K}) must be a multiple of 32")
+    return (x.new_empty(x.shape, dtype=torch.float8_e4m3fn),
+            x.new_empty((*x.shape[:-1], K // 32), dtype=torch.uint8))
+
+
+def _mx_quantize_rows_cuda(x: Tensor):
+    """bf16 x [..., K] -> (e4m3fn codes [..., K], E8M0 bytes uint8 [..., K/32]); to_mx, FLOOR."""
+    torch._check(x.dtype is torch.bfloat16, lambda: "mx quantize (HIP) needs bf16 x")
+    torch._check(x.dim() >= 1, lambda: "mx quantize: x must have at least one dimension")
+    K = x.size(-1)
+    torch._check(K % 32 == 0, lambda: f"K ({K}) must be a multiple of 32")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+    s = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("tao_mx_quantize_rows_bf16", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+    return q.reshape(x.shape), s.reshape(*x.shape[:-1], K // 32)
+
+
+@torch.library.register_fake("torchao::mx_scaled_mm")
+def _(xq, x_scale, wq, w_scale, bias=None):
+    N, K = _check_mx_weight(wq, w_scale)
+    torch._check(xq.size(-1) == K, lambda: f"x last dim {xq.size(-1)} != K {K}")
+    return xq.new_empty(_linear_out_shape(xq, N), dtype=torch.bfloat16)
+
+
+def _mx_scaled_mm_cuda(xq, x_scale, wq, w_scale, bias=None):
+    """y = bf16(sum_b 2^(xs-127) 2^(ws-127) (f(xq) . f(wq))_b + bias), fp32 up to the one rounding
+    (include/torchao_mi355x.h tao_mx_scaled_mm_bf16)."""
+    N, K = _check_mx_weight(wq, w_scale)
+    torch._check(xq.dim() >= 1 and xq.size(-1) == K,
+                 lambda: f"x last dim {xq.size(-1) if xq.dim() else 0} != K {K}")
+    _check_mx_operand(xq, x_scale, "xq", "x_scale")
+    _same_device(xq, x_scale=x_scale, wq=wq, w_scale=w_scale, bias=bias)
+    x2 = xq.reshape(-1, K).contiguous()
+    M = x2.size(0)
+    xs = _mx_scale_rows(x_scale, K)
+    ws = _mx_scale_rows(w_scale, K)
+    wq = wq.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    with torch.cuda.device(xq.device):
+        _lib.call("tao_mx_scaled_mm_bf16", _ptr(x2), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias),
+                  _ptr(y), M, N, K, _stream(xq))
+    return y.reshape(_linear_out_shape(xq, N))
+
+
+@torch.library.register_fake("torchao::mx_dyn_linear")
+def _(x, wq, w_scale, bias=None):
+    N, K = _check_mx_weight(wq, w_scale)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N), dtype=torch.bfloat16)
+
+
+def _mx_dyn_linear_cuda(x, wq, w_scale, bias=None):
+    """The whole linear from a bf16 activation. One token: block quantisation + GEMV in one
+    launch. More: mx_quantize_rows into buffers of the caching allocator, then mx_scaled_mm;
+    bit-identical to calling the two ops."""
+    N, K = _check_mx_weight(wq, w_scale)
+    torch._check(x.dtype is torch.bfloat16, lambda: "mx_dyn_linear (HIP) needs bf16 x")
+    torch._check(x.dim() >= 1 and x.size(-1) == K,
+                 lambda: f"x last dim {x.size(-1) if x.dim() else 0} != K {K}")
+    _same_device(x, wq=wq, w_scale=w_scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    ws = _mx_scale_rows(w_scale, K)
+    wq = wq.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if M == 1 and K <= 65536:
+            _lib.call("tao_mx_dyn_linear_bf16", _ptr(x2), _ptr(wq), _ptr(ws), _ptr(bias),
+                      _ptr(y), 1, N, K, _stream(x))
+        elif M > 0:
+            q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+            s = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
+            _lib.call("tao_mx_quantize_rows_bf16", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+            _lib.call("tao_mx_scaled_mm_bf16", _ptr(q), _ptr(s), _ptr(wq), _ptr(ws), _ptr(bias),
+                      _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
 # ---- register device impls ------------------------------------------------------------------
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
@@ -788,6 +922,7 @@ _OPS_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtorchao_
 _native_served: frozenset = frozenset()
 _native_served_float8: frozenset = frozenset()
 _native_served_float8_dyn: frozenset = frozenset()
+_native_served_mx: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -804,6 +939,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_float8_dyn
         _served.restype = ctypes.c_char_p
         _native_served_float8_dyn = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_mx
+        _served.restype = ctypes.c_char_p
+        _native_served_mx = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -822,6 +960,11 @@ def native_dispatch_float8() -> frozenset:
 def native_dispatch_float8_dyn() -> frozenset:
     """The float8 dynamic-activation ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_float8_dyn
+
+
+def native_dispatch_mx() -> frozenset:
+    """The MXFP8 ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_mx
 
 
 for _name, _fn in [
@@ -855,6 +998,13 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_float8_dyn:
         lib_float8_dyn.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("mx_quantize_rows", _mx_quantize_rows_cuda),
+    ("mx_scaled_mm", _mx_scaled_mm_cuda),
+    ("mx_dyn_linear", _mx_dyn_linear_cuda),
+]:
+    if _name not in _native_served_mx:
+        lib_mx.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")
