@@ -272,6 +272,39 @@ int tao_int4_quantize_bf16(const uint16_t* w, uint32_t* packed, uint16_t* scales
 int tao_int8_quantize_rows_bf16(const uint16_t* w, int8_t* q, uint16_t* scale, int64_t rows,
                                 int64_t K, float eps, void* stream);
 
+/* ---- int8 KV cache (AffineQuantizedKVCache, torchao/_models/llama/model.py:198-240) -----------
+ * k_cache / v_cache [B][Hkv][T][128] int8 codes, k_scale / v_scale [B][Hkv][T] bf16, one scale per
+ * row: symmetric, [-127, 127], eps 1e-5, the arithmetic of _quantize_activation_per_token_absmax in
+ * bf16 (quantization/utils.py:152-182): s = max(bf16(amax / 127), bf16(1e-5)),
+ * q = clamp(rint(bf16(x * bf16(1 / s))), -127, 127). */
+
+/* tao_rope_kv_bf16 (torchao_mi355x_llama.h) with the cache write quantized: qkv
+ * [B*S][(H + 2 Hkv) * 128] bf16 -> q_out [B][H][S][128] rotated; the rotated k and the raw v rows
+ * of the S tokens exact in k_cur / v_cur [B][Hkv][S][128] bf16, and their codes and scales written
+ * to the caches at pos[s] (a position outside [0, T) writes no cache row and sets
+ * tao_decode_status bit 1). head_dim == 128. Replaces apply_rotary_emb and the quantize-and-store
+ * half of AffineQuantizedKVCache.update (model.py:219-233). */
+int tao_rope_kv_q8_bf16(const uint16_t* qkv, const float* freqs, const int64_t* pos,
+                        uint16_t* q_out, int8_t* k_cache, int8_t* v_cache, uint16_t* k_scale,
+                        uint16_t* v_scale, uint16_t* k_cur, uint16_t* v_cur, int64_t B, int64_t S,
+                        int64_t H, int64_t Hkv, int64_t D, int64_t T, void* stream);
+
+/* One-query attention of a decode step over the int8 caches: q [B][H][1][128] bf16 against keys
+ * 0..pos[0] (pos read on the device), keys 0..pos[0]-1 from the codes and scales, the key at pos[0]
+ * exact from k_cur / v_cur [B][Hkv][1][128] (the rows tao_rope_kv_q8_bf16 left there). In fp32:
+ * score_t = k_scale[t] * (q . k8[t]) * scale, o = sum_t p_t * v_scale[t] * v8[t], online softmax.
+ * Any T. splits 1: out [B][1][H*128] bf16. splits 2 or 4: the cached keys split into that many
+ * ranges per head, the unnormalised partials written to partial [B * H][splits][132] fp32 in the
+ * record of tao_attn_decode_split_bf16 (the current key in split 0) for tao_attn_merge_bf16.
+ * H / Hkv in {1, 2, 4, 8}; caches, q, k_cur, v_cur and partial 16-B aligned. Replaces the
+ * dequantize-everything half of AffineQuantizedKVCache.update and the F.scaled_dot_product_attention
+ * after it (model.py:219-233, 441-476) without forming the bf16 cache. */
+int tao_attn_decode_q8_bf16(const uint16_t* q, const int8_t* k_cache, const int8_t* v_cache,
+                            const uint16_t* k_scale, const uint16_t* v_scale,
+                            const uint16_t* k_cur, const uint16_t* v_cur, const int64_t* pos,
+                            float* partial, uint16_t* out, int64_t B, int64_t H, int64_t Hkv,
+                            int64_t D, int64_t T, float scale, int64_t splits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ int int8dyn_decode_status(unsigned* bits);
 int fp8gemv_decode_status(unsigned* bits);
 int fp8dyn_decode_status(unsigned* bits);
 int engine_decode_status(unsigned* bits);
+int kvq8_decode_status(unsigned* bits);
 
 namespace {
 
@@ -942,6 +943,7 @@ extern "C" int tao_decode_status(int* bits) {
   if (rc == TAO_OK) rc = tao::fp8dyn_decode_status(&v);
   if (rc == TAO_OK) rc = tao::sf_decode_status(&v);
   if (rc == TAO_OK) rc = tao::engine_decode_status(&v);
+  if (rc == TAO_OK) rc = tao::kvq8_decode_status(&v);
   unsigned to = 0;  // split-K reducer timeouts of the single-fetch GEMMs (prefill)
   if (rc == TAO_OK) rc = tao_gemm_sf_status(&to);
   if (to != 0) v |= tao::kDecodeErrSplitK;

@@ -12,6 +12,7 @@
 //      is in flight, then runs the GEMV on it: one launch per linear instead of two.
 #include <atomic>
 
+#include "int8_quant_row.h"
 #include "tao_gemv.h"
 
 namespace tao {
@@ -51,31 +52,7 @@ __device__ __forceinline__ int sdot4(uint32_t a, uint32_t b, int c) {
   return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
 }
 
-// per-token scale and its reciprocal from amax (quant_primitives.py:1548-1554, 449-453)
-__device__ __forceinline__ float token_scale(float amax) {
-  float s = round_bf16(amax / 127.f);
-  const float eps = round_bf16(1e-5f);
-  return s < eps ? eps : s;
-}
-
-// q = clamp(round(bf16(x * r)), -127, 127) for the 8 bf16 of one 16-B piece -> 8 int8 bytes
-__device__ __forceinline__ uint2 quant8(const uint4 v, float r) {
-  const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-  uint32_t packed[2] = {0u, 0u};
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float xv = (j & 1) ? bf16hi_to_f32(d[j >> 1]) : bf16lo_to_f32(d[j >> 1]);
-    float t = rintf(round_bf16(xv * r));
-    t = fminf(fmaxf(t, -127.f), 127.f);
-    packed[j >> 2] |= ((uint32_t)(int32_t)t & 0xFFu) << (8 * (j & 3));
-  }
-  return make_uint2(packed[0], packed[1]);
-}
-
-__device__ __forceinline__ float bf16_abs_max2(uint32_t d, float m) {
-  m = fmaxf(m, fabsf(bf16lo_to_f32(d)));
-  return fmaxf(m, fabsf(bf16hi_to_f32(d)));
-}
+// per-token scale (token_scale), codes (quant8) and amax step (bf16_abs_max2): int8_quant_row.h
 
 template <int MT, int RPW, int NPT, int EPI = kEpiNone>
 __global__ __launch_bounds__(512) void int8dyn_gemv_kernel(Int8DynGemvArgs a) {

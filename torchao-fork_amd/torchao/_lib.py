@@ -106,6 +106,10 @@ _SIGNATURES = {
     "tao_int4wo_attn_out_bf16": [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p],
     "tao_attn_decode_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
                              ctypes.c_float, _p],
+    "tao_rope_kv_q8_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
+                            _i64, _p],
+    "tao_attn_decode_q8_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64,
+                                _i64, ctypes.c_float, _i64, _p],
     "tao_attn_prefill_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64,
                               ctypes.c_float, _p],
     "tao_tune_attn": [_int],

@@ -9,6 +9,9 @@ model in place of ``torch.compile(mode="reduce-overhead")`` (:865-875): the one-
 step is captured once in a HIP graph and replayed, the next token and position advancing on
 the device, so a token costs one graph launch and no host round trip until the end.
 
+``--kv_cache_quantization`` (reference generate.py, same flag) keeps the KV cache as int8 codes with
+per-row scales; the result line records ``kv_cache_bytes`` and ``kv_quant``.
+
 No checkpoint or tokenizer travels with the repo (no network): with no ``--checkpoint_path``
 the model is random-initialised with nn.Linear-default weights and the prompt is synthetic
 token ids (seeded), which exercises exactly the shapes and kernels a real checkpoint would.
@@ -341,6 +344,10 @@ def main(argv=None):
     ap.add_argument("--tune", action="append", default=[], metavar="KNOB=V[,V..]",
                     help="launch-shape override for this run (torchao.kernel.tuning knobs; A/B "
                          "measurement only), e.g. --tune cnt_stride=1")
+    ap.add_argument("--kv_cache_quantization", action="store_true",
+                    help="int8 KV cache with per-row scales (AffineQuantizedKVCache; reference "
+                         "generate.py --kv_cache_quantization); the fused decode attention reads "
+                         "the codes (tao_attn_decode_q8_bf16)")
     ap.add_argument("--tile_format", choices=("cuda", "rocm"), default=None,
                     help="nibble map of TensorCoreTiledLayout tensors in --checkpoint_path")
     ap.add_argument("--device", default="cuda")
@@ -403,7 +410,9 @@ def main(argv=None):
     model_bytes = get_model_size_in_bytes(model, ignore_embeddings=True)
 
     B, P, T = args.batch_size, args.prompt_length, args.max_new_tokens
-    model.setup_caches(B, P + T)
+    model.setup_caches(B, P + T, kv_cache_quantization=args.kv_cache_quantization)
+    kv_bytes = sum(b.numel() * b.element_size() for blk in model.layers
+                   for b in blk.attention.kv_cache.buffers())
     if not args.no_fused:
         model.enable_fused_kernels()
     gen = torch.Generator(device="cpu").manual_seed(args.seed + 1)
@@ -442,6 +451,8 @@ def main(argv=None):
         "prefill_ms": round(t_pre * 1e3, 3),
         "tokens_per_s_incl_prefill": round(B * T / (t_pre + t_dec), 2),
         "model_bytes_excl_embeddings": model_bytes,
+        "kv_cache_bytes": kv_bytes,
+        "kv_quant": bool(args.kv_cache_quantization),
         "memory_bandwidth_GBps": round(model_bytes * dec_tok_s / B / 1e9, 1),
         "build_s": round(t_build, 2),
         "quantize_s": round(t_quant, 2),

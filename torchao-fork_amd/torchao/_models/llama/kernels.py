@@ -8,7 +8,7 @@ import torch
 
 from torchao import _lib
 
-__all__ = ["rmsnorm", "rope_kv", "attn_decode", "silu_mul", "int4_linear_swiglu",
+__all__ = ["rmsnorm", "rope_kv", "attn_decode", "rope_kv_q8", "attn_decode_q8", "silu_mul", "int4_linear_swiglu",
            "int4_linear_rope_kv", "int4_decode", "int8wo_decode", "int8dq_decode", "fp8wo_decode",
            "fp8dq_decode", "argmax", "argmax_advance", "check_decode_status"]
 
@@ -272,6 +272,88 @@ def int4_attn_out(part: torch.Tensor, n_head: int, packed: torch.Tensor, sz: tor
               packed.data_ptr(), sz.data_ptr(), N, K, group_size,
               None if residual is None else residual.data_ptr(), y.data_ptr(), _stream(part))
     return y
+
+
+def rope_kv_q8(qkv: torch.Tensor, freqs: torch.Tensor, pos: torch.Tensor, kv, n_head: int):
+    """rope_kv for an AffineQuantizedKVCache ``kv`` (tao_rope_kv_q8_bf16): qkv [B, S, (H + 2 Hkv) D]
+    -> (rotated q [B, H, S, D], k_cur, v_cur [B, Hkv, S, D]): the exact bf16 rotated k and raw v of
+    these S tokens; their int8 codes and bf16 scales are written into kv's buffers at pos."""
+    _check(qkv, torch.bfloat16, "rope_kv_q8 qkv")
+    _check(freqs, torch.float32, "rope_kv_q8 freqs")
+    _check(pos, torch.int64, "rope_kv_q8 pos")
+    for name in ("k_cache", "v_cache"):
+        _check(getattr(kv, name), torch.int8, f"rope_kv_q8 {name}")
+        _check(getattr(kv, name + "_scale"), torch.bfloat16, f"rope_kv_q8 {name}_scale")
+    B, S, _ = qkv.shape
+    _, Hkv, T, D = kv.k_cache.shape
+    if pos.numel() != S or kv.k_cache.shape[0] < B:
+        raise RuntimeError(f"rope_kv_q8: {pos.numel()} positions / batch {kv.k_cache.shape[0]} "
+                           f"for qkv {tuple(qkv.shape)}")
+    q = torch.empty(B, n_head, S, D, dtype=qkv.dtype, device=qkv.device)
+    k_cur = torch.empty(B, Hkv, S, D, dtype=qkv.dtype, device=qkv.device)
+    v_cur = torch.empty_like(k_cur)
+    _lib.call("tao_rope_kv_q8_bf16", qkv.data_ptr(), freqs.data_ptr(), pos.data_ptr(),
+              q.data_ptr(), kv.k_cache.data_ptr(), kv.v_cache.data_ptr(),
+              kv.k_cache_scale.data_ptr(), kv.v_cache_scale.data_ptr(), k_cur.data_ptr(),
+              v_cur.data_ptr(), B, S, n_head, Hkv, D, T, _stream(qkv))
+    return q, k_cur, v_cur
+
+
+# Decode attention over an int8 KV cache (tao_attn_decode_q8_bf16): key ranges per head by the
+# cache's capacity T (a graph is captured once per capacity), as ATTN_SPLIT_MIN_T above: one range
+# for caches below ATTN_Q8_SPLIT_MIN_T rows, ATTN_Q8_SPLITS from there on. Measured per layer
+# (experiments/bench_attn_kvq8.py, profiles/attn_kvq8_bench.jsonl; 32 q / 8 kv heads, graph of 32
+# layers), us at 32 / 128 / 328 / 400 / 512 / 768 / 1024 / 4096 / 8192 / 32768 keys:
+#   one range            4.5 / 5.3 / 7.2 / 7.5 / 8.0 / 9.7 / 11.3 / 31.8 / 59.4 / 224.5
+#   2 ranges + merge     6.6 / 6.8 / 8.0 / 8.4 / 8.4 / 9.3 / 10.0 / 20.5 / 34.7 / 116.5
+#   4 ranges + merge     6.5 / 6.8 / 7.4 / 7.5 / 7.7 / 8.0 /  8.5 / 14.0 / 21.2 /  62.9
+#   4 ranges, no merge   4.8 / 5.0 / 5.5 / 5.6 / 5.8 / 6.2 /  6.8 / 12.0 / 19.4 /  61.6
+# Two ranges never win. Four ranges with the merge launch draw level with one range at 400 keys
+# and win from 512; with the merge folded into an int4 wo (tao_int4wo_attn_out_bf16, which costs wo
+# ~1.5 us, see ATTN_SPLITS above) the pair crosses between 328 and 400 keys. One threshold serves
+# both: 513 rows, where every position past ~400 keys gains; the earlier positions of such a cache
+# lose up to 2 us per layer (32 keys).
+ATTN_Q8_SPLIT_MIN_T = 513
+ATTN_Q8_SPLITS = 4
+
+
+def attn_q8_splits(T: int) -> int:
+    """Key ranges per head of attn_decode_q8 for a cache of T rows."""
+    return ATTN_Q8_SPLITS if T >= ATTN_Q8_SPLIT_MIN_T else 1
+
+
+def attn_decode_q8(q: torch.Tensor, kv, k_cur: torch.Tensor, v_cur: torch.Tensor,
+                   pos: torch.Tensor, scale: float, splits: int = 1) -> torch.Tensor:
+    """q [B, H, 1, D] against keys 0..pos[0] of the AffineQuantizedKVCache ``kv``: keys below
+    pos[0] from its int8 codes and scales, the key at pos[0] from k_cur / v_cur [B, Hkv, 1, D]
+    (rope_kv_q8's exact rows). splits 1 -> [B, 1, H * D] bf16; splits 2 / 4 -> the unnormalised
+    partials [B * H, splits, 132] fp32 for attn_merge."""
+    _check(q, torch.bfloat16, "attn_decode_q8 q")
+    _check(pos, torch.int64, "attn_decode_q8 pos")
+    _check(k_cur, torch.bfloat16, "attn_decode_q8 k_cur")
+    _check(v_cur, torch.bfloat16, "attn_decode_q8 v_cur")
+    for name in ("k_cache", "v_cache"):
+        _check(getattr(kv, name), torch.int8, f"attn_decode_q8 {name}")
+        _check(getattr(kv, name + "_scale"), torch.bfloat16, f"attn_decode_q8 {name}_scale")
+    B, H, S, D = q.shape
+    assert S == 1, "attn_decode_q8 takes one query per (batch, head)"
+    _, Hkv, T, _ = kv.k_cache.shape
+    if kv.k_cache.shape[0] < B:
+        raise RuntimeError(f"attn_decode_q8: batch {B} past the cache's {kv.k_cache.shape[0]}")
+    if tuple(k_cur.shape) != (B, Hkv, 1, D) or v_cur.shape != k_cur.shape:
+        raise RuntimeError(f"attn_decode_q8: k_cur {tuple(k_cur.shape)} / v_cur "
+                           f"{tuple(v_cur.shape)} must be {(B, Hkv, 1, D)}")
+    part = out = None
+    if splits == 1:
+        out = torch.empty(B, 1, H * D, dtype=q.dtype, device=q.device)
+    else:
+        part = torch.empty(B * H, splits, PART_STRIDE, dtype=torch.float32, device=q.device)
+    _lib.call("tao_attn_decode_q8_bf16", q.data_ptr(), kv.k_cache.data_ptr(),
+              kv.v_cache.data_ptr(), kv.k_cache_scale.data_ptr(), kv.v_cache_scale.data_ptr(),
+              k_cur.data_ptr(), v_cur.data_ptr(), pos.data_ptr(),
+              None if part is None else part.data_ptr(), None if out is None else out.data_ptr(),
+              B, H, Hkv, D, T, float(scale), int(splits), _stream(q))
+    return out if splits == 1 else part
 
 
 def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,

@@ -21,7 +21,11 @@ Decode-time structure for one process per GPU and HIP graphs (no tracing compile
     caches; ``prefill_next`` runs the output head at the last position only;
   * otherwise (CPU, or fused kernels off): torch ops, ``index_copy_`` into the caches, a
     causal-mask row gathered by ``input_pos``, ``F.scaled_dot_product_attention(enable_gqa=True)``;
-  * rotary tables precomputed once (Llama-3.1 frequency scaling where configured).
+  * rotary tables precomputed once (Llama-3.1 frequency scaling where configured);
+  * ``setup_caches(..., kv_cache_quantization=True)``: int8 KV caches with per-row scales
+    (AffineQuantizedKVCache, the reference's class). Unfused runs dequantize through ``update``
+    as the reference does; the fused path writes codes with tao_rope_kv_q8_bf16 and attends them in
+    place with tao_attn_decode_q8_bf16 (csrc/kv_q8.hip).
 """
 
 import math
@@ -34,7 +38,7 @@ import torch.nn.functional as F
 
 from torchao.utils import find_multiple
 
-__all__ = ["ModelArgs", "Transformer", "KVCache", "llama_configs"]
+__all__ = ["ModelArgs", "Transformer", "KVCache", "AffineQuantizedKVCache", "llama_configs"]
 
 
 @dataclass
@@ -112,6 +116,49 @@ class KVCache(nn.Module):
         self.k_cache.index_copy_(2, input_pos, k)
         self.v_cache.index_copy_(2, input_pos, v)
         return self.k_cache, self.v_cache
+
+
+class AffineQuantizedKVCache(nn.Module):
+    """The KV cache as per-row symmetric int8 codes [B, H_kv, T, D] with one scale per (batch,
+    head, position) [B, H_kv, T, 1] in the model dtype (reference model.py:198-240; generate.py
+    --kv_cache_quantization): half the bytes of KVCache per cached element.
+
+    ``update`` is the reference formulation: it stores the codes and scales of the new rows and
+    returns the whole cache dequantized, with the new rows exact. It serves CPU and unfused GPU
+    runs; the fused decode path reads the codes in place (kernels.rope_kv_q8 /
+    kernels.attn_decode_q8)."""
+
+    def __init__(self, batch: int, seq_len: int, n_heads: int, head_dim: int,
+                 scale_dtype=torch.bfloat16, device=None):
+        super().__init__()
+        shape = (batch, n_heads, seq_len, head_dim)
+        for name in ("k_cache", "v_cache"):
+            self.register_buffer(name, torch.zeros(shape, dtype=torch.int8, device=device),
+                                 persistent=False)
+            self.register_buffer(name + "_scale",
+                                 torch.ones(shape[:-1] + (1,), dtype=scale_dtype, device=device),
+                                 persistent=False)
+
+    def update(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+        # k, v: [B, H_kv, S, D] at positions input_pos [S]
+        from torchao.quantization.utils import _quantize_activation_per_token_absmax
+
+        out = []
+        for cache, scales, val in ((self.k_cache, self.k_cache_scale, k),
+                                   (self.v_cache, self.v_cache_scale, v)):
+            q, s = _quantize_activation_per_token_absmax(val)
+            cache.index_copy_(2, input_pos, q)
+            scales.index_copy_(2, input_pos, s.unsqueeze(-1).to(scales.dtype))
+            deq = cache * scales
+            deq.index_copy_(2, input_pos, val.to(deq.dtype))
+            out.append(deq)
+        return out[0], out[1]
+
+    @classmethod
+    def from_float(cls, kv_cache: "KVCache") -> "AffineQuantizedKVCache":
+        batch, n_heads, seq_len, head_dim = kv_cache.k_cache.shape
+        return cls(batch, seq_len, n_heads, head_dim, kv_cache.k_cache.dtype,
+                   kv_cache.k_cache.device)
 
 
 class RMSNorm(nn.Module):
@@ -363,7 +410,8 @@ class Attention(nn.Module):
         self.wo = nn.Linear(cfg.dim, cfg.dim, bias=False)
         self.kv_cache: Optional[KVCache] = None
 
-    def forward(self, x, freqs, mask, input_pos):
+    def _attend(self, x, freqs, mask, input_pos):
+        """forward() up to the wo linear -> [B, S, H * D]."""
         B, S, _ = x.shape
         q_sz, kv_sz = self.n_head * self.head_dim, self.n_kv * self.head_dim
         q, k, v = self.wqkv(x).split([q_sz, kv_sz, kv_sz], dim=-1)
@@ -374,16 +422,58 @@ class Attention(nn.Module):
         if self.kv_cache is not None:
             k, v = self.kv_cache.update(input_pos, k, v)
         y = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, enable_gqa=True)
-        return self.wo(y.transpose(1, 2).reshape(B, S, q_sz))
+        return y.transpose(1, 2).reshape(B, S, q_sz)
 
-    def forward_prefill(self, x, freqs_table, mask, input_pos, wo=True):
+    def forward(self, x, freqs, mask, input_pos):
+        return self.wo(self._attend(x, freqs, mask, input_pos))
+
+    def _prefill_q8(self, x, freqs_table, mask, input_pos, from_zero, last_only):
+        """The prefill attention over an int8 KV cache -> [B, S, H * D] (last_only: [B, 1, H * D]
+        of the last query). A prompt at positions 0..S-1 (from_zero; None = look, a host read):
+        rope_kv_q8 writes the codes and leaves the exact bf16 rows k_cur / v_cur [B, Hkv, S, D]
+        (the reference attends these exact rows too: update() returns the new rows
+        undequantized). All queries: torch's SDPA over them, in the unfused forward's own call
+        shape (keys padded to the cache's T rows, which the causal mask hides), NOT
+        tao_attn_prefill_bf16: the next layer quantizes what this attention produces, and only the
+        same attention arithmetic leaves every layer's codes and scales bit-equal to the unfused
+        path's (with tao_attn_prefill_bf16, 92 % of a second layer's codes). last_only: the
+        bf16 decode attention kernel over k_cur / v_cur as caches of capacity S (nothing is
+        quantized behind the last block's attention). Any other positions: the update()
+        formulation and SDPA (forward's math)."""
+        from torchao._models.llama import kernels
+
+        S = x.shape[1]
+        if from_zero is None:
+            from_zero = bool(torch.equal(input_pos, torch.arange(S, device=input_pos.device)))
+        if not (from_zero and self.head_dim == 128 and x.dtype == torch.bfloat16):
+            y = self._attend(x, freqs_table[input_pos], mask, input_pos)
+            return y[:, -1:].contiguous() if last_only else y
+        q, k_cur, v_cur = kernels.rope_kv_q8(self.wqkv(x), freqs_table, input_pos, self.kv_cache,
+                                             self.n_head)
+        scale = 1.0 / math.sqrt(self.head_dim)
+        if last_only:
+            return kernels.attn_decode(q[:, :, -1:].contiguous(), k_cur, v_cur, input_pos[-1:],
+                                       scale)
+        T = mask.shape[-1]
+        k_all = k_cur.new_zeros(k_cur.shape[0], k_cur.shape[1], T, self.head_dim)
+        v_all = torch.zeros_like(k_all)
+        k_all[:, :, :S] = k_cur
+        v_all[:, :, :S] = v_cur
+        y = F.scaled_dot_product_attention(q, k_all, v_all, attn_mask=mask, enable_gqa=True)
+        return y.transpose(1, 2).reshape(x.shape[0], S, self.n_head * self.head_dim)
+
+    def forward_prefill(self, x, freqs_table, mask, input_pos, wo=True, from_zero=None):
         """S > 1 tokens on the gfx950 kernels: wqkv (MFMA GEMM), RoPE + KV-cache write in one
         launch, then F.scaled_dot_product_attention over the caches (forward's math). wo=False:
-        the attention output [B, S, H * D] before the wo linear."""
+        the attention output [B, S, H * D] before the wo linear. from_zero: _prefill_q8's (int8
+        KV cache only)."""
         from torchao._models.llama import kernels
 
         B, S, _ = x.shape
         kv = self.kv_cache
+        if isinstance(kv, AffineQuantizedKVCache):
+            y = self._prefill_q8(x, freqs_table, mask, input_pos, from_zero, False)
+            return self.wo(y) if wo else y
         q = None
         p4 = _int4_parts(self.wqkv) if PREFILL_ROPE else None
         if p4 is not None and x.is_contiguous():  # wqkv GEMM with RoPE + KV write (one launch)
@@ -402,12 +492,15 @@ class Attention(nn.Module):
         y = y.transpose(1, 2).reshape(B, S, self.n_head * self.head_dim)
         return self.wo(y) if wo else y
 
-    def prefill_last(self, x, freqs_table, input_pos):
+    def prefill_last(self, x, freqs_table, input_pos, mask=None, from_zero=None):
         """forward_prefill's q / K / V for every row (the KV caches need them all), then the
-        attention of the LAST query only -> [B, 1, H * D] (the greedy prefill's last block)."""
+        attention of the LAST query only -> [B, 1, H * D] (the greedy prefill's last block).
+        mask, from_zero: _prefill_q8's (int8 KV cache only)."""
         from torchao._models.llama import kernels
 
         kv = self.kv_cache
+        if isinstance(kv, AffineQuantizedKVCache):
+            return self._prefill_q8(x, freqs_table, mask, input_pos, from_zero, True)
         q = None
         p4 = _int4_parts(self.wqkv) if PREFILL_ROPE else None
         if p4 is not None and x.is_contiguous():
@@ -424,6 +517,26 @@ class Attention(nn.Module):
 
         kv = self.kv_cache
         scale = 1.0 / math.sqrt(self.head_dim)
+        if isinstance(kv, AffineQuantizedKVCache):
+            # int8 KV cache: no kernel that writes bf16 K / V may see it. The wqkv GEMV with the
+            # norm inside and no epilogue, RoPE + quantized cache write, the attention over the
+            # codes (merged when split), then wo.
+            qkv = None if norm is None else _fused_decode(x, self.wqkv, norm)
+            if qkv is None:
+                if norm is not None:
+                    x = kernels.rmsnorm(x, norm.weight, norm.eps)
+                qkv = self.wqkv(x)
+            q, k_cur, v_cur = kernels.rope_kv_q8(qkv.view(x.shape[0], 1, -1), freqs_table,
+                                                 input_pos, kv, self.n_head)
+            # int4 wo at batch 1 merges the split partials in its x load (as the bf16 route below)
+            p4 = _int4_parts(self.wo) if q.shape[0] == 1 else None
+            splits = kernels.attn_q8_splits(kv.k_cache.shape[2])
+            y = kernels.attn_decode_q8(q, kv, k_cur, v_cur, input_pos, scale, splits)
+            if splits > 1 and p4 is not None:
+                return kernels.int4_attn_out(y, self.n_head, *p4, residual=residual)
+            if splits > 1:
+                y = kernels.attn_merge(y, q.shape[0], self.n_head)
+            return _linear_plus(y, self.wo, residual)
         # int4 at batch 1: RMSNorm -> wqkv -> RoPE + KV write -> attention in one launch
         pq = None if (norm is None or not kernels.DECODE_QKV_ATTN) else _int4_parts(self.wqkv)
         if (pq is not None and x.numel() == x.shape[-1] and kv.k_cache.shape[0] == 1
@@ -540,14 +653,14 @@ class TransformerBlock(nn.Module):
         h = self.attention.forward_fused(x, freqs_table, input_pos, x, self.attention_norm)
         return self.feed_forward.forward_fused(h, h, self.ffn_norm)
 
-    def forward_prefill(self, x, freqs_table, mask, input_pos):
+    def forward_prefill(self, x, freqs_table, mask, input_pos, from_zero=None):
         """forward() for S > 1 tokens with the norms, RoPE + KV write and SiLU-mul on the
         gfx950 kernels (one launch each instead of ~8, ~20 and 2 eager torch ops)."""
         from torchao._models.llama import kernels
 
         an, fn = self.attention_norm, self.ffn_norm
         h = x + self.attention.forward_prefill(kernels.rmsnorm(x, an.weight, an.eps), freqs_table,
-                                               mask, input_pos)
+                                               mask, input_pos, from_zero=from_zero)
         ff = self.feed_forward
         xn = kernels.rmsnorm(h, fn.weight, fn.eps)
         return h + ff.w2(ff.swiglu_prefill(xn))
@@ -562,24 +675,32 @@ class Transformer(nn.Module):
         self.norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.output = nn.Linear(cfg.dim, cfg.vocab_size, bias=False)
         self.max_batch = self.max_seq = -1
+        self.kv_quant = False
+        self._from_zero_seen = (None, False)
         self.fused = False
 
     @classmethod
     def from_name(cls, name: str) -> "Transformer":
         return cls(ModelArgs.from_name(name))
 
-    def setup_caches(self, max_batch_size: int, max_seq_length: int):
-        """Allocate the static KV caches, rotary table and causal mask on the model's device."""
+    def setup_caches(self, max_batch_size: int, max_seq_length: int,
+                     kv_cache_quantization: bool = False):
+        """Allocate the static KV caches, rotary table and causal mask on the model's device.
+        kv_cache_quantization: int8 caches with per-row scales (AffineQuantizedKVCache; reference
+        setup_caches, model.py:260-330) instead of KVCache."""
         cfg = self.config
         max_seq_length = find_multiple(max_seq_length, 8)
-        if self.max_batch >= max_batch_size and self.max_seq >= max_seq_length:
+        kv_quant = bool(kv_cache_quantization)
+        if (self.max_batch >= max_batch_size and self.max_seq >= max_seq_length
+                and self.kv_quant == kv_quant):
             return
-        self.max_batch, self.max_seq = max_batch_size, max_seq_length
+        self.max_batch, self.max_seq, self.kv_quant = max_batch_size, max_seq_length, kv_quant
         dev = self.norm.weight.device
         dtype = self.norm.weight.dtype
+        cache_cls = AffineQuantizedKVCache if kv_quant else KVCache
         for blk in self.layers:
-            blk.attention.kv_cache = KVCache(max_batch_size, max_seq_length, cfg.n_local_heads,
-                                             cfg.head_dim, dtype, dev)
+            blk.attention.kv_cache = cache_cls(max_batch_size, max_seq_length, cfg.n_local_heads,
+                                               cfg.head_dim, dtype, dev)
         self.register_buffer("freqs", _rope_freqs(cfg, cfg.block_size).to(dev), persistent=False)
         mask = torch.tril(torch.ones(max_seq_length, max_seq_length, dtype=torch.bool, device=dev))
         self.register_buffer("causal_mask", mask, persistent=False)
@@ -616,6 +737,22 @@ class Transformer(nn.Module):
             return y
         return self.output(kernels.rmsnorm(x, self.norm.weight, self.norm.eps))
 
+    def _prompt_from_zero(self, input_pos: torch.Tensor) -> bool:
+        """Whether a prefill's positions are 0..S-1 (what the int8-cache prefill kernels serve:
+        Attention._prefill_q8). A host read of input_pos, once per prefill; a graph capture
+        cannot read, and takes the answer of the eager run on the same positions tensor that
+        precedes every capture (generate.GraphPrefill)."""
+        key = (input_pos.data_ptr(), input_pos.numel())
+        if input_pos.is_cuda and torch.cuda.is_current_stream_capturing():
+            if self._from_zero_seen[0] != key:
+                raise RuntimeError("int8 KV cache: run the prefill once eagerly on these "
+                                   "positions before capturing it")
+            return self._from_zero_seen[1]
+        S = input_pos.numel()
+        ok = bool(torch.equal(input_pos, torch.arange(S, device=input_pos.device)))
+        self._from_zero_seen = (key, ok)
+        return ok
+
     def _layers_prefill(self, idx: torch.Tensor, input_pos: torch.Tensor,
                         last_only: bool = False) -> torch.Tensor:
         """The blocks over S > 1 tokens -> hidden states [B, S, dim]; last_only (greedy prefill,
@@ -627,9 +764,10 @@ class Transformer(nn.Module):
         x = self.tok_embeddings(idx)
         last_only = (last_only and kernels.PREFILL_LAST_ROW and kernels.PREFILL_ADD_NORM
                      and self.config.head_dim == 128 and x.dtype == torch.bfloat16)
+        from_zero = self._prompt_from_zero(input_pos) if self.kv_quant else None
         if not kernels.PREFILL_ADD_NORM:
             for blk in self.layers:
-                x = blk.forward_prefill(x, self.freqs, mask, input_pos)
+                x = blk.forward_prefill(x, self.freqs, mask, input_pos, from_zero)
             return x
         # each residual add fused with the RMSNorm that follows it (tao_add_rmsnorm_bf16): the
         # w2 output of block i is added at block i + 1's attention norm, the last one at the end
@@ -641,10 +779,11 @@ class Transformer(nn.Module):
             else:
                 x, xn = _add_norm(x, pending, an)
             if last_only and i == len(self.layers) - 1:
-                y = blk.attention.prefill_last(xn, self.freqs, input_pos)
+                y = blk.attention.prefill_last(xn, self.freqs, input_pos, mask, from_zero)
                 h = _linear_plus(y, blk.attention.wo, x[:, -1:].contiguous())
                 return ff.forward_fused(h, h, fn)
-            y = blk.attention.forward_prefill(xn, self.freqs, mask, input_pos, wo=False)
+            y = blk.attention.forward_prefill(xn, self.freqs, mask, input_pos, wo=False,
+                                              from_zero=from_zero)
             x, hn = _add_norm(x, _linear_or_partials(y, blk.attention.wo), fn)
             pending = _linear_or_partials(ff.swiglu_prefill(hn), ff.w2)
         if pending is None:

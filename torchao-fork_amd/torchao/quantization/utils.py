@@ -9,7 +9,9 @@
   reference's tile-layout tests are written with (float zero-point domain = tinygemm; nibbles
   packed ``q[2i] << 4 | q[2i+1]`` into uint8 on a GPU device, int32 kept on the host);
 * ``compute_error`` (SQNR in dB, :53-56), ``_get_per_token_block_size`` (:141-146),
-  ``recommended_inductor_config_setter`` (:665-680).
+  ``recommended_inductor_config_setter`` (:665-680);
+* ``_quantize_activation_per_token_absmax`` (:152-182): the per-row symmetric int8 quantizer of the
+  quantized KV cache (``_models/llama/model.py`` AffineQuantizedKVCache).
 """
 
 from typing import List
@@ -141,6 +143,21 @@ def groupwise_affine_dequantize_tensor_from_qparams(w_int4x8, scales, zeros, n_b
 
 def _get_per_token_block_size(x: torch.Tensor) -> List[int]:
     return [1] * (x.dim() - 1) + [x.shape[-1]]
+
+
+def _quantize_activation_per_token_absmax(t: torch.Tensor):
+    """Symmetric int8 in [-127, 127] with one scale per last-dim row, eps 1e-5: t [..., K] ->
+    (codes int8 [..., K], scale [...]) (reference utils.py:152-182). The scale is in t's dtype
+    (fp32 for fp16 input) and every step runs in t's dtype, as the reference's choose_qparams_affine
+    / quantize_affine do: s = max(amax / 127, 1e-5), q = clamp(round(t * (1 / s)), -127, 127). For
+    bf16 that is the arithmetic of csrc/int8_quant_row.h (the quantized KV-cache write of
+    tao_rope_kv_q8_bf16 and the per-token activation quantizer), bit for bit."""
+    amax = torch.maximum(-torch.clamp(t.amin(dim=-1), max=0), torch.clamp(t.amax(dim=-1), min=0))
+    scale = torch.clamp(amax / 127.0, min=1e-5)
+    if t.dtype == torch.float16:
+        scale = scale.to(torch.float32)
+    q = torch.clamp(torch.round(t * (1.0 / scale).unsqueeze(-1)), -127, 127)
+    return q.to(torch.int8), scale
 
 
 def recommended_inductor_config_setter():
