@@ -220,6 +220,42 @@ int tao_mx_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const uint8_t* 
                            const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                            void* stream);
 
+/* ---- MXFP4 weights under MXFP8 activations: e2m1 codes, two per byte, one E8M0 scale byte per
+ * 32-element block (csrc/mx_fp4.hip). Storage is the reference's: element 2 j of a row in the HIGH
+ * nibble of byte j, element 2 j + 1 in the low nibble. ------------------------------------------ */
+
+/* Block quantizer of x [M][K] bf16 to e2m1, FLOOR mode: per block of 32 consecutive k,
+ *   byte = max((biased fp32 exponent field of amax|x|) - 2, 0), 255 if the amax is NaN,
+ *   q    = e2m1_rne(float(x) / d) saturating at +-6 (no clamp before the cast: +-inf -> +-6), d the
+ *          fp32 number with `byte` as exponent field, at least 2^-126.
+ * q uint8 [M][K/2] packed codes, scale uint8 [M][K/32] E8M0 bytes. Replaces to_mx
+ * (torchao/prototype/mx_formats/mx_tensor.py:133-326, elem_dtype float4_e2m1fn_x2, block_size 32,
+ * ScaleCalculationMode.FLOOR) with f32_to_f4_unpacked and pack_uint4, byte for byte (the sign bit
+ * of the nibble written for a NaN input is the input's). K % 32 == 0; M == 0 is a no-op; x, q 16-B
+ * aligned, M * K below 2^32. */
+int tao_mxfp4_quantize_rows_bf16(const uint16_t* x, uint8_t* q, uint8_t* scale, int64_t M,
+                                 int64_t K, void* stream);
+
+/* y[m][n] = bf16( acc[m][n] + fp32(bias[n]) ),
+ * acc[m][n] = sum_b 2^(xs[m][b]-127) 2^(ws[n][b]-127) sum_{k in block b} e4m3(xq[m][k]) e2m1(wq[n][k])
+ * in fp32: one rounding to bf16. xq uint8 [M][K] e4m3fn codes, wq uint8 [N][K/2] packed e2m1 codes;
+ * xs uint8 [M][K/32], ws uint8 [N][K/32] E8M0 bytes (255 is NaN); bias bf16 [N] or NULL. Replaces
+ * the emulated branch of _addmm_mx_dispatch (torchao/prototype/mx_formats/mx_ops.py:144-156:
+ * to_dtype of both operands and a bf16 addmm) for an e4m3fn activation and an e2m1 weight.
+ * K % 32 == 0, any N, M >= 0 (M == 0 is a no-op); xq, wq 16-B aligned, and xs, ws 8-B aligned where
+ * K % 256 == 0; M * K and N * K below 2^32. */
+int tao_mxfp4w_scaled_mm_bf16(const uint8_t* xq, const uint8_t* xs, const uint8_t* wq,
+                              const uint8_t* ws, const uint16_t* bias, uint16_t* y, int64_t M,
+                              int64_t N, int64_t K, void* stream);
+
+/* One token (M <= 1): tao_mx_quantize_rows_bf16 of the bf16 token x [K] (e4m3fn blocks) and the
+ * product above in one launch, bit-identical to the two calls. Replaces MXTensor.to_mx on the
+ * activation followed by _addmm_mx_dispatch (torchao/prototype/mx_formats/mx_ops.py). More tokens
+ * are the two calls. K % 32 == 0, K <= 65536. */
+int tao_mxfp4w_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const uint8_t* ws,
+                               const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                               void* stream);
+
 /* ---- int8 dynamic activation x int8 weight -------------------------------------------------- */
 
 /* Per-token symmetric reduced-range int8 quantization of x [M][K] bf16:

@@ -7,6 +7,7 @@
 //   Int8Dyn : int8 x (per-token scale), int8 W (per-channel scale),   v_mfma_i32_16x16x64_i8
 //   Fp8Dyn  : e4m3fn x (per-token scale), e4m3fn W (per-row scale),   v_mfma_scale_f32_16x16x128_f8f6f4
 //   MxFp8   : e4m3fn x and W, one E8M0 scale byte per 32-k block,    v_mfma_scale_f32_16x16x128_f8f6f4
+//   MxFp8Fp4: e4m3fn x, e2m1 W (two codes per byte), the same scales, the same MFMA (cbsz 0, blgp 4)
 // Replaces aten._weight_int4pack_mm (tensor_core_tiled_layout.py:104), mm(x, w.to(bf16)) * s
 // (plain_layout.py:256-266), int_scaled_matmul + scales (plain_layout.py:294-315,
 // kernel/intmm.py:108-143), F.linear(x, w.dequantize()) (floatx/float8_layout.py:391-396) and the
@@ -654,6 +655,139 @@ struct MxFp8 {
     return u == 0 ? __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, (int)asc, 0,
                                                                       (int)bsc)
                   : __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 1, (int)asc, 1,
+                                                                      (int)bsc);
+  }
+  static constexpr bool kRowF = false, kColF = false;
+  __device__ __forceinline__ const uint16_t* row_factor() const { return nullptr; }
+  __device__ __forceinline__ const uint16_t* col_factor() const { return nullptr; }
+  __device__ __forceinline__ float epi(float acc, float, float) const { return acc; }
+};
+
+// MxFp8Fp4: MxFp8 with an e2m1 W (MXFP4 weights, mx_fp4.hip): cbsz 0 (A e4m3), blgp 4 (B e2m1,
+// four operand VGPRs). MxFp8's tile, x image, x scale array, 256-k step, two MFMAs per step and
+// scale bytes unchanged; W is 128 B per row and step, one full line, so a wave loads its 16 rows
+// with two instructions (lane l: row 8 h + l / 8, bytes 16 (l % 8)) instead of four.
+// Layout of the B operand, as the one-MFMA probe with one-hot data measured it
+// (experiments/probe_fp4_layout.hip; the exact k map of tests/test_gpu_mxfp4.py holds it):
+//  * lane (i, g) holds, in its four VGPRs, the 32 contiguous k 32 g .. + 32 of the MFMA's 128,
+//    in A's numbering (where lane (i, g) holds k 16 g .. + 16 and 64 + 16 g .. + 16, see MxFp8):
+//    VGPR d, nibble p (p = 0 the lowest four bits) is k 32 g + 8 d + p. So, unlike A, a lane holds
+//    one whole block: block g, the one whose scale byte it supplies.
+//  * the even element is the LOW nibble. Storage has it in the high nibble (the reference's
+//    packing), so the nibbles of every byte are swapped after the stage read (a shift each way
+//    and one bit-field insert per dword); the stored bytes are never changed.
+// So for MFMA u of a step lane (n, kq) takes the 16 B of block 4 u + kq of row n: slot 4 u + kq
+// of the row's eight 16-B slots in the per-wave stage ([16 rows][8 slots], XOR-swizzled by
+// row >> 1: the 16 lanes of each ds_read_b128 pass, rows {0-3, 12-15} of one kq and {4-11} of the
+// next, hit 16 distinct 16-B granules). A 16-B piece is a whole block, inside the row or past
+// it: mask_tail zeroes it and replaces its scale byte by 127, as MxFp8 does.
+template <bool AL>
+struct MxFp8Fp4 {
+  static constexpr int kPathId = 6;  // no measured table entries: the heuristic shapes
+  static constexpr bool kMaskTail = !AL;
+  static constexpr bool kBlockScaled = true;
+  static constexpr bool kScaleAligned = AL;
+  static constexpr int kABytes = 1;  // e4m3fn x
+  static constexpr int kKStep = 256;
+  static constexpr int kMfma = 2;
+  static constexpr int kASlots = 2;  // 16-B x slots per MFMA
+  static constexpr int kMaxBM = 128;
+  static constexpr int kPrefKG = 1;
+  static constexpr int kMaxKG = 2;
+  static constexpr int kMinSlice = 4;
+  typedef f32x4_t Acc;
+  const uint4* w;          // [N][K/32] 16-B blocks of e2m1 codes, element 2 j in the high nibble
+  const uint8_t* wscale;   // [N][K/32] E8M0 bytes
+  const uint8_t* xscale;   // [M][K/32] E8M0 bytes
+  static constexpr int kStage = 128;  // uint4 per wave: [16 rows][8 slots]
+  struct Lane {
+    Rsrc w;
+    uint32_t wv0, wv1;
+    const uint8_t* s;  // the lane's row of scale bytes
+    int nblk, kq;
+  };
+  struct Chunk {
+    uint4 v[2];       // rows l / 8 and 8 + l / 8, bytes 16 (l % 8) of the step's 128
+    uint32_t s0, s1;  // as MxFp8::Chunk
+  };
+  struct Prep {
+    uint4 v[2];   // v[u]: block 4 u + kq of row n, nibbles in the instruction's order
+    uint32_t sc;  // byte u: the scale of block 4 u + kq
+  };
+  static __device__ __forceinline__ int slot(int s, int kq) { return Int8Dyn::slot(s, kq); }
+  static __device__ __forceinline__ int xswz(int row) { return row & 15; }
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    Lane L;
+    const uint32_t rb = (uint32_t)K >> 1;  // bytes per row
+    L.w = make_rsrc(w, (uint32_t)N * rb);
+    const int base = bn - (lane & 15);
+    const int r0 = base + (lane >> 3), r1 = r0 + 8;
+    L.wv0 = (uint32_t)(r0 < N ? r0 : N - 1) * rb + 16 * (lane & 7);
+    L.wv1 = (uint32_t)(r1 < N ? r1 : N - 1) * rb + 16 * (lane & 7);
+    L.nblk = K >> 5;
+    L.kq = lane >> 4;
+    L.s = wscale + (size_t)(bn < N ? bn : N - 1) * L.nblk;
+    return L;
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    Chunk ch;
+    ch.v[0] = bload16<kNT>(L.w, L.wv0, st * 128);
+    ch.v[1] = bload16<kNT>(L.w, L.wv1, st * 128);
+    if constexpr (AL) {
+      const uint2 v = *reinterpret_cast<const uint2*>(L.s + st * 8);
+      ch.s0 = v.x;
+      ch.s1 = v.y;
+    } else {
+      const int b0 = st * 8 + L.kq, b1 = b0 + 4;
+      ch.s0 = L.s[b0 < L.nblk ? b0 : L.nblk - 1];
+      ch.s1 = L.s[b1 < L.nblk ? b1 : L.nblk - 1];
+    }
+    return ch;
+  }
+  static __device__ __forceinline__ uint32_t swap_nibbles(uint32_t v) {
+    return ((v << 4) & 0xF0F0F0F0u) | ((v >> 4) & 0x0F0F0F0Fu);
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    const int r = lane >> 3, c = lane & 7;
+    stage[r * 8 + (c ^ (r >> 1))] = ch.v[0];
+    stage[(r + 8) * 8 + (c ^ ((r + 8) >> 1))] = ch.v[1];
+    const int n = lane & 15, kq = lane >> 4;
+    Prep p;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const uint4 q = stage[n * 8 + ((4 * u + kq) ^ (n >> 1))];
+      p.v[u] = make_uint4(swap_nibbles(q.x), swap_nibbles(q.y), swap_nibbles(q.z),
+                          swap_nibbles(q.w));
+    }
+    if constexpr (AL) {
+      const int sh = 8 * kq;
+      p.sc = ((ch.s0 >> sh) & 0xFFu) | (((ch.s1 >> sh) & 0xFFu) << 8);
+    } else {
+      p.sc = ch.s0 | (ch.s1 << 8);
+    }
+    return p;
+  }
+  // blocks 4 u + kq at or past K / 32: codes zeroed, scale byte 127
+  static __device__ __forceinline__ void mask_tail(Prep& p, int st, int kq, int K) {
+    const int b0 = st * kKStep + 32 * kq;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const uint32_t k = b0 + 128 * u < K ? ~0u : 0u;
+      p.v[u] = make_uint4(p.v[u].x & k, p.v[u].y & k, p.v[u].z & k, p.v[u].w & k);
+    }
+    p.sc = (b0 < K ? p.sc & 0xFFu : 127u) | (b0 + 128 < K ? p.sc & 0xFF00u : 127u << 8);
+  }
+  __device__ __forceinline__ i32x8_t frag(const Prep& p, int u) const {
+    const uint4 v = u == 0 ? p.v[0] : p.v[1];
+    return i32x8_t{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};  // blgp 4 reads four
+  }
+  // cbsz 0 / blgp 4: A e4m3, B e2m1; MFMA u takes byte u of both scale VGPRs
+  static __device__ __forceinline__ Acc mfma2s(const uint4& a0, const uint4& a1, const i32x8_t& b,
+                                               Acc c, int u, uint32_t asc, uint32_t bsc) {
+    const i32x8_t a = Fp8Dyn::pair(a0, a1);
+    return u == 0 ? __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 4, 0, (int)asc, 0,
+                                                                      (int)bsc)
+                  : __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 4, 1, (int)asc, 1,
                                                                       (int)bsc);
   }
   static constexpr bool kRowF = false, kColF = false;
@@ -1906,6 +2040,16 @@ int mx_scaled_mm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* wq,
   if (K % 256 == 0)  // (the entry has checked the scale arrays' 8-B alignment)
     return launch_gemm(xq, MxFp8<true>{w, ws, xs}, bias, y, M, N, K, stream);
   return launch_gemm(xq, MxFp8<false>{w, ws, xs}, bias, y, M, N, K, stream);
+}
+
+// MXFP4 weights (mx_fp4.hip): the same route rule (mx_takes_gemv) and the same split by K % 256
+int mxfp4w_scaled_mm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* wq,
+                            const uint8_t* ws, const uint16_t* bias, uint16_t* y, int M, int N,
+                            int K, hipStream_t stream) {
+  const uint4* w = reinterpret_cast<const uint4*>(wq);
+  if (K % 256 == 0)
+    return launch_gemm(xq, MxFp8Fp4<true>{w, ws, xs}, bias, y, M, N, K, stream);
+  return launch_gemm(xq, MxFp8Fp4<false>{w, ws, xs}, bias, y, M, N, K, stream);
 }
 
 int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq,

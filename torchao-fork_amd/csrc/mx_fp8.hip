@@ -44,6 +44,7 @@
 // block apart equals scaling their sum), then accumulated in fp32.
 #include "fp8_dyn_host.h"
 #include "fp8_quant_row.h"
+#include "mx_block.h"
 #include "tao_gemv.h"
 
 namespace tao {
@@ -55,35 +56,7 @@ bool mx_takes_gemv(int64_t M, int64_t N, int64_t K);    // gemm_mfma.hip
 
 namespace {
 
-// ---- the quantizer's arithmetic (shared by the row quantizer and the one-token prologue) -------
-// max(m, |.|) over the 8 bf16 of one 16-B piece, on the 15-bit magnitude patterns
-__device__ __forceinline__ uint32_t mx_amax8(const uint4 v, uint32_t m) {
-  const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t a = d[j] & 0x7FFF7FFFu;
-    const uint32_t lo = a & 0xFFFFu, hi = a >> 16;
-    m = m > lo ? m : lo;
-    m = m > hi ? m : hi;
-  }
-  return m;
-}
-// the block's E8M0 byte from its amax pattern: exponent field - 8, floored at 0; NaN -> 255
-__device__ __forceinline__ uint32_t mx_scale_byte(uint32_t amax15) {
-  const uint32_t e = amax15 >> 7;
-  return amax15 > 0x7F80u ? 255u : (e > 8u ? e - 8u : 0u);
-}
-// the fp32 number with that exponent field, at least 2^-126 (byte 255: +inf)
-__device__ __forceinline__ float mx_divisor(uint32_t byte) {
-  return __builtin_bit_cast(float, (byte > 1u ? byte : 1u) << 23);
-}
-
-// d * 2^(xb - 127) * 2^(wb - 127); a byte 255 is NaN
-__device__ __forceinline__ float mx_scaled(float d, uint32_t xb, uint32_t wb) {
-  const float v = ldexpf(d, (int)(xb + wb) - 254);
-  return (xb == 255u || wb == 255u) ? __builtin_nanf("") : v;
-}
-
+// ---- the quantizer (its arithmetic, shared with the one-token prologues: mx_block.h) -----------
 // One thread per 16 elements (half a block); lanes 2i, 2i + 1 share block i of the flat run.
 __global__ __launch_bounds__(256) void mx_quantize_rows_kernel(const uint4* __restrict__ x,
                                                                uint4* __restrict__ q,

@@ -2,7 +2,8 @@
 // once per linear per forward: int4_weight_only_linear, int8_weight_only_linear,
 // int8_quantize_per_token, int8_scaled_mm, int8_dyn_linear, the float8 weight-only set
 // fp8_weight_only_linear, fp8_quantize_rows, fp8_dequantize, and the float8 dynamic-activation set
-// fp8_scaled_mm, fp8_dyn_linear, and the MXFP8 set mx_quantize_rows, mx_scaled_mm, mx_dyn_linear.
+// fp8_scaled_mm, fp8_dyn_linear, the MXFP8 set mx_quantize_rows, mx_scaled_mm, mx_dyn_linear, and the
+// MXFP4-weight set mxfp4_quantize_rows, mxfp4w_scaled_mm, mxfp4w_dyn_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -428,6 +429,103 @@ Tensor mx_dyn_linear(const Tensor& x, const Tensor& wq, const Tensor& w_scale,
   return y.reshape(out_shape(x, N));
 }
 
+// ---- MXFP4 weights under MXFP8 activations (ops.py _mxfp4w_scaled_mm_cuda & co) --------------------
+// wq: uint8 [N, K/2], two e2m1 codes per byte (element 2 j in the high nibble); scales as above.
+int64_t check_mxfp4_weight(const Tensor& wq, const Tensor& w_scale) {
+  TORCH_CHECK(wq.dim() == 2 && wq.scalar_type() == at::kByte,
+              "wq must be a 2D uint8 tensor of packed e2m1 codes [N, K/2]");
+  TORCH_CHECK(w_scale.scalar_type() == at::kByte, "w_scale must be uint8 (E8M0 bytes)");
+  const int64_t K = 2 * wq.size(1);
+  TORCH_CHECK(K % 32 == 0, "K (", K, ") must be a multiple of 32");
+  TORCH_CHECK(w_scale.numel() * 32 == 2 * wq.numel() &&
+                  (w_scale.dim() == 0 || w_scale.size(-1) == K / 32),
+              "w_scale must hold one byte per 32-element block: [..., K/32] = [..., ", K / 32,
+              "], got ", w_scale.sizes());
+  return K;
+}
+
+std::tuple<Tensor, Tensor> mxfp4_quantize_rows(const Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), "expected x on a HIP device, got ", x.device());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "mxfp4 quantize (HIP) needs bf16 x");
+  TORCH_CHECK(x.dim() >= 1, "mxfp4 quantize: x must have at least one dimension");
+  const int64_t K = x.size(-1);
+  TORCH_CHECK(K % 32 == 0, "K (", K, ") must be a multiple of 32");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor q = at::empty({M, K / 2}, x.options().dtype(at::kByte));
+  Tensor s = at::empty({M, K / 32}, x.options().dtype(at::kByte));
+  check_rc(tao_mxfp4_quantize_rows_bf16(cptr<uint16_t>(x2), mptr<uint8_t>(q), mptr<uint8_t>(s), M,
+                                        K, stream_of(x)),
+           "tao_mxfp4_quantize_rows_bf16");
+  std::vector<int64_t> qs(x.sizes().begin(), x.sizes().end() - 1), ss = qs;
+  qs.push_back(K / 2);
+  ss.push_back(K / 32);
+  return {q.reshape(qs), s.reshape(ss)};
+}
+
+Tensor mxfp4w_scaled_mm(const Tensor& xq, const Tensor& x_scale, const Tensor& wq,
+                        const Tensor& w_scale, const std::optional<Tensor>& bias) {
+  const int64_t K = check_mxfp4_weight(wq, w_scale), N = wq.size(0);
+  TORCH_CHECK(xq.dim() >= 1 && xq.size(-1) == K, "x last dim ", xq.dim() ? xq.size(-1) : 0,
+              " != K ", K);
+  check_mx_operand(xq, x_scale, "xq", "x_scale");
+  check_device(xq, x_scale, "x_scale");
+  check_device(xq, wq, "wq");
+  check_device(xq, w_scale, "w_scale");
+  check_device(xq, bias, "bias");
+  const Tensor x2 = xq.reshape({-1, K}).contiguous();
+  const int64_t M = x2.size(0);
+  const Tensor xs = mx_scale_rows(x_scale, K);
+  const Tensor ws = mx_scale_rows(w_scale, K);
+  const Tensor w = wq.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(xq.device());
+  Tensor y = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
+  check_rc(tao_mxfp4w_scaled_mm_bf16(cptr<uint8_t>(x2), cptr<uint8_t>(xs), cptr<uint8_t>(w),
+                                     cptr<uint8_t>(ws), b ? cptr<uint16_t>(*b) : nullptr,
+                                     mptr<uint16_t>(y), M, N, K, stream_of(xq)),
+           "tao_mxfp4w_scaled_mm_bf16");
+  return y.reshape(out_shape(xq, N));
+}
+
+Tensor mxfp4w_dyn_linear(const Tensor& x, const Tensor& wq, const Tensor& w_scale,
+                         const std::optional<Tensor>& bias) {
+  const int64_t K = check_mxfp4_weight(wq, w_scale), N = wq.size(0);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "mxfp4w_dyn_linear (HIP) needs bf16 x");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "x last dim ", x.dim() ? x.size(-1) : 0, " != K ",
+              K);
+  check_device(x, wq, "wq");
+  check_device(x, w_scale, "w_scale");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const Tensor ws = mx_scale_rows(w_scale, K);
+  const Tensor w = wq.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  const uint16_t* bp = b ? cptr<uint16_t>(*b) : nullptr;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  if (M == 1 && K <= 65536) {
+    check_rc(tao_mxfp4w_dyn_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(w), cptr<uint8_t>(ws),
+                                        bp, mptr<uint16_t>(y), 1, N, K, stream_of(x)),
+             "tao_mxfp4w_dyn_linear_bf16");
+  } else if (M > 0) {
+    // the activation's e4m3fn codes and scale bytes live in buffers of the caching allocator
+    // between the two launches
+    Tensor q = at::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+    Tensor s = at::empty({M, K / 32}, x.options().dtype(at::kByte));
+    check_rc(tao_mx_quantize_rows_bf16(cptr<uint16_t>(x2), mptr<uint8_t>(q), mptr<uint8_t>(s), M, K,
+                                       stream_of(x)),
+             "tao_mx_quantize_rows_bf16");
+    check_rc(tao_mxfp4w_scaled_mm_bf16(cptr<uint8_t>(q), cptr<uint8_t>(s), cptr<uint8_t>(w),
+                                       cptr<uint8_t>(ws), bp, mptr<uint16_t>(y), M, N, K,
+                                       stream_of(x)),
+             "tao_mxfp4w_scaled_mm_bf16");
+  }
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
@@ -444,6 +542,9 @@ TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
   m.impl("mx_quantize_rows", &mx_quantize_rows);
   m.impl("mx_scaled_mm", &mx_scaled_mm);
   m.impl("mx_dyn_linear", &mx_dyn_linear);
+  m.impl("mxfp4_quantize_rows", &mxfp4_quantize_rows);
+  m.impl("mxfp4w_scaled_mm", &mxfp4w_scaled_mm);
+  m.impl("mxfp4w_dyn_linear", &mxfp4w_dyn_linear);
 }
 
 // Probe for torchao.ops (which ops this library serves).
@@ -465,4 +566,9 @@ extern "C" const char* tao_torch_ops_served_float8_dyn(void) {
 // The MXFP8 ops served here, again a set of their own.
 extern "C" const char* tao_torch_ops_served_mx(void) {
   return "mx_quantize_rows,mx_scaled_mm,mx_dyn_linear";
+}
+
+// The MXFP4-weight ops served here, a set of their own as well.
+extern "C" const char* tao_torch_ops_served_mxfp4(void) {
+  return "mxfp4_quantize_rows,mxfp4w_scaled_mm,mxfp4w_dyn_linear";
 }

@@ -94,6 +94,9 @@ _SIGNATURES = {
     "tao_mx_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_mx_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_tune_mx_mfma": [_int],
+    "tao_mxfp4_quantize_rows_bf16": [_p, _p, _p, _i64, _i64, _p],
+    "tao_mxfp4w_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_mxfp4w_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_rmsnorm_bf16": [_p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_bf16": [_p, _p, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_partials_bf16": [_p, _p, _i64, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],

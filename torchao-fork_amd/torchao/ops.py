@@ -39,6 +39,8 @@ Operators:
     call of ``_addmm_mx_dispatch`` (prototype/mx_formats/mx_ops.py).
   * ``mx_dyn_linear`` — both from a bf16 input (one token: one launch), bit-identical to
     ``mx_quantize_rows`` -> ``mx_scaled_mm``.
+  * ``mxfp4_quantize_rows`` / ``mxfp4w_scaled_mm`` / ``mxfp4w_dyn_linear`` — the same three for
+    e2m1 weights (two codes per byte) under e4m3fn activations (csrc/mx_fp4.hip).
 """
 
 import ctypes
@@ -119,6 +121,15 @@ lib_mx.define(
     "-> Tensor"
 )
 lib_mx.define("mx_dyn_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias=None) -> Tensor")
+# The MXFP4-weight ops (e4m3fn activation x e2m1 weight), again on a fragment of their own; opchecked
+# in tests/test_gpu_mxfp4.py. Weight codes cross as uint8 [N, K/2], two per byte.
+lib_mxfp4 = torch.library.Library("torchao", "FRAGMENT")
+lib_mxfp4.define("mxfp4_quantize_rows(Tensor x) -> (Tensor, Tensor)")
+lib_mxfp4.define(
+    "mxfp4w_scaled_mm(Tensor xq, Tensor x_scale, Tensor wq, Tensor w_scale, Tensor? bias=None) "
+    "-> Tensor")
+lib_mxfp4.define(
+    "mxfp4w_dyn_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -912,6 +923,117 @@ def _mx_dyn_linear_cuda(x, wq, w_scale, bias=None):
     return y.reshape(_linear_out_shape(x, N))
 
 
+# ---------------------------------------------------------------------------------------------
+# MXFP4 weights under MXFP8 activations: e2m1 codes, two per byte (element 2 j in the high nibble),
+# one E8M0 scale byte per 32-element block (csrc/mx_fp4.hip)
+# ---------------------------------------------------------------------------------------------
+def _check_mxfp4_weight(wq, w_scale):
+    torch._check(wq.dim() == 2 and wq.dtype is torch.uint8,
+                 lambda: "wq must be a 2D uint8 tensor of packed e2m1 codes [N, K/2]")
+    torch._check(w_scale.dtype is torch.uint8, lambda: "w_scale must be uint8 (E8M0 bytes)")
+    K = 2 * wq.size(1)
+    torch._check(K % 32 == 0, lambda: f"K ({K}) must be a multiple of 32")
+    torch._check(
+        w_scale.numel() * 32 == 2 * wq.numel()
+        and (w_scale.dim() == 0 or w_scale.size(-1) == K // 32),
+        lambda: f"w_scale must hold one byte per 32-element block: [..., K/32] = [..., {K // 32}], "
+                f"got {tuple(w_scale.shape)}")
+    return wq.size(0), K
+
+
+@torch.library.register_fake("torchao::mxfp4_quantize_rows")
+def _(x):
+    K = x.size(-1)
+    torch._check(K % 32 == 0, lambda: f"K ({K}) must be a multiple of 32")
+    return (x.new_empty((*x.shape[:-1], K // 2), dtype=torch.uint8),
+            x.new_empty((*x.shape[:-1], K // 32), dtype=torch.uint8))
+
+
+def _mxfp4_quantize_rows_cuda(x: Tensor):
+    """bf16 x [..., K] -> (packed e2m1 codes uint8 [..., K/2], E8M0 bytes uint8 [..., K/32]);
+    to_mx with float4_e2m1fn_x2, FLOOR."""
+    torch._check(x.dtype is torch.bfloat16, lambda: "mxfp4 quantize (HIP) needs bf16 x")
+    torch._check(x.dim() >= 1, lambda: "mxfp4 quantize: x must have at least one dimension")
+    K = x.size(-1)
+    torch._check(K % 32 == 0, lambda: f"K ({K}) must be a multiple of 32")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    q = torch.empty((M, K // 2), dtype=torch.uint8, device=x.device)
+    s = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("tao_mxfp4_quantize_rows_bf16", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+    return q.reshape(*x.shape[:-1], K // 2), s.reshape(*x.shape[:-1], K // 32)
+
+
+@torch.library.register_fake("torchao::mxfp4w_scaled_mm")
+def _(xq, x_scale, wq, w_scale, bias=None):
+    N, K = _check_mxfp4_weight(wq, w_scale)
+    torch._check(xq.size(-1) == K, lambda: f"x last dim {xq.size(-1)} != K {K}")
+    return xq.new_empty(_linear_out_shape(xq, N), dtype=torch.bfloat16)
+
+
+def _mxfp4w_scaled_mm_cuda(xq, x_scale, wq, w_scale, bias=None):
+    """y = bf16(sum_b 2^(xs-127) 2^(ws-127) (e4m3(xq) . e2m1(wq))_b + bias), fp32 up to the one
+    rounding (include/torchao_mi355x.h tao_mxfp4w_scaled_mm_bf16)."""
+    N, K = _check_mxfp4_weight(wq, w_scale)
+    torch._check(xq.dim() >= 1 and xq.size(-1) == K,
+                 lambda: f"x last dim {xq.size(-1) if xq.dim() else 0} != K {K}")
+    _check_mx_operand(xq, x_scale, "xq", "x_scale")
+    _same_device(xq, x_scale=x_scale, wq=wq, w_scale=w_scale, bias=bias)
+    x2 = xq.reshape(-1, K).contiguous()
+    M = x2.size(0)
+    xs = _mx_scale_rows(x_scale, K)
+    ws = _mx_scale_rows(w_scale, K)
+    wq = wq.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    with torch.cuda.device(xq.device):
+        _lib.call("tao_mxfp4w_scaled_mm_bf16", _ptr(x2), _ptr(xs), _ptr(wq), _ptr(ws),
+                  _ptr(bias), _ptr(y), M, N, K, _stream(xq))
+    return y.reshape(_linear_out_shape(xq, N))
+
+
+@torch.library.register_fake("torchao::mxfp4w_dyn_linear")
+def _(x, wq, w_scale, bias=None):
+    N, K = _check_mxfp4_weight(wq, w_scale)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N), dtype=torch.bfloat16)
+
+
+def _mxfp4w_dyn_linear_cuda(x, wq, w_scale, bias=None):
+    """The whole linear from a bf16 activation. One token: the e4m3fn block quantisation + GEMV in
+    one launch. More: mx_quantize_rows into buffers of the caching allocator, then
+    mxfp4w_scaled_mm; bit-identical to calling the two ops."""
+    N, K = _check_mxfp4_weight(wq, w_scale)
+    torch._check(x.dtype is torch.bfloat16, lambda: "mxfp4w_dyn_linear (HIP) needs bf16 x")
+    torch._check(x.dim() >= 1 and x.size(-1) == K,
+                 lambda: f"x last dim {x.size(-1) if x.dim() else 0} != K {K}")
+    _same_device(x, wq=wq, w_scale=w_scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    ws = _mx_scale_rows(w_scale, K)
+    wq = wq.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if M == 1 and K <= 65536:
+            _lib.call("tao_mxfp4w_dyn_linear_bf16", _ptr(x2), _ptr(wq), _ptr(ws), _ptr(bias),
+                      _ptr(y), 1, N, K, _stream(x))
+        elif M > 0:
+            q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+            s = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
+            _lib.call("tao_mx_quantize_rows_bf16", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+            _lib.call("tao_mxfp4w_scaled_mm_bf16", _ptr(q), _ptr(s), _ptr(wq), _ptr(ws),
+                      _ptr(bias), _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
 # ---- register device impls ------------------------------------------------------------------
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
@@ -923,6 +1045,7 @@ _native_served: frozenset = frozenset()
 _native_served_float8: frozenset = frozenset()
 _native_served_float8_dyn: frozenset = frozenset()
 _native_served_mx: frozenset = frozenset()
+_native_served_mxfp4: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -942,6 +1065,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_mx
         _served.restype = ctypes.c_char_p
         _native_served_mx = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_mxfp4
+        _served.restype = ctypes.c_char_p
+        _native_served_mxfp4 = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -965,6 +1091,11 @@ def native_dispatch_float8_dyn() -> frozenset:
 def native_dispatch_mx() -> frozenset:
     """The MXFP8 ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_mx
+
+
+def native_dispatch_mxfp4() -> frozenset:
+    """The MXFP4-weight ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_mxfp4
 
 
 for _name, _fn in [
@@ -1005,6 +1136,13 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_mx:
         lib_mx.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("mxfp4_quantize_rows", _mxfp4_quantize_rows_cuda),
+    ("mxfp4w_scaled_mm", _mxfp4w_scaled_mm_cuda),
+    ("mxfp4w_dyn_linear", _mxfp4w_dyn_linear_cuda),
+]:
+    if _name not in _native_served_mxfp4:
+        lib_mxfp4.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")

@@ -5,7 +5,9 @@ from enum import Enum
 import torch
 
 SERVED = ("MXFP8 inference is served: MXFPInferenceConfig with activation_dtype = weight_dtype = "
-          "torch.float8_e4m3fn, block_size = 32, ScaleCalculationMode.FLOOR, bf16 modules")
+          "torch.float8_e4m3fn, block_size = 32, ScaleCalculationMode.FLOOR, bf16 modules. "
+          "MXFP4 weights are served under float8 activations: activation_dtype = "
+          "torch.float8_e4m3fn with weight_dtype = torch.float4_e2m1fn_x2")
 
 
 class MXGemmKernelChoice(Enum):
@@ -27,9 +29,10 @@ class ScaleCalculationMode(Enum):
 
 
 def _check_served(elem_dtype, block_size, scaling_mode=ScaleCalculationMode.FLOOR,
-                  pack_fp6=False):
-    """NotImplementedError, naming what is served, for every MX recipe that is not."""
-    if elem_dtype != torch.float8_e4m3fn:
+                  pack_fp6=False, weight=False):
+    """NotImplementedError, naming what is served, for every MX recipe that is not. e2m1 is an
+    element dtype of a weight (``weight=True``) only."""
+    if elem_dtype != torch.float8_e4m3fn and not (weight and elem_dtype == torch.float4_e2m1fn_x2):
         raise NotImplementedError(f"MX element dtype {elem_dtype} is not built. {SERVED}")
     if block_size != 32:
         raise NotImplementedError(f"MX block_size {block_size} is not built. {SERVED}")
@@ -37,6 +40,15 @@ def _check_served(elem_dtype, block_size, scaling_mode=ScaleCalculationMode.FLOO
         raise NotImplementedError(f"MX {scaling_mode} is not built. {SERVED}")
     if pack_fp6:
         raise NotImplementedError(f"fp6 packing is not built. {SERVED}")
+
+
+def _check_pair(activation_dtype, weight_dtype, block_size):
+    """The two served (activation, weight) pairs: e4m3fn x e4m3fn and e4m3fn x e2m1."""
+    _check_served(weight_dtype, block_size, weight=True)
+    if activation_dtype != torch.float8_e4m3fn:
+        raise NotImplementedError(
+            f"MX activation_dtype {activation_dtype} with weight_dtype {weight_dtype} is not "
+            f"built. {SERVED}")
 
 
 class MXLinearConfig:

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from torchao.core.config import AOBaseConfig
-from torchao.prototype.mx_formats.config import SERVED, MXGemmKernelChoice, _check_served
+from torchao.prototype.mx_formats.config import SERVED, MXGemmKernelChoice, _check_pair
 from torchao.prototype.mx_formats.mx_tensor import MXTensor, QuantizeTensorToMXKwargs
 from torchao.quantization.quant_api import _swap_weight
 from torchao.quantization.transform_module import register_quantize_module_handler
@@ -19,8 +19,10 @@ from torchao.quantization.transform_module import register_quantize_module_handl
 
 @dataclass
 class MXFPInferenceConfig(AOBaseConfig):
-    """MXFP8 dynamic-activation inference: weight and activation float8_e4m3fn, 32-element blocks
-    with E8M0 scales. ``gemm_kernel_choice`` is kept and round-trips for API and checkpoint
+    """MX dynamic-activation inference, 32-element blocks with E8M0 scales: float8_e4m3fn
+    activations with float8_e4m3fn (MXFP8) or float4_e2m1fn_x2 (MXFP4) weights. The reference asserts
+    equal dtypes; the mixed pair is this project's fp4 recipe (the block-scaled MFMA of gfx950 mixes
+    operand formats), and fp4 activations are not built. ``gemm_kernel_choice`` is kept and round-trips for API and checkpoint
     compatibility; it does not pick a kernel (every value runs the HIP path). Every other dtype
     and block size of the reference raises ``NotImplementedError``."""
 
@@ -30,11 +32,7 @@ class MXFPInferenceConfig(AOBaseConfig):
     gemm_kernel_choice: MXGemmKernelChoice = MXGemmKernelChoice.CUBLAS
 
     def __post_init__(self):
-        if self.activation_dtype != self.weight_dtype:
-            raise NotImplementedError(
-                f"MXFPInferenceConfig: activation_dtype {self.activation_dtype} differs from "
-                f"weight_dtype {self.weight_dtype}. {SERVED}")
-        _check_served(self.weight_dtype, self.block_size)
+        _check_pair(self.activation_dtype, self.weight_dtype, self.block_size)
         if not isinstance(self.gemm_kernel_choice, MXGemmKernelChoice):
             raise TypeError(f"gemm_kernel_choice must be an MXGemmKernelChoice, got "
                             f"{self.gemm_kernel_choice!r}")
@@ -56,8 +54,7 @@ def _mx_extra_repr(self):
 @register_quantize_module_handler(MXFPInferenceConfig)
 def _mx_inference_linear_transform(module: torch.nn.Module, config: MXFPInferenceConfig):
     # a config's fields can be reassigned after construction: refuse before touching the weight
-    for dtype in (config.weight_dtype, config.activation_dtype):
-        _check_served(dtype, config.block_size)
+    _check_pair(config.activation_dtype, config.weight_dtype, config.block_size)
     assert module.weight.dtype == torch.bfloat16, (
         f"Only supporting bf16 out dtype for now, got {module.weight.dtype}")
     recipe = dict(block_size=config.block_size, gemm_kernel_choice=config.gemm_kernel_choice)
