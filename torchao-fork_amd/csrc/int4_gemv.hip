@@ -47,6 +47,12 @@ __device__ __forceinline__ uint32_t mul_pair_bf16(uint32_t xv, uint32_t wv) {
   return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
 }
 
+// a * b rounded to fp32 on its own: never contracted into a neighbouring add
+__device__ __forceinline__ float mul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // WPE: minimum waves per SIMD the register allocation must allow (8 -> <= 64 VGPRs, so four
 // 512-thread workgroups fit on a CU and mid-size grids run in a single resident round).
 // NPT > 0 enables the RMSNorm prologue with NPT 16-B pieces of x per thread (PRO).
@@ -56,21 +62,34 @@ __device__ __forceinline__ uint32_t mul_pair_bf16(uint32_t xv, uint32_t wv) {
 // calls it).
 // COH (tao_int4wo_qkv_attn_bf16): the RoPE epilogue's q and cache stores are agent-scope (sc1)
 // stores, read by the same launch's attention workgroups after their ticket wait.
+// WK, GG > 0 (int4wo_gemv_static_kernel): the launch shape as compile-time constants instead of
+// the arguments Wk and G. The wave's (wk, rg) are then a mask and a shift instead of a 32-bit
+// division, the row strides and clamps fold on the scalar unit, a wave that owns one slice
+// (!PAIR, S == WK) runs no loop, and wg_combine's loop over the K-split partials unrolls.
 template <int MT, int RPW, bool PAIR, int NPT = 0, int EPI = kEpiNone, int MRG = 0,
-          bool COH = false>
+          bool COH = false, int WK = 0, int GG = 0>
 __device__ __forceinline__ void gemv_body(
     const uint16_t* __restrict__ x, const uint4* __restrict__ wq, const uint32_t* __restrict__ sz,
     const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M, int N, int K, int gshift,
-    int Wk, int G, int S, const GemvFuse& fu, int row_base) {
+    int Wk_arg, int G_arg, int S, const GemvFuse& fu, int row_base) {
   constexpr bool PRO = NPT > 0;
+  constexpr bool STATIC = WK > 0;
+  static_assert((WK > 0) == (GG > 0), "static shapes fix Wk and G together");
+  static_assert(!STATIC || (MT == 1 && !PRO && EPI == kEpiNone && (WK & (WK - 1)) == 0),
+                "static shapes: the plain M == 1 GEMV, Wk a power of two");
+  const int Wk = STATIC ? WK : Wk_arg;
+  const int G = STATIC ? GG : G_arg;
+  // PAIR is launched only for S > Wk: every wave owns a first slice, so the slice loop needs no
+  // entry test, and the pointer arguments are not loaded behind one
+  if constexpr (STATIC && PAIR) __builtin_assume(S > WK);
   static_assert(MRG == 0 || (PRO && EPI == kEpiNone && MT == 1), "merge prologue: M == 1, NPT");
   static_assert(!(PRO || EPI) || (MT == 1 && RPW % 2 == 0), "fusions are M == 1, row pairs");
   constexpr int V = RPW * MT;
   extern __shared__ float red[];  // [G][Wk][V] (PRO: + [8] partial sums, + normalised x [K])
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
-  const int wk = wave % Wk;
-  const int rg = wave / Wk;
+  const int wk = STATIC ? (int)((unsigned)wave % (unsigned)Wk) : wave % Wk;
+  const int rg = STATIC ? (int)((unsigned)wave / (unsigned)Wk) : wave / Wk;
   const int row0 = row_base + rg * RPW;
   const int nchunk = K >> 5;               // 32-k chunks per row
   const int ngroups = K >> (5 + gshift);   // quantisation groups per row
@@ -242,7 +261,7 @@ __device__ __forceinline__ void gemv_body(
     // x is streamed one row of M at a time: 16 live VGPRs whatever M is.
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-      const int mm = m < M ? m : M - 1;
+      const int mm = STATIC ? 0 : (m < M ? m : M - 1);  // the entries guarantee M >= 1
       const uint4* xp = reinterpret_cast<const uint4*>(x + (size_t)mm * K + (size_t)cc * 32);
       uint32_t xd[4][4];
 #pragma unroll
@@ -258,7 +277,11 @@ __device__ __forceinline__ void gemv_body(
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) sx = dot2_bf16(xd[j][i], 0x3F803F80u, sx);
-      const float sx136 = 136.f * sx;
+      // Static shapes (RPW >= 2): 136 sx rounded on its own, as the generic kernel of >= 2 rows
+      // per wave compiles it (the product is shared by the rows). Left to -ffp-contract=fast the
+      // compiler fuses it into each row's d - 136 sx where a wave's only slice is straight-line
+      // code, and the outputs' low bits change.
+      const float sx136 = STATIC ? mul_unfused(136.f, sx) : 136.f * sx;
 #pragma unroll
       for (int r = 0; r < RPW; ++r) {
         const uint32_t wd[4] = {wv[r].x, wv[r].y, wv[r].z, wv[r].w};
@@ -350,6 +373,8 @@ __device__ __forceinline__ void gemv_body(
       v[0] *= rsqrtf(t / (float)K + fu.eps);
     }
   }
+  // (static shapes: Wk is a constant here, so the join's loop over the K-split partials unrolls
+  // and Wk == 1 has neither LDS traffic nor a barrier)
   const WgTotal<float> t = wg_combine<V>(v[0], red, lane, wk, rg, Wk);
   if constexpr (EPI == kEpiNone) {
     if (t.writer) {
@@ -374,6 +399,25 @@ __global__ __launch_bounds__(512, WPE) void int4wo_gemv_kernel(
     int Wk, int G, int S, GemvFuse fu) {
   gemv_body<MT, RPW, PAIR, NPT, EPI, MRG>(x, wq, sz, bias, y, M, N, K, gshift, Wk, G, S, fu,
                                           (int)blockIdx.x * G * RPW);
+}
+
+// The plain M == 1 GEMV on a compile-time launch shape (launch_gemv_static picks it when
+// m1_shape's choice is one of the instantiated tuples): no GemvFuse in the kernarg segment, M == 1
+// and the workgroup size known, S an argument only where a wave walks several slices (PAIR; the
+// guarded second slice keeps its loads behind the first slice's arithmetic).
+// Same loads, arithmetic and summation order as int4wo_gemv_kernel on that shape: bit-identical
+// outputs.
+template <int RPW, int WPE, bool PAIR, int WK, int GG>
+__global__ __launch_bounds__(64 * WK * GG, WPE) void int4wo_gemv_static_kernel(
+    const uint16_t* __restrict__ x, const uint4* __restrict__ wq, const uint32_t* __restrict__ sz,
+    const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int N, int K, int gshift,
+    int S) {
+  // every argument in one scalar round trip at entry: left to itself the compiler fetches the
+  // bias and y pointers in the tail, a second kernarg wait behind the join
+  asm volatile("" ::"s"(bias), "s"(y));
+  gemv_body<1, RPW, PAIR, 0, kEpiNone, 0, false, WK, GG>(
+      x, wq, sz, bias, y, 1, N, K, gshift, WK, GG, PAIR ? S : WK, GemvFuse{},
+      (int)blockIdx.x * (GG * RPW));
 }
 
 // ---- wqkv + RoPE / KV write + decode attention in one launch (tao_int4wo_qkv_attn_bf16) -------
@@ -661,6 +705,10 @@ int launch_gemv(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
 // M == 1 launch shape. Measured on MI355X (experiments/sweep_gemv.py,
 // profiles/r1_sweep_gemv*.jsonl): the best shapes per (N, K) class, dispatch-event timed over
 // weights rotated past the MALL.
+// The tuples returned for the Llama-3-8B / 7B-class / Llama-3-70B linears have static-shape
+// instantiations (try_gemv_static below; a new tuple here runs the generic kernel until it is
+// added there). The sweeps behind these choices were timed with the generic kernel; they have not
+// been repeated with the static ones.
 struct M1Shape {
   int rpw, occ;
   GemvShape sh;
@@ -719,6 +767,52 @@ M1Shape m1_shape(int N, int S) {
   if (twk > 0) c.sh.wk = twk;
   if (tg > 0) c.sh.g = tg;
   return c;
+}
+
+// ---- static-shape launch of the plain M == 1 linear ---------------------------------------------
+// int4wo_gemv_static_kernel is instantiated for the (rows per wave, occupancy, PAIR, Wk, G) tuples
+// m1_shape returns for the Llama-3-8B linears (wo, wqkv, w1||w3, w2, head: the bench step), the
+// 7B-class mid-N FFN shapes and the Llama-3-70B linears. Every other shape, M > 1, the fused
+// decode instantiations (NPT / EPI / MRG), the grouped kernel and any tao_tune_int4_gemv /
+// tao_tune_int4_lds override take int4wo_gemv_kernel with the shape as arguments. Returns -1 when
+// no instantiation matches.
+template <int RPW, int WPE, bool PAIR, int WK, int GG>
+int launch_gemv_static(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
+                       const uint16_t* bias, uint16_t* y, int N, int K, int gshift, int S,
+                       hipStream_t stream) {
+  constexpr int rows_per_wg = GG * RPW;
+  launch((int4wo_gemv_static_kernel<RPW, WPE, PAIR, WK, GG>),
+         dim3((unsigned)((N + rows_per_wg - 1) / rows_per_wg)), dim3(64 * WK * GG),
+         (size_t)GG * WK * RPW * sizeof(float), stream, x, reinterpret_cast<const uint4*>(packed),
+         reinterpret_cast<const uint32_t*>(sz), bias, y, N, K, gshift, S);
+  return check_launch("int4wo_gemv_static_kernel");
+}
+
+int try_gemv_static(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
+                    const uint16_t* bias, uint16_t* y, int N, int K, int gshift,
+                    const M1Shape& c, hipStream_t stream) {
+  const auto& tu = tao::tuning();
+  if (tu.rpw > 0 || tu.occ > 0 || tu.wk > 0 || tu.g > 0 || tu.gemv_lds > 0) return -1;
+  const int S = (K / 32 + 63) / 64;
+  const int wk = c.sh.wk < S ? c.sh.wk : S;
+  const bool pair = S > wk;
+  // the occupancy int4wo_gemv instantiates the generic kernel with
+  const int wpe = c.rpw <= 2 ? 8 : c.rpw == 8 ? 4 : c.occ == 4 ? 4 : 8;
+#define TAO_STATIC(R, W, P, WK_, G_)                                                    \
+  if (c.rpw == R && wpe == W && pair == P && wk == WK_ && c.sh.g == G_)                 \
+    return launch_gemv_static<R, W, P, WK_, G_>(x, packed, sz, bias, y, N, K, gshift, S, stream);
+  TAO_STATIC(2, 8, false, 2, 1)  // 4096 x 4096 (wo)
+  TAO_STATIC(2, 8, true, 1, 4)   // 6144 x 4096 (wqkv)
+  TAO_STATIC(4, 4, true, 1, 4)   // 28672 x 4096 (w1 || w3)
+  TAO_STATIC(4, 4, true, 2, 1)   // 4096 x 14336 (w2)
+  TAO_STATIC(4, 8, false, 2, 2)  // 128256 x 4096 (head)
+  TAO_STATIC(2, 8, false, 2, 2)  // 8192 < N < 16384 at K = 4096 (11008, 14336)
+  TAO_STATIC(2, 8, false, 2, 4)  // 4096 < N < 6144 at K = 4096
+  TAO_STATIC(4, 4, true, 1, 1)   // 70B: 8192 x 8192, 8192 x 28672, 28672 x 8192
+  TAO_STATIC(4, 4, true, 2, 2)   // 70B: 10240 x 8192 (wqkv)
+  TAO_STATIC(8, 4, true, 2, 1)   // 70B: 57344 x 8192 (w1 || w3), 128256 x 8192 (head)
+#undef TAO_STATIC
+  return -1;
 }
 
 template <int NPT, int EPI>
@@ -835,6 +929,10 @@ int int4wo_gemv(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
   if (M <= 1) {
     const M1Shape c = m1_shape(iN, S);
     sh = c.sh;
+    if (iM == 1) {
+      const int rc = try_gemv_static(x, packed, sz, bias, y, iN, iK, gs, c, stream);
+      if (rc >= 0) return rc;
+    }
     if (c.rpw == 1) return launch_gemv<1, 1, 8>(x, packed, sz, bias, y, iM, iN, iK, gs, sh, stream);
     if (c.rpw == 2) return launch_gemv<1, 2, 8>(x, packed, sz, bias, y, iM, iN, iK, gs, sh, stream);
     if (c.rpw == 8) return launch_gemv<1, 8, 4>(x, packed, sz, bias, y, iM, iN, iK, gs, sh, stream);
