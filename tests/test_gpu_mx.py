@@ -1,4 +1,4 @@
-"""GPU tests of the MXFP8 inference linear (csrc/mx_fp8.hip, the MxFp8 policy of csrc/gemm_mfma.hip,
+"""GPU tests of the MXFP8 inference linear (csrc/mx_fp8.hip, the MxFp8 policy of csrc/gemm_mfma_policy.h,
 torchao.prototype.mx_formats) against the reference fixtures (tests/golden/mxfp8_*.npz,
 mx_quant_edges.npz, written by experiments/gen_golden_mx.py): the quantizer byte for byte, the
 scale mapping of the block-scaled MFMA and of the GEMV on exact inputs, the ops against the float64

@@ -1,5 +1,5 @@
 """GPU tests of the MXFP4-weight inference linear (csrc/mx_fp4.hip, the MxFp8Fp4 policy of
-csrc/gemm_mfma.hip, torchao.prototype.mx_formats with e4m3fn activations and float4_e2m1fn_x2
+csrc/gemm_mfma_policy.h, torchao.prototype.mx_formats with e4m3fn activations and float4_e2m1fn_x2
 weights) against the reference fixtures (tests/golden/mxfp4w_*.npz, mxfp4_quant_edges.npz, written by
 experiments/gen_golden_mxfp4.py): the quantizer byte for byte, the scale map and the k map of the
 mixed-format MFMA and of the GEMV on exact inputs, the ops against the float64 formula on the

@@ -35,6 +35,7 @@
 // cancel.
 #include "fp8_dyn_host.h"
 #include "fp8_quant_row.h"
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 // The epilogue is specified as separate fp32 roundings (mul, mul, add): no fused multiply-add.
@@ -43,11 +44,6 @@
 namespace tao {
 
 TAO_DECODE_ERROR_WORD(fp8dyn_decode_status)
-
-int fp8_scaled_mm_launch(const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
-                         const uint16_t* bias, uint16_t* y, int M, int N, int K,
-                         hipStream_t stream);                // gemm_mfma.hip
-bool fp8dyn_takes_gemv(int64_t M, int64_t N, int64_t K);   // gemm_mfma.hip
 
 namespace {
 

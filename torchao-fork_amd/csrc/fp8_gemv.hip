@@ -12,6 +12,7 @@
 // numbers) turns two codes into a bf16 pair, one v_dot2c_f32_bf16 multiplies it with the x pair
 // as loaded: 1.0 VALU per weight and no x conversion (v_cvt_pk_f32_fp8 + v_fma_f32 would be 1.5
 // plus the bf16 -> f32 shifts of x). No bias trick is needed: the codes decode signed.
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 namespace tao {

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "tao_common.h"
+#include "tao_gemm.h"
 
 // 1: with 3+ stages, each step's DMA pieces are issued between its MFMA groups (after group kb,
 // pieces r with r KB / R == kb) instead of all after the step's barrier (gemm_sf32.hip's IL)
@@ -89,7 +90,7 @@ __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
 // r & 15 puts the 16 lanes of every ds_read_b128 lane group on 16 distinct bank granules.
 __device__ __forceinline__ int pos256(int row, int g) { return g ^ (row & 15); }
 // 256-B rows read in the int4 order (granule 4 kq + kb): flip bit 2 of r & 15 on rows whose bits
-// 2 and 3 differ (gemm_mfma.hip's Int4WO x image mask; checked by tests/test_host_cpu.py).
+// 2 and 3 differ (gemm_mfma_policy.h's Int4WO x image mask; checked by tests/test_host_cpu.py).
 __device__ __forceinline__ int pos256q(int row, int g) {
   const int m = row & 15;
   return g ^ (m ^ ((m ^ (m >> 1)) & 4));
@@ -181,7 +182,7 @@ struct SfI4 {
 // int4 B fragment: 8 nibbles (row-stream dword: q0,q4,q1,q5 in the bytes of w & 0x0F0F0F0F,
 // q2,q6,q3,q7 in those of (w >> 4) & 0x0F0F0F0F) -> bf16(fma(q, s, z - 8 s)) in k order. A byte
 // b < 16 read as OCP e4m3 is exactly b / 512: one v_cvt_scalef32_pk_f32_fp8 (scale 512) gives
-// two exact fp32 integers (gemm_mfma.hip Int4WO::frag).
+// two exact fp32 integers (gemm_mfma_policy.h Int4WO::frag).
 __device__ __forceinline__ bf16x8_t deq8(uint32_t w, float sc, float zc) {
   const uint32_t lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;
   const f32x2_t q04 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(lo, 512.f, false);
@@ -1010,7 +1011,7 @@ int sf_int4_partial_slices(int M, int N, int K) {
 
 int sf_int4(const uint16_t* x, const uint32_t* packed, const uint16_t* sz, int lg,
             const uint16_t* bias, uint16_t* y, int M, int N, int K, hipStream_t stream,
-            int epi = 0) {
+            int epi) {
   SfEpi ep{};
   ep.kind = epi;
   return sf_int4_epi(x, packed, sz, lg, bias, y, M, N, K, stream, ep);
@@ -1023,15 +1024,6 @@ int sf_int4(const uint16_t* x, const uint32_t* packed, const uint16_t* sz, int l
 // bf16(bf16(silu(a_i)) * b_i), (a_i, b_i) = bf16 outputs of rows (2i, 2i+1). Served by the
 // single-fetch GEMM where it is routed (tao_tune_gemm_sf 2: wherever it applies);
 // TAO_ERR_UNSUPPORTED elsewhere (the caller runs the linear and tao_silu_mul_bf16).
-namespace tao {
-int int4_check_linear_args(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
-                           uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t group_size);
-}  // namespace tao
-
-namespace tao {
-bool int4_linear_takes_gemv(int64_t M, int64_t N, int64_t K);
-}  // namespace tao
-
 static int lg_of(int64_t g) { return g == 32 ? 5 : g == 64 ? 6 : g == 128 ? 7 : 8; }
 
 extern "C" int tao_int4wo_linear_swiglu_bf16(const uint16_t* x, const uint32_t* packed,

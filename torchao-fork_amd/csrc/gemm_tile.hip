@@ -22,7 +22,7 @@
 //     waiting): no workgroup waits on one that might not be resident, the grid always drains, and
 //     the slab sum runs in slice order (run-to-run deterministic).
 //
-// Weights/format policies (same numerics as gemm_mfma.hip's Int4WO / Int8WO / Int8Dyn):
+// Weights/format policies (same numerics as gemm_mfma_policy.h's Int4WO / Int8WO / Int8Dyn):
 //   TInt4   : bf16 x, int4 row-stream W + (scale, zero) per group, v_mfma_f32_16x16x32_bf16,
 //             B = bf16(fma(q, s, z - 8 s)), y = bf16(acc)
 //   TInt8WO : bf16 x, int8 W (exact in bf16), y = bf16(bf16(acc) * scale)
@@ -31,6 +31,7 @@
 // Replaces aten._weight_int4pack_mm (tensor_core_tiled_layout.py:104), mm(x, w.to(bf16)) * s
 // (plain_layout.py:256-266) and int_scaled_matmul + scales (plain_layout.py:294-315).
 #include "tao_common.h"
+#include "tao_gemm.h"
 
 // The timing-only variant builds (TAO_TILE_DEBUG / TAO_TILE_STAMPS) were removed in round 6;
 // their code is in git history (commit 1bac331), their measurements in profiles/r3_*.

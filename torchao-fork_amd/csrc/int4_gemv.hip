@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "tao_attn.h"
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 // The timing-only variant builds of rounds 1-5 (no x loads, no arithmetic, no (scale, zero)

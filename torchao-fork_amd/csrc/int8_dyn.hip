@@ -13,6 +13,7 @@
 #include <atomic>
 
 #include "int8_quant_row.h"
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 namespace tao {
@@ -384,11 +385,6 @@ int launch_quant_per_token(const uint16_t* x, int8_t* q, uint16_t* scale, int M,
 }
 
 }  // namespace
-
-int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq,
-                          const uint16_t* ws, const uint16_t* bias, uint16_t* y, int M, int N,
-                          int K, hipStream_t stream);  // gemm_mfma.hip
-
 }  // namespace tao
 
 using namespace tao;

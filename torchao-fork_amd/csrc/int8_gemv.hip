@@ -9,6 +9,7 @@
 // 128 * sum(x).
 #include <atomic>
 
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 namespace tao {

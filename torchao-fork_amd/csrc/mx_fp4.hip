@@ -50,15 +50,10 @@
 #include "fp8_dyn_host.h"
 #include "fp8_quant_row.h"
 #include "mx_block.h"
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 namespace tao {
-
-int mxfp4w_scaled_mm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* wq,
-                            const uint8_t* ws, const uint16_t* bias, uint16_t* y, int M, int N,
-                            int K, hipStream_t stream);   // gemm_mfma.hip
-bool mx_takes_gemv(int64_t M, int64_t N, int64_t K);     // gemm_mfma.hip
-
 namespace {
 
 // ---- quantizer -------------------------------------------------------------------------------------
