@@ -256,6 +256,49 @@ int tao_mxfp4w_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const uint8
                                const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                                void* stream);
 
+/* ---- Blockwise float8 (torchao.prototype.blockwise_fp8_inference): e4m3fn codes, one fp32 scale
+ * per 1 x 128 block of the activation and per 128 x 128 block of the weight (csrc/block_fp8.hip).
+ * K % 128 == 0 throughout; NB = ceil(N / 128). -------------------------------------------------- */
+
+/* Activation quantizer of x [M][K] bf16, per block of 128 consecutive k of one row:
+ *   amax = max |x| (a NaN element ignored, 0 if there is no number), s = amax / 448 (correctly
+ *   rounded fp32, subnormals kept), q = e4m3fn_rne(float(x) / s), and q = e4m3fn_rne(float(x))
+ *   where amax == 0 (an all-zero block: zero codes, scale 0; the reference stores NaN codes).
+ * q uint8 [M][K] codes, scale fp32 [M][K/128]. Replaces fp8_blockwise_act_quant
+ * (torchao/prototype/blockwise_fp8_inference/blockwise_quantization.py), byte for byte but for the
+ * all-zero block. M == 0 is a no-op; x 16-B, q 8-B aligned, M * K below 2^32. */
+int tao_blockfp8_quantize_act_bf16(const uint16_t* x, uint8_t* q, float* scale, int64_t M,
+                                   int64_t K, void* stream);
+
+/* Weight quantizer of w [N][K] bf16: the same arithmetic per block of up to 128 rows x 128 k (the
+ * last row block takes its amax over the rows that exist). q uint8 [N][K], scale fp32 [NB][K/128].
+ * Replaces fp8_blockwise_weight_quant, which needs N % 128 == 0. */
+int tao_blockfp8_quantize_weight_bf16(const uint16_t* w, uint8_t* q, float* scale, int64_t N,
+                                      int64_t K, void* stream);
+
+/* out[n][k] = float(q[n][k]) * scale[n / 128][k / 128] in fp32, stored as fp32 (out_bf16 == 0) or
+ * rounded once to bf16 (out_bf16 == 1). Replaces fp8_blockwise_weight_dequant. q, out 16-B
+ * aligned. */
+int tao_blockfp8_dequant_weight(const uint8_t* q, const float* scale, void* out, int64_t N,
+                                int64_t K, int out_bf16, void* stream);
+
+/* y[m][n] = bf16( sum_b P[m][n][b] * (xs[m][b] * ws[n / 128][b]) + fp32(bias[n]) ), P the fp32 dot
+ * product of the 128 code pairs of block b; fp32 throughout (each term one fma on the rounded
+ * factor), one rounding to bf16, the bias a separate add. xq uint8 [M][K], wq uint8 [N][K] e4m3fn
+ * codes; xs fp32 [M][K/128], ws fp32 [NB][K/128]; bias bf16 [N] or NULL. Replaces
+ * blockwise_fp8_gemm. Any N, M >= 0 (M == 0 is a no-op); xq, wq 16-B aligned; each operand below
+ * 4 GiB. No scale outside the two arrays is read. */
+int tao_blockfp8_scaled_mm_bf16(const uint8_t* xq, const float* xs, const uint8_t* wq,
+                                const float* ws, const uint16_t* bias, uint16_t* y, int64_t M,
+                                int64_t N, int64_t K, void* stream);
+
+/* One token (M <= 1): tao_blockfp8_quantize_act_bf16 of the bf16 token x [K] and the product above
+ * in one launch, bit-identical to the two calls. Replaces BlockwiseQuantLinear.forward at one
+ * token. More tokens are the two calls. K <= 65536. */
+int tao_blockfp8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const float* ws,
+                                 const uint16_t* bias, uint16_t* y, int64_t M, int64_t N,
+                                 int64_t K, void* stream);
+
 /* ---- int8 dynamic activation x int8 weight -------------------------------------------------- */
 
 /* Per-token symmetric reduced-range int8 quantization of x [M][K] bf16:

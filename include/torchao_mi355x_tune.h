@@ -206,6 +206,10 @@ int tao_tune_fp8dyn_mfma(int on);
  * tao_tune_linear_crossover moves, the MFMA kernel above it), 1 = the MFMA kernel at every M, so
  * that tests and A/B runs reach it below the crossover too. Calling thread only. */
 int tao_tune_mx_mfma(int on);
+/* Route of tao_blockfp8_scaled_mm_bf16: 0 = built-in (GEMV up to the crossover that
+ * tao_tune_linear_crossover moves, the MFMA kernel above it), 1 = the MFMA kernel at every M, so
+ * that tests and A/B runs reach it below the crossover too. Calling thread only. */
+int tao_tune_blockfp8_mfma(int on);
 /* Per-token int8 quantisation kernel (A/B only): 0 = one wave per token, the token held in
  * registers (default, K <= 8192); 1 = one 256-thread workgroup per token. Bit-identical. */
 int tao_tune_int8_quant(int block);

@@ -1,6 +1,6 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// seven weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
+// eight weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
 //   Int4WO  : bf16 x, int4 group-quant W (gfx950 row-stream layout), v_mfma_f32_16x16x32_bf16
 //   Int8WO  : bf16 x, int8 per-channel W,                            v_mfma_f32_16x16x32_bf16
 //   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
@@ -8,6 +8,8 @@
 //   Fp8Dyn  : e4m3fn x (per-token scale), e4m3fn W (per-row scale),   v_mfma_scale_f32_16x16x128_f8f6f4
 //   MxFp8   : e4m3fn x and W, one E8M0 scale byte per 32-k block,    v_mfma_scale_f32_16x16x128_f8f6f4
 //   MxFp8Fp4: e4m3fn x, e2m1 W (two codes per byte), the same scales, the same MFMA (cbsz 0, blgp 4)
+//   BlockFp8: e4m3fn x (1 x 128 fp32 scales), e4m3fn W (128 x 128 fp32 scales), the same MFMA with
+//             unit scale bytes into a zero accumulator, then a scaled fp32 accumulate
 // Replaces aten._weight_int4pack_mm (tensor_core_tiled_layout.py:104), mm(x, w.to(bf16)) * s
 // (plain_layout.py:256-266), int_scaled_matmul + scales (plain_layout.py:294-315,
 // kernel/intmm.py:108-143), F.linear(x, w.dequantize()) (floatx/float8_layout.py:391-396) and the
@@ -84,7 +86,11 @@ __device__ __forceinline__ int x_slot(int row, int slot) {
 #if TAO_GEMM_WPE > 0
 #define TAO_GEMM_WPE_ATTR __attribute__((amdgpu_waves_per_eu(TAO_GEMM_WPE)))
 #else
-#define TAO_GEMM_WPE_ATTR
+// kBlockF32 policies read every MFMA's product back for the scaled accumulate. With up to 512
+// registers per lane (256 threads) hipcc puts MFMA results into AGPRs and copies each one out with
+// a v_accvgpr_read; asked to leave room for two waves per SIMD (256 registers, which these
+// instances fit without scratch) it writes them to VGPRs. 0: no attribute (every other policy).
+#define TAO_GEMM_WPE_ATTR __attribute__((amdgpu_waves_per_eu(P::kBlockF32 ? 2 : 0)))
 #endif
 template <int BM, int D, int KG, int NW, class P>
 __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
@@ -102,11 +108,12 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
   static_assert((KG - 1) * 4 * NA * 64 <= KG * 2 * TILE, "k-group reduction must fit in LDS");
   // one LDS array (a second __shared__ object can de-pipeline the loop, cdna guide §5 item 4a):
   // [KG][2][x tile] then the per-wave weight stages (NW per wave), then (block-scaled policies)
-  // [KG][2][BM rows][8 scale bytes] of the x tiles
+  // [KG][2][BM rows][8 scale bytes] of the x tiles ([KG][2][2 blocks][BM rows] floats: kBlockF32)
   constexpr bool kBS = P::kBlockScaled;
   constexpr bool kBSA = P::kScaleAligned;  // whole 8-B words of scale bytes per row and step
   constexpr int XSL = kBSA ? 2 : kBS ? (BM + 31) / 32 : 1;  // x scale registers per thread per step
-  constexpr int XSC = kBS ? BM / 2 : 0;          // uint4 per tile of x scale bytes
+  constexpr bool kBF = P::kBlockF32;  // fp32 x scales per 128-k block: BM x 2 floats per step
+  constexpr int XSC = (kBS || kBF) ? BM / 2 : 0;  // uint4 per tile of x scale bytes / floats
   __shared__ uint4 lds[KG * 2 * TILE + KG * 4 * NW * P::kStage + (P::kStage == 0) + KG * 2 * XSC];
 
   const int tid = threadIdx.x;
@@ -167,6 +174,16 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
     }
   }
 
+  // kBlockF32: this thread's x scale, block ktid & 1 of row ktid >> 1 (rows past BM: row BM - 1,
+  // not stored)
+  const int nblk128 = K >> 7;
+  const float* xfrow = nullptr;
+  if constexpr (kBF) {
+    const int r = ktid >> 1;
+    const int gm = m_blk + (r < BM ? r : BM - 1);
+    xfrow = pol.xscale + (size_t)(gm < M ? gm : M - 1) * nblk128;
+  }
+
   Acc acc[NA];  // [t][c]
 #pragma unroll
   for (int t = 0; t < NA; ++t) acc[t] = Acc{0, 0, 0, 0};
@@ -192,6 +209,9 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
       const int bc = b < nblk ? b : nblk - 1;  // never past the row's K / 32 bytes
 #pragma unroll
       for (int i = 0; i < XSL; ++i) sdst[i] = xsrow[i][bc];
+    } else if constexpr (kBF) {
+      const int b = st * 2 + (ktid & 1);
+      sdst[0] = __float_as_uint(xfrow[b < nblk128 ? b : nblk128 - 1]);  // never past K / 128
     }
 #pragma unroll
     for (int c = 0; c < NW; ++c) wdst[c] = pol.load(wl[c], st);
@@ -231,6 +251,12 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
         if (row < BM)
           dst[row * 8 + (xsblk & 3) * 2 + (xsblk >> 2)] = (uint8_t)(in ? src[i] : 127u);
       }
+    } else if constexpr (kBF) {
+      // [block][row]; a block past K / 128 (or an inactive step) gets 0 against its zeroed codes
+      const int st = abs_step(j);
+      const bool in = st < s1 && st * 2 + (ktid & 1) < nblk128;
+      uint32_t* dst = reinterpret_cast<uint32_t*>(xscl + (j & 1) * (BM * 8));
+      if ((ktid >> 1) < BM) dst[(ktid & 1) * BM + (ktid >> 1)] = in ? src[0] : 0u;
     }
   };
   // local step j; u = j % D at compile time
@@ -271,6 +297,15 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
               for (int c = 0; c < NW; ++c)
                 acc[t * NW + c] =
                     P::mfma2s(a0, a1, bfrag[c], acc[t * NW + c], s, asc[t], pw[c].sc);
+            } else if constexpr (kBF) {
+              // block s of the step: the scales of this lane's C rows 4 kq .. 4 kq + 3 of tile t
+              const float4 xf = reinterpret_cast<const float4*>(
+                  xscl + (j & 1) * (BM * 8))[(s * BM + t * 16) / 4 + kq];
+#pragma unroll
+              for (int c = 0; c < NW; ++c)
+                acc[t * NW + c] =
+                    P::scaled_acc(P::mfma2(a0, a1, bfrag[c], Acc{0, 0, 0, 0}), xf, pw[c], s,
+                                  acc[t * NW + c]);
             } else {
 #pragma unroll
               for (int c = 0; c < NW; ++c)
@@ -689,6 +724,22 @@ int mxfp4w_scaled_mm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t*
   return launch_mx<MxFp8Fp4<false>>(xq, xs, wq, ws, bias, y, M, N, K, stream);
 }
 
+// the blockwise float8 route (block_fp8.hip): the same rule again, its force switch
+// tao_tune_blockfp8_mfma
+bool blockfp8_takes_gemv(int64_t M, int64_t N, int64_t K) {
+  return fp8dyn_route_gemv(M, N, K, tuning().blockfp8_mfma, tuning().max_gemv_m);
+}
+
+int blockfp8_scaled_mm_launch(const uint8_t* xq, const float* xs, const uint8_t* wq,
+                              const float* ws, const uint16_t* bias, uint16_t* y, int M, int N,
+                              int K, hipStream_t stream) {
+  BlockFp8 pol;
+  pol.w = reinterpret_cast<const uint4*>(wq);
+  pol.wscale = ws;
+  pol.xscale = xs;
+  return launch_gemm(xq, pol, bias, y, M, N, K, stream);
+}
+
 int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq,
                           const uint16_t* ws, const uint16_t* bias, uint16_t* y, int M, int N,
                           int K, hipStream_t stream) {
@@ -803,6 +854,12 @@ extern "C" int tao_tune_fp8dyn_mfma(int on) {
 extern "C" int tao_tune_mx_mfma(int on) {
   TAO_CHECK_ARG(on == 0 || on == 1, "tune: mx mfma must be 0 (built-in route) or 1");
   tao::tuning().mx_mfma = on;
+  return TAO_OK;
+}
+
+extern "C" int tao_tune_blockfp8_mfma(int on) {
+  TAO_CHECK_ARG(on == 0 || on == 1, "tune: blockfp8 mfma must be 0 (built-in route) or 1");
+  tao::tuning().blockfp8_mfma = on;
   return TAO_OK;
 }
 

@@ -37,6 +37,7 @@ struct PolicyDefaults {
   static constexpr int kMaxKG = 4;             // k-groups per workgroup the policy is built for
   static constexpr bool kBlockScaled = false;  // the MFMAs take per-block scale bytes
   static constexpr bool kScaleAligned = false;  // ... a row's 8 per step are one aligned 8-B word
+  static constexpr bool kBlockF32 = false;     // fp32 scales per 128-k block, applied per MFMA
   typedef f32x4_t Acc;
   // x image mask (x_slot, gemm_mfma.hip)
   static __device__ __forceinline__ int xswz(int row) { return row & 15; }
@@ -375,6 +376,102 @@ struct Fp8Dyn : ByteWeights<256> {
 #pragma clang fp contract(off)
     return (acc * xs) * ws;
   }
+};
+
+// BlockFp8: e4m3fn x with one fp32 scale per 1 x 128 block ([M][K/128]) and e4m3fn W with one per
+// 128 x 128 block ([ceil(N/128)][K/128]) (block_fp8.hip). Fp8Dyn's tile, x image, weight path, k
+// order and unit E8M0 bytes; K = 128 of the instruction is one scale block, MFMA u of a step is
+// block 2 st + u, and the k order inside an MFMA is immaterial under one scale. Each MFMA runs into
+// a zero accumulator and the kernel then does acc = fma(P, xs * ws, acc) per element (kBlockF32):
+//  * W: a wave's 16 columns start at a multiple of 16, so they lie in one 128-row scale block: the
+//    scale is wave-uniform (every lane loads the same two floats per step, riding in the weight
+//    ring); the scale row of a column past N is that of row N - 1, which is ceil(N/128) - 1.
+//  * x: the step's BM x 2 floats are loaded by the k-group's threads (thread t: row t >> 1, block
+//    t & 1), ride in the x ring and are stored beside the x image, double-buffered like it, as
+//    [block][row]; a lane reads the four factors of its four C rows with one ds_read_b128.
+// K % 256 == 128 is the only tail: the codes of the missing block are zeroed on both sides (mask_tail
+// here, the LDS store for x) and both its scales are replaced by 0 (never a clamped neighbour's,
+// which may be inf or NaN), so it adds exactly fma(0, 0, acc). A block index is clamped to
+// K / 128 - 1 before any load. No row or column factor: the epilogue is the bias add and the one
+// rounding.
+struct BlockFp8 : ByteWeights<256> {
+  static constexpr int kPathId = 7;  // no measured table entries: the heuristic shapes
+  static constexpr bool kMaskTail = true;
+  static constexpr bool kBlockF32 = true;
+  static constexpr int kABytes = 1;  // e4m3fn x
+  static constexpr int kMfma = 2;
+  static constexpr int kASlots = 2;  // 16-B x slots per MFMA
+  // 128-row tiles never won (M = 512: 31.7 vs 31.8 us on 4096^2, 61.1 vs 46.9 on 6144 x 4096,
+  // 123.1 vs 119.9 on 14336 x 4096): at one wave per SIMD the products land in AGPRs and are
+  // copied out one v_accvgpr_read each (gemm_mfma.hip, TAO_GEMM_WPE_ATTR)
+  static constexpr int kMaxBM = 64;
+  static constexpr int kPrefKG = 1;
+  static constexpr int kMaxKG = 2;
+  static constexpr int kMinSlice = 4;
+  const float* wscale;   // [ceil(N/128)][K/128] fp32
+  const float* xscale;   // [M][K/128] fp32
+  typedef ByteWeights<256> Codes;  // w: [N][K/16] e4m3fn codes
+  struct Lane {
+    Codes::Lane c;
+    const float* s;  // the wave's row of weight scales
+    int nblk;
+  };
+  struct Chunk {
+    Codes::Chunk c;
+    float s0, s1;  // scales of blocks 2 st and 2 st + 1 (clamped to the row)
+  };
+  struct Prep {
+    Codes::Prep c;  // v[s]: bytes 64 s + 16 kq .. + 16 of row n
+    float s0, s1;   // mask_tail: a block past K / 128 -> 0
+  };
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    Lane L;
+    L.c = Codes::setup(bn, lane, N, K);
+    L.nblk = K >> 7;
+    L.s = wscale + (size_t)((bn < N ? bn : N - 1) >> 7) * L.nblk;
+    return L;
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    Chunk ch;
+    ch.c = Codes::load(L.c, st);
+    const int b0 = 2 * st, b1 = b0 + 1;
+    ch.s0 = L.s[b0 < L.nblk ? b0 : L.nblk - 1];
+    ch.s1 = L.s[b1 < L.nblk ? b1 : L.nblk - 1];
+    return ch;
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    Prep p;
+    p.c = Codes::prep(ch.c, stage, lane);
+    p.s0 = ch.s0;
+    p.s1 = ch.s1;
+    return p;
+  }
+  // the codes as Fp8Dyn masks them (16-B pieces); the scale of a block at or past K / 128 -> 0
+  static __device__ __forceinline__ void mask_tail(Prep& p, int st, int kq, int K) {
+    Codes::mask_tail(p.c, st, kq, K);
+    p.s0 = st * kKStep < K ? p.s0 : 0.f;
+    p.s1 = st * kKStep + 128 < K ? p.s1 : 0.f;
+  }
+  __device__ __forceinline__ i32x8_t frag(const Prep& p, int u) const {
+    return u == 0 ? pair(p.c.v[0], p.c.v[1]) : pair(p.c.v[2], p.c.v[3]);
+  }
+  // cbsz 0 / blgp 0: both operands e4m3; scale bytes 127 = 2^0
+  static __device__ __forceinline__ Acc mfma2(const uint4& a0, const uint4& a1, const i32x8_t& b,
+                                              Acc c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(pair(a0, a1), b, c, 0, 0, 0,
+                                                            0x7F7F7F7F, 0, 0x7F7F7F7F);
+  }
+  // the scaled accumulate of MFMA u's product: xf the lane's four C rows' activation scales
+  static __device__ __forceinline__ Acc scaled_acc(const Acc& pr, const float4& xf, const Prep& p,
+                                                   int u, Acc c) {
+    const float w = u == 0 ? p.s0 : p.s1;
+    c[0] = __builtin_fmaf(pr[0], xf.x * w, c[0]);
+    c[1] = __builtin_fmaf(pr[1], xf.y * w, c[1]);
+    c[2] = __builtin_fmaf(pr[2], xf.z * w, c[2]);
+    c[3] = __builtin_fmaf(pr[3], xf.w * w, c[3]);
+    return c;
+  }
+  __device__ __forceinline__ float epi(float acc, float, float) const { return acc; }
 };
 
 // The weight side of the E8M0 scale bytes of the MX formats ([N][K/32], one per 32-k block);

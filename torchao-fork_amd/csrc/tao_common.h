@@ -65,6 +65,7 @@ struct Tuning {
   int fp8_rpw = 0, fp8_wk = 0, fp8_g = 0;        // fp8 GEMVs (tao_tune_fp8_gemv)
   int fp8dyn_mfma = 0;                           // fp8 x fp8 scaled mm: 1 = MFMA route at every M
   int mx_mfma = 0;                               // mx scaled mm: 1 = MFMA route at every M
+  int blockfp8_mfma = 0;                         // blockfp8 scaled mm: 1 = MFMA route at every M
   int attn_mode = 0;                             // decode attention (tao_tune_attn)
   int splitk_fenced = fence_free_validated() ? 0 : 1;  // split-K hand-off with agent fences
   int gemm_order = 0;                            // MFMA GEMM tile order: 0 plain, 1 XCD-grouped

@@ -3,7 +3,9 @@
 // int8_quantize_per_token, int8_scaled_mm, int8_dyn_linear, the float8 weight-only set
 // fp8_weight_only_linear, fp8_quantize_rows, fp8_dequantize, and the float8 dynamic-activation set
 // fp8_scaled_mm, fp8_dyn_linear, the MXFP8 set mx_quantize_rows, mx_scaled_mm, mx_dyn_linear, and the
-// MXFP4-weight set mxfp4_quantize_rows, mxfp4w_scaled_mm, mxfp4w_dyn_linear.
+// MXFP4-weight set mxfp4_quantize_rows, mxfp4w_scaled_mm, mxfp4w_dyn_linear, and the blockwise
+// float8 set blockfp8_quantize_act, blockfp8_quantize_weight, blockfp8_dequantize_weight,
+// blockfp8_scaled_mm, blockfp8_dyn_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -526,9 +528,157 @@ Tensor mxfp4w_dyn_linear(const Tensor& x, const Tensor& wq, const Tensor& w_scal
   return y.reshape(out_shape(x, N));
 }
 
+// ---- Blockwise float8: e4m3fn codes, fp32 scales per 1 x 128 (activation) and 128 x 128 (weight)
+// block (ops.py _blockfp8_scaled_mm_cuda & co) ---------------------------------------------------
+int64_t check_blockfp8_k(const Tensor& t, const char* name) {
+  TORCH_CHECK(t.dim() >= 1, name, " must have at least one dimension");
+  const int64_t K = t.size(-1);
+  TORCH_CHECK(K % 128 == 0, "K (", K, ") must be a multiple of 128 (blockwise float8 serves block ",
+              "size 128 only)");
+  return K;
+}
+
+void check_blockfp8_act(const Tensor& xq, const Tensor& x_scale) {
+  TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn, "xq must be float8_e4m3fn");
+  TORCH_CHECK(x_scale.scalar_type() == at::kFloat, "x_scale must be float32");
+  const int64_t K = check_blockfp8_k(xq, "xq");
+  TORCH_CHECK(x_scale.numel() * 128 == xq.numel() &&
+                  (x_scale.dim() == 0 || x_scale.size(-1) == K / 128),
+              "x_scale must hold one float32 per 1x128 block: [..., K/128] = [..., ", K / 128,
+              "], got ", x_scale.sizes());
+}
+
+std::pair<int64_t, int64_t> check_blockfp8_weight(const Tensor& wq, const Tensor& w_scale) {
+  TORCH_CHECK(wq.dim() == 2 && wq.scalar_type() == at::kFloat8_e4m3fn,
+              "wq must be a 2D float8_e4m3fn tensor");
+  TORCH_CHECK(w_scale.scalar_type() == at::kFloat, "w_scale must be float32");
+  const int64_t N = wq.size(0), K = check_blockfp8_k(wq, "wq");
+  TORCH_CHECK(w_scale.dim() == 2 && w_scale.size(0) == (N + 127) / 128 &&
+                  w_scale.size(1) == K / 128,
+              "w_scale must hold one float32 per 128x128 block: [ceil(N/128), K/128] = [",
+              (N + 127) / 128, ", ", K / 128, "], got ", w_scale.sizes());
+  return {N, K};
+}
+
+std::tuple<Tensor, Tensor> blockfp8_quantize_act(const Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), "expected x on a HIP device, got ", x.device());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "blockfp8 quantize act (HIP) needs bf16 x");
+  const int64_t K = check_blockfp8_k(x, "x");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor q = at::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+  Tensor s = at::empty({M, K / 128}, x.options().dtype(at::kFloat));
+  check_rc(tao_blockfp8_quantize_act_bf16(cptr<uint16_t>(x2), mptr<uint8_t>(q), mptr<float>(s), M,
+                                          K, stream_of(x)),
+           "tao_blockfp8_quantize_act_bf16");
+  std::vector<int64_t> ss(x.sizes().begin(), x.sizes().end() - 1);
+  ss.push_back(K / 128);
+  return {q.reshape(x.sizes()), s.reshape(ss)};
+}
+
+std::tuple<Tensor, Tensor> blockfp8_quantize_weight(const Tensor& w) {
+  TORCH_CHECK(w.is_cuda(), "expected w on a HIP device, got ", w.device());
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16, "blockfp8 quantize weight (HIP) needs bf16 w");
+  TORCH_CHECK(w.dim() == 2, "blockfp8 quantize weight: w must be 2D [N, K]");
+  const int64_t N = w.size(0), K = check_blockfp8_k(w, "w");
+  const Tensor w2 = rows_of(w, K);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+  Tensor q = at::empty({N, K}, w.options().dtype(at::kFloat8_e4m3fn));
+  Tensor s = at::empty({(N + 127) / 128, K / 128}, w.options().dtype(at::kFloat));
+  check_rc(tao_blockfp8_quantize_weight_bf16(cptr<uint16_t>(w2), mptr<uint8_t>(q), mptr<float>(s),
+                                             N, K, stream_of(w)),
+           "tao_blockfp8_quantize_weight_bf16");
+  return {q, s};
+}
+
+Tensor blockfp8_dequantize_weight(const Tensor& wq, const Tensor& w_scale, bool out_bf16) {
+  TORCH_CHECK(wq.is_cuda(), "expected wq on a HIP device, got ", wq.device());
+  const auto [N, K] = check_blockfp8_weight(wq, w_scale);
+  check_device(wq, w_scale, "w_scale");
+  const Tensor q = wq.contiguous();
+  const Tensor s = w_scale.contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(wq.device());
+  Tensor out = at::empty({N, K}, wq.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  check_rc(tao_blockfp8_dequant_weight(cptr<uint8_t>(q), cptr<float>(s), out.data_ptr(), N, K,
+                                       out_bf16 ? 1 : 0, stream_of(wq)),
+           "tao_blockfp8_dequant_weight");
+  return out;
+}
+
+Tensor blockfp8_scaled_mm(const Tensor& xq, const Tensor& x_scale, const Tensor& wq,
+                          const Tensor& w_scale, const std::optional<Tensor>& bias) {
+  const auto [N, K] = check_blockfp8_weight(wq, w_scale);
+  TORCH_CHECK(xq.dim() >= 1 && xq.size(-1) == K, "x last dim ", xq.dim() ? xq.size(-1) : 0,
+              " != K ", K);
+  check_blockfp8_act(xq, x_scale);
+  TORCH_CHECK(!bias.has_value() || (bias->scalar_type() == at::kBFloat16 && bias->numel() == N),
+              "bias must be bfloat16 with N elements");
+  check_device(xq, x_scale, "x_scale");
+  check_device(xq, wq, "wq");
+  check_device(xq, w_scale, "w_scale");
+  check_device(xq, bias, "bias");
+  const Tensor x2 = xq.reshape({-1, K}).contiguous();
+  const int64_t M = x2.size(0);
+  const Tensor xs = x_scale.reshape({-1, K / 128}).contiguous();
+  const Tensor ws = w_scale.contiguous();
+  const Tensor w = wq.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(xq.device());
+  Tensor y = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
+  check_rc(tao_blockfp8_scaled_mm_bf16(cptr<uint8_t>(x2), cptr<float>(xs), cptr<uint8_t>(w),
+                                       cptr<float>(ws), b ? cptr<uint16_t>(*b) : nullptr,
+                                       mptr<uint16_t>(y), M, N, K, stream_of(xq)),
+           "tao_blockfp8_scaled_mm_bf16");
+  return y.reshape(out_shape(xq, N));
+}
+
+Tensor blockfp8_dyn_linear(const Tensor& x, const Tensor& wq, const Tensor& w_scale,
+                           const std::optional<Tensor>& bias) {
+  const auto [N, K] = check_blockfp8_weight(wq, w_scale);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "blockfp8_dyn_linear (HIP) needs bf16 x");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "x last dim ", x.dim() ? x.size(-1) : 0, " != K ",
+              K);
+  TORCH_CHECK(!bias.has_value() || (bias->scalar_type() == at::kBFloat16 && bias->numel() == N),
+              "bias must be bfloat16 with N elements");
+  check_device(x, wq, "wq");
+  check_device(x, w_scale, "w_scale");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const Tensor ws = w_scale.contiguous();
+  const Tensor w = wq.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  const uint16_t* bp = b ? cptr<uint16_t>(*b) : nullptr;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  if (M == 1 && K <= 65536) {
+    check_rc(tao_blockfp8_dyn_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(w), cptr<float>(ws),
+                                          bp, mptr<uint16_t>(y), 1, N, K, stream_of(x)),
+             "tao_blockfp8_dyn_linear_bf16");
+  } else if (M > 0) {
+    // codes and scales live in buffers of the caching allocator between the two launches
+    Tensor q = at::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+    Tensor s = at::empty({M, K / 128}, x.options().dtype(at::kFloat));
+    check_rc(tao_blockfp8_quantize_act_bf16(cptr<uint16_t>(x2), mptr<uint8_t>(q), mptr<float>(s),
+                                            M, K, stream_of(x)),
+             "tao_blockfp8_quantize_act_bf16");
+    check_rc(tao_blockfp8_scaled_mm_bf16(cptr<uint8_t>(q), cptr<float>(s), cptr<uint8_t>(w),
+                                         cptr<float>(ws), bp, mptr<uint16_t>(y), M, N, K,
+                                         stream_of(x)),
+             "tao_blockfp8_scaled_mm_bf16");
+  }
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
+  m.impl("blockfp8_quantize_act", &blockfp8_quantize_act);
+  m.impl("blockfp8_quantize_weight", &blockfp8_quantize_weight);
+  m.impl("blockfp8_dequantize_weight", &blockfp8_dequantize_weight);
+  m.impl("blockfp8_scaled_mm", &blockfp8_scaled_mm);
+  m.impl("blockfp8_dyn_linear", &blockfp8_dyn_linear);
   m.impl("int4_weight_only_linear", &int4_weight_only_linear);
   m.impl("int8_weight_only_linear", &int8_weight_only_linear);
   m.impl("int8_quantize_per_token", &int8_quantize_per_token);
@@ -566,6 +716,12 @@ extern "C" const char* tao_torch_ops_served_float8_dyn(void) {
 // The MXFP8 ops served here, again a set of their own.
 extern "C" const char* tao_torch_ops_served_mx(void) {
   return "mx_quantize_rows,mx_scaled_mm,mx_dyn_linear";
+}
+
+// The blockwise float8 ops served here, a set of their own too.
+extern "C" const char* tao_torch_ops_served_blockfp8(void) {
+  return "blockfp8_quantize_act,blockfp8_quantize_weight,blockfp8_dequantize_weight,"
+         "blockfp8_scaled_mm,blockfp8_dyn_linear";
 }
 
 // The MXFP4-weight ops served here, a set of their own as well.

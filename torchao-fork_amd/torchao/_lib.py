@@ -97,6 +97,12 @@ _SIGNATURES = {
     "tao_mxfp4_quantize_rows_bf16": [_p, _p, _p, _i64, _i64, _p],
     "tao_mxfp4w_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_mxfp4w_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_blockfp8_quantize_act_bf16": [_p, _p, _p, _i64, _i64, _p],
+    "tao_blockfp8_quantize_weight_bf16": [_p, _p, _p, _i64, _i64, _p],
+    "tao_blockfp8_dequant_weight": [_p, _p, _p, _i64, _i64, _int, _p],
+    "tao_blockfp8_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_blockfp8_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_tune_blockfp8_mfma": [_int],
     "tao_rmsnorm_bf16": [_p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_bf16": [_p, _p, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],
     "tao_add_rmsnorm_partials_bf16": [_p, _p, _i64, _p, _p, _p, _i64, _i64, ctypes.c_float, _p],

@@ -33,6 +33,7 @@ _KNOBS = {
     "fp8_gemv": ("tao_tune_fp8_gemv", 3),
     "fp8dyn_mfma": ("tao_tune_fp8dyn_mfma", 1),
     "mx_mfma": ("tao_tune_mx_mfma", 1),
+    "blockfp8_mfma": ("tao_tune_blockfp8_mfma", 1),
     "attn": ("tao_tune_attn", 1),
     "splitk_fenced": ("tao_tune_splitk_fenced", 1),
     "gemm_tile": ("tao_tune_gemm_tile", 2),

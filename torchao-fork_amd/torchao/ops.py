@@ -41,6 +41,10 @@ Operators:
     ``mx_quantize_rows`` -> ``mx_scaled_mm``.
   * ``mxfp4_quantize_rows`` / ``mxfp4w_scaled_mm`` / ``mxfp4w_dyn_linear`` — the same three for
     e2m1 weights (two codes per byte) under e4m3fn activations (csrc/mx_fp4.hip).
+  * ``blockfp8_quantize_act`` / ``blockfp8_quantize_weight`` / ``blockfp8_dequantize_weight`` /
+    ``blockfp8_scaled_mm`` / ``blockfp8_dyn_linear`` — the blockwise float8 recipe (e4m3fn codes,
+    fp32 scales per 1 x 128 activation block and 128 x 128 weight block, csrc/block_fp8.hip);
+    replace the Triton kernels of prototype/blockwise_fp8_inference/blockwise_quantization.py.
 """
 
 import ctypes
@@ -130,6 +134,19 @@ lib_mxfp4.define(
     "-> Tensor")
 lib_mxfp4.define(
     "mxfp4w_dyn_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias=None) -> Tensor")
+# The blockwise float8 ops (torchao.prototype.blockwise_fp8_inference), on a fragment of their own;
+# opchecked in tests/test_gpu_blockfp8.py. Codes cross as float8_e4m3fn, scales as float32:
+# [..., K/128] for the activation, [ceil(N/128), K/128] for the weight.
+lib_blockfp8 = torch.library.Library("torchao", "FRAGMENT")
+lib_blockfp8.define("blockfp8_quantize_act(Tensor x) -> (Tensor, Tensor)")
+lib_blockfp8.define("blockfp8_quantize_weight(Tensor w) -> (Tensor, Tensor)")
+lib_blockfp8.define(
+    "blockfp8_dequantize_weight(Tensor wq, Tensor w_scale, bool out_bf16=False) -> Tensor")
+lib_blockfp8.define(
+    "blockfp8_scaled_mm(Tensor xq, Tensor x_scale, Tensor wq, Tensor w_scale, Tensor? bias=None) "
+    "-> Tensor")
+lib_blockfp8.define(
+    "blockfp8_dyn_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -1034,6 +1051,180 @@ def _mxfp4w_dyn_linear_cuda(x, wq, w_scale, bias=None):
     return y.reshape(_linear_out_shape(x, N))
 
 
+# ---------------------------------------------------------------------------------------------
+# Blockwise float8 (torchao.prototype.blockwise_fp8_inference): e4m3fn codes, one fp32 scale per
+# 1 x 128 block of the activation and per 128 x 128 block of the weight (csrc/block_fp8.hip)
+# ---------------------------------------------------------------------------------------------
+def _check_blockfp8_k(t, name):
+    torch._check(t.dim() >= 1, lambda: f"{name} must have at least one dimension")
+    K = t.size(-1)
+    torch._check(K % 128 == 0, lambda: f"K ({K}) must be a multiple of 128 (blockwise float8 "
+                                       f"serves block size 128 only)")
+    return K
+
+
+def _check_blockfp8_act(xq, x_scale):
+    torch._check(xq.dtype is torch.float8_e4m3fn, lambda: "xq must be float8_e4m3fn")
+    torch._check(x_scale.dtype is torch.float32, lambda: "x_scale must be float32")
+    K = _check_blockfp8_k(xq, "xq")
+    torch._check(
+        x_scale.numel() * 128 == xq.numel() and (x_scale.dim() == 0 or x_scale.size(-1) == K // 128),
+        lambda: f"x_scale must hold one float32 per 1x128 block: [..., K/128] = [..., {K // 128}], "
+                f"got {tuple(x_scale.shape)}")
+
+
+def _check_blockfp8_weight(wq, w_scale):
+    torch._check(wq.dim() == 2 and wq.dtype is torch.float8_e4m3fn,
+                 lambda: "wq must be a 2D float8_e4m3fn tensor")
+    torch._check(w_scale.dtype is torch.float32, lambda: "w_scale must be float32")
+    N, K = wq.size(0), _check_blockfp8_k(wq, "wq")
+    NB = (N + 127) // 128
+    torch._check(
+        w_scale.dim() == 2 and w_scale.size(0) == NB and w_scale.size(1) == K // 128,
+        lambda: f"w_scale must hold one float32 per 128x128 block: [ceil(N/128), K/128] = "
+                f"[{NB}, {K // 128}], got {tuple(w_scale.shape)}")
+    return N, K
+
+
+def _check_blockfp8_bias(bias, N):
+    torch._check(bias is None or (bias.dtype is torch.bfloat16 and bias.numel() == N),
+                 lambda: "bias must be bfloat16 with N elements")
+
+
+@torch.library.register_fake("torchao::blockfp8_quantize_act")
+def _(x):
+    K = _check_blockfp8_k(x, "x")
+    return (x.new_empty(x.shape, dtype=torch.float8_e4m3fn),
+            x.new_empty((*x.shape[:-1], K // 128), dtype=torch.float32))
+
+
+def _blockfp8_quantize_act_cuda(x: Tensor):
+    """bf16 x [..., K] -> (e4m3fn codes [..., K], fp32 scales [..., K/128])."""
+    torch._check(x.dtype is torch.bfloat16, lambda: "blockfp8 quantize act (HIP) needs bf16 x")
+    K = _check_blockfp8_k(x, "x")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+    s = torch.empty((M, K // 128), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("tao_blockfp8_quantize_act_bf16", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+    return q.reshape(x.shape), s.reshape(*x.shape[:-1], K // 128)
+
+
+@torch.library.register_fake("torchao::blockfp8_quantize_weight")
+def _(w):
+    torch._check(w.dim() == 2, lambda: "blockfp8 quantize weight: w must be 2D [N, K]")
+    K = _check_blockfp8_k(w, "w")
+    return (w.new_empty(w.shape, dtype=torch.float8_e4m3fn),
+            w.new_empty(((w.size(0) + 127) // 128, K // 128), dtype=torch.float32))
+
+
+def _blockfp8_quantize_weight_cuda(w: Tensor):
+    """bf16 w [N, K] -> (e4m3fn codes [N, K], fp32 scales [ceil(N/128), K/128])."""
+    torch._check(w.dtype is torch.bfloat16, lambda: "blockfp8 quantize weight (HIP) needs bf16 w")
+    torch._check(w.dim() == 2, lambda: "blockfp8 quantize weight: w must be 2D [N, K]")
+    K = _check_blockfp8_k(w, "w")
+    N = w.size(0)
+    w2 = w if w.is_contiguous() and w.data_ptr() % 16 == 0 else w.contiguous()
+    q = torch.empty((N, K), dtype=torch.float8_e4m3fn, device=w.device)
+    s = torch.empty(((N + 127) // 128, K // 128), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("tao_blockfp8_quantize_weight_bf16", _ptr(w2), _ptr(q), _ptr(s), N, K,
+                  _stream(w))
+    return q, s
+
+
+@torch.library.register_fake("torchao::blockfp8_dequantize_weight")
+def _(wq, w_scale, out_bf16=False):
+    _check_blockfp8_weight(wq, w_scale)
+    return wq.new_empty(wq.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32)
+
+
+def _blockfp8_dequantize_weight_cuda(wq, w_scale, out_bf16=False):
+    """float(code) * scale in fp32, stored as fp32 or rounded once to bf16."""
+    N, K = _check_blockfp8_weight(wq, w_scale)
+    _same_device(wq, w_scale=w_scale)
+    q, s = wq.contiguous(), w_scale.contiguous()
+    out = torch.empty((N, K), dtype=torch.bfloat16 if out_bf16 else torch.float32,
+                      device=wq.device)
+    with torch.cuda.device(wq.device):
+        _lib.call("tao_blockfp8_dequant_weight", _ptr(q), _ptr(s), _ptr(out), N, K,
+                  1 if out_bf16 else 0, _stream(wq))
+    return out
+
+
+@torch.library.register_fake("torchao::blockfp8_scaled_mm")
+def _(xq, x_scale, wq, w_scale, bias=None):
+    N, K = _check_blockfp8_weight(wq, w_scale)
+    torch._check(xq.size(-1) == K, lambda: f"x last dim {xq.size(-1)} != K {K}")
+    return xq.new_empty(_linear_out_shape(xq, N), dtype=torch.bfloat16)
+
+
+def _blockfp8_scaled_mm_cuda(xq, x_scale, wq, w_scale, bias=None):
+    """y = bf16(sum_b P_b * (xs_b * ws_b) + bias), fp32 up to the one rounding
+    (include/torchao_mi355x.h tao_blockfp8_scaled_mm_bf16)."""
+    N, K = _check_blockfp8_weight(wq, w_scale)
+    torch._check(xq.dim() >= 1 and xq.size(-1) == K,
+                 lambda: f"x last dim {xq.size(-1) if xq.dim() else 0} != K {K}")
+    _check_blockfp8_act(xq, x_scale)
+    _check_blockfp8_bias(bias, N)
+    _same_device(xq, x_scale=x_scale, wq=wq, w_scale=w_scale, bias=bias)
+    x2 = xq.reshape(-1, K).contiguous()
+    M = x2.size(0)
+    xs = x_scale.reshape(-1, K // 128).contiguous()
+    ws = w_scale.contiguous()
+    wq = wq.contiguous()
+    if bias is not None:
+        bias = bias.contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    with torch.cuda.device(xq.device):
+        _lib.call("tao_blockfp8_scaled_mm_bf16", _ptr(x2), _ptr(xs), _ptr(wq), _ptr(ws),
+                  _ptr(bias), _ptr(y), M, N, K, _stream(xq))
+    return y.reshape(_linear_out_shape(xq, N))
+
+
+@torch.library.register_fake("torchao::blockfp8_dyn_linear")
+def _(x, wq, w_scale, bias=None):
+    N, K = _check_blockfp8_weight(wq, w_scale)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N), dtype=torch.bfloat16)
+
+
+def _blockfp8_dyn_linear_cuda(x, wq, w_scale, bias=None):
+    """The whole linear from a bf16 activation. One token: block quantisation + GEMV in one
+    launch. More: blockfp8_quantize_act into buffers of the caching allocator, then
+    blockfp8_scaled_mm; bit-identical to calling the two ops."""
+    N, K = _check_blockfp8_weight(wq, w_scale)
+    torch._check(x.dtype is torch.bfloat16, lambda: "blockfp8_dyn_linear (HIP) needs bf16 x")
+    torch._check(x.dim() >= 1 and x.size(-1) == K,
+                 lambda: f"x last dim {x.size(-1) if x.dim() else 0} != K {K}")
+    _check_blockfp8_bias(bias, N)
+    _same_device(x, wq=wq, w_scale=w_scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    ws = w_scale.contiguous()
+    wq = wq.contiguous()
+    if bias is not None:
+        bias = bias.contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if M == 1 and K <= 65536:
+            _lib.call("tao_blockfp8_dyn_linear_bf16", _ptr(x2), _ptr(wq), _ptr(ws), _ptr(bias),
+                      _ptr(y), 1, N, K, _stream(x))
+        elif M > 0:
+            q = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+            s = torch.empty((M, K // 128), dtype=torch.float32, device=x.device)
+            _lib.call("tao_blockfp8_quantize_act_bf16", _ptr(x2), _ptr(q), _ptr(s), M, K,
+                      _stream(x))
+            _lib.call("tao_blockfp8_scaled_mm_bf16", _ptr(q), _ptr(s), _ptr(wq), _ptr(ws),
+                      _ptr(bias), _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
 # ---- register device impls ------------------------------------------------------------------
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
@@ -1046,6 +1237,7 @@ _native_served_float8: frozenset = frozenset()
 _native_served_float8_dyn: frozenset = frozenset()
 _native_served_mx: frozenset = frozenset()
 _native_served_mxfp4: frozenset = frozenset()
+_native_served_blockfp8: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -1068,6 +1260,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_mxfp4
         _served.restype = ctypes.c_char_p
         _native_served_mxfp4 = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_blockfp8
+        _served.restype = ctypes.c_char_p
+        _native_served_blockfp8 = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -1096,6 +1291,11 @@ def native_dispatch_mx() -> frozenset:
 def native_dispatch_mxfp4() -> frozenset:
     """The MXFP4-weight ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_mxfp4
+
+
+def native_dispatch_blockfp8() -> frozenset:
+    """The blockwise float8 ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_blockfp8
 
 
 for _name, _fn in [
@@ -1143,6 +1343,15 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_mxfp4:
         lib_mxfp4.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("blockfp8_quantize_act", _blockfp8_quantize_act_cuda),
+    ("blockfp8_quantize_weight", _blockfp8_quantize_weight_cuda),
+    ("blockfp8_dequantize_weight", _blockfp8_dequantize_weight_cuda),
+    ("blockfp8_scaled_mm", _blockfp8_scaled_mm_cuda),
+    ("blockfp8_dyn_linear", _blockfp8_dyn_linear_cuda),
+]:
+    if _name not in _native_served_blockfp8:
+        lib_blockfp8.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")
