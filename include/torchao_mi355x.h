@@ -61,6 +61,36 @@ int tao_int4wo_linear_bf16(const uint16_t* x, const uint32_t* packed, const uint
                            const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                            int64_t group_size, void* stream);
 
+/* y[m][k] = bf16( float(x[m][k]) / float(scale[k]) ): the IEEE fp32 quotient (no reciprocal, no
+ * fast-math) rounded once to nearest-even; zero, inf, NaN and bf16-subnormal operands and results
+ * behave as IEEE division does (a NaN stays a quiet NaN). x, y bf16 [M][K], scale bf16 [K].
+ * Replaces `scaled_input_act = input_tensor / scale` of
+ * WeightTensorWithLinearActivationScaleMetadata._quantized_linear_op at
+ * torchao/quantization/linear_activation_scale.py:61-70 (the AWQ / SmoothQuant equalization
+ * scale). K % 8 == 0; x, scale, y 16-B aligned; M >= 0 (M == 0 is a no-op). */
+int tao_act_prescale_bf16(const uint16_t* x, const uint16_t* scale, uint16_t* y, int64_t M,
+                          int64_t K, void* stream);
+
+/* One token (M <= 1): tao_act_prescale_bf16 of the bf16 token x [K] by act_scale [K] and
+ * tao_int4wo_linear_bf16 in one launch: the quotient is formed while the workgroup stages x in
+ * LDS. Replaces the division and the F.linear of linear_activation_scale.py:61-70 over an int4
+ * TensorCoreTiledLayout weight. Bit-identical to the two calls with the second under
+ * the x-in-LDS tuning mode (the same launch shape and summation order). Returns
+ * TAO_ERR_INVALID_ARGUMENT for M > 1, for a bias, and for K > 16384 (the prologue holds x in
+ * registers): those are the two calls, the caller owning the buffer between them (as for the int8
+ * and float8 dynamic paths). act_scale 16-B aligned. */
+int tao_int4wo_prescaled_linear_bf16(const uint16_t* x, const uint16_t* act_scale,
+                                     const uint32_t* packed, const uint16_t* sz,
+                                     const uint16_t* bias, uint16_t* y, int64_t M, int64_t N,
+                                     int64_t K, int64_t group_size, void* stream);
+
+/* 1 when a caller replacing linear_activation_scale.py:61-70 should take
+ * tao_int4wo_prescaled_linear_bf16 for this call, 0 when it should take the two calls: one token
+ * without a bias at K <= 4096 and N * K <= 2^24 weights. Past those the plain linear's own
+ * launch shapes outrun the prologue's shape by more than the saved launch (measured:
+ * experiments/bench_awq.py). Never fails. */
+int tao_int4wo_prescaled_linear_fused(int64_t M, int64_t N, int64_t K, int has_bias);
+
 /* packed[N][K/8] <- q[N][K] (int32 values 0..15).
  * Replaces aten._convert_weight_to_int4pack(u8, inner_k_tiles) at
  * torchao/dtypes/uintx/tensor_core_tiled_layout.py:279 (device kernel). K % 8 == 0. */

@@ -48,6 +48,20 @@ __device__ __forceinline__ uint32_t mul_pair_bf16(uint32_t xv, uint32_t wv) {
   return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
 }
 
+// bf16(float(x) / float(s)) on a bf16 pair: the IEEE fp32 quotient (v_div_scale / v_div_fmas /
+// v_div_fixup, no reciprocal estimate), then one round-to-nearest-even. Shared by
+// tao_act_prescale_bf16 and the prologue of tao_int4wo_prescaled_linear_bf16, so both write the
+// same bits.
+__device__ __forceinline__ uint32_t div_pair_bf16(uint32_t xv, uint32_t sv) {
+  const float lo = bf16lo_to_f32(xv) / bf16lo_to_f32(sv);
+  const float hi = bf16hi_to_f32(xv) / bf16hi_to_f32(sv);
+  return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
+}
+__device__ __forceinline__ uint4 div_piece_bf16(uint4 xv, uint4 sv) {
+  return make_uint4(div_pair_bf16(xv.x, sv.x), div_pair_bf16(xv.y, sv.y),
+                    div_pair_bf16(xv.z, sv.z), div_pair_bf16(xv.w, sv.w));
+}
+
 // a * b rounded to fp32 on its own: never contracted into a neighbouring add
 __device__ __forceinline__ float mul_unfused(float a, float b) {
 #pragma clang fp contract(off)
@@ -67,8 +81,10 @@ __device__ __forceinline__ float mul_unfused(float a, float b) {
 // the arguments Wk and G. The wave's (wk, rg) are then a mask and a shift instead of a 32-bit
 // division, the row strides and clamps fold on the scalar unit, a wave that owns one slice
 // (!PAIR, S == WK) runs no loop, and wg_combine's loop over the K-split partials unrolls.
+// PSC (with NPT; int4wo_gemv_prescale_kernel): the prologue stages bf16(x / act_scale), the
+// per-input-channel scale [K] passed as fu.norm_w, instead of the RMSNorm.
 template <int MT, int RPW, bool PAIR, int NPT = 0, int EPI = kEpiNone, int MRG = 0,
-          bool COH = false, int WK = 0, int GG = 0>
+          bool COH = false, int WK = 0, int GG = 0, bool PSC = false>
 __device__ __forceinline__ void gemv_body(
     const uint16_t* __restrict__ x, const uint4* __restrict__ wq, const uint32_t* __restrict__ sz,
     const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M, int N, int K, int gshift,
@@ -84,6 +100,7 @@ __device__ __forceinline__ void gemv_body(
   // entry test, and the pointer arguments are not loaded behind one
   if constexpr (STATIC && PAIR) __builtin_assume(S > WK);
   static_assert(MRG == 0 || (PRO && EPI == kEpiNone && MT == 1), "merge prologue: M == 1, NPT");
+  static_assert(!PSC || (PRO && EPI == kEpiNone && MRG == 0), "pre-scale prologue: NPT, plain");
   static_assert(!(PRO || EPI) || (MT == 1 && RPW % 2 == 0), "fusions are M == 1, row pairs");
   constexpr int V = RPW * MT;
   extern __shared__ float red[];  // [G][Wk][V] (PRO: + [8] partial sums, + normalised x [K])
@@ -140,7 +157,10 @@ __device__ __forceinline__ void gemv_body(
       const int i = threadIdx.x + u * (int)blockDim.x;
       const int ic = i < nx ? i : nx - 1;  // clamped, masked below
       xv[u] = xr[ic];
-      if (fu.norm_w != nullptr) gv[u] = gr[ic];  // wave-uniform
+      if constexpr (PSC)
+        gv[u] = gr[ic];  // the activation scale's pieces
+      else if (fu.norm_w != nullptr)
+        gv[u] = gr[ic];  // wave-uniform
     }
   };
   auto norm_finish = [&]() __attribute__((always_inline)) {
@@ -174,6 +194,18 @@ __device__ __forceinline__ void gemv_body(
         if (i < nx) {
           const int c = i >> 2;
           xs[c * 4 + (((i & 3) + (c >> 2)) & 3)] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
+        }
+      }
+      __syncthreads();
+      return;
+    }
+    if constexpr (PSC) {  // x / act_scale, as tao_act_prescale_bf16 writes it
+#pragma unroll
+      for (int u = 0; u < NPT; ++u) {
+        const int i = threadIdx.x + u * (int)blockDim.x;
+        if (i < nx) {
+          const int c = i >> 2;
+          xs[c * 4 + (((i & 3) + (c >> 2)) & 3)] = div_piece_bf16(xv[u], gv[u]);
         }
       }
       __syncthreads();
@@ -366,7 +398,7 @@ __device__ __forceinline__ void gemv_body(
     for (int m = 0; m < MT; ++m) v[r * MT + m] = acc[r][m];
   wave_reduce_scatter<V>(v, lane);
 
-  if constexpr (PRO) {
+  if constexpr (PRO && !PSC) {
     if (fu.norm_deferred && fu.norm_w != nullptr) {  // the deferred RMSNorm scale (norm_finish)
       const float* ssr = red + G * Wk * V;
       float t = 0.f;
@@ -400,6 +432,31 @@ __global__ __launch_bounds__(512, WPE) void int4wo_gemv_kernel(
     int Wk, int G, int S, GemvFuse fu) {
   gemv_body<MT, RPW, PAIR, NPT, EPI, MRG>(x, wq, sz, bias, y, M, N, K, gshift, Wk, G, S, fu,
                                           (int)blockIdx.x * G * RPW);
+}
+
+// The AWQ linear of one token (tao_int4wo_prescaled_linear_bf16): the plain linear of the PRO
+// launch shape with x / act_scale formed while x is staged in LDS. fu.norm_w = act_scale [K].
+template <int RPW, int WPE, bool PAIR, int NPT>
+__global__ __launch_bounds__(512, WPE) void int4wo_gemv_prescale_kernel(
+    const uint16_t* __restrict__ x, const uint4* __restrict__ wq, const uint32_t* __restrict__ sz,
+    const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M, int N, int K, int gshift,
+    int Wk, int G, int S, GemvFuse fu) {
+  gemv_body<1, RPW, PAIR, NPT, kEpiNone, 0, false, 0, 0, true>(
+      x, wq, sz, bias, y, M, N, K, gshift, Wk, G, S, fu, (int)blockIdx.x * G * RPW);
+}
+
+// y[m][k] = bf16(x[m][k] / scale[k]) (tao_act_prescale_bf16): one 16-B piece of a row per thread,
+// the scale's piece loaded once and kept across the rows blockIdx.y walks.
+__global__ __launch_bounds__(256) void act_prescale_kernel(const uint4* __restrict__ x,
+                                                           const uint4* __restrict__ scale,
+                                                           uint4* __restrict__ y, int M, int nx) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= nx) return;
+  const uint4 sv = scale[i];
+  for (int m = (int)blockIdx.y; m < M; m += (int)gridDim.y) {
+    const size_t o = (size_t)m * nx + i;
+    y[o] = div_piece_bf16(x[o], sv);
+  }
 }
 
 // The plain M == 1 GEMV on a compile-time launch shape (launch_gemv_static picks it when
@@ -672,7 +729,7 @@ GemvShape default_shape(int S) {
   return {wk, g};
 }
 
-template <int MT, int RPW, int WPE, int NPT = 0, int EPI = kEpiNone, int MRG = 0>
+template <int MT, int RPW, int WPE, int NPT = 0, int EPI = kEpiNone, int MRG = 0, bool PSC = false>
 int launch_gemv(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
                 const uint16_t* bias, uint16_t* y, int M, int N, int K, int gshift,
                 GemvShape sh, hipStream_t stream, const GemvFuse& fu = GemvFuse{}) {
@@ -690,6 +747,18 @@ int launch_gemv(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
   // workgroups resident per CU (160 KiB / bytes) and so the weight bytes in flight per CU
   if (tao::tuning().gemv_lds > 0 && (size_t)tao::tuning().gemv_lds > lds)
     lds = (size_t)tao::tuning().gemv_lds;
+  if constexpr (PSC) {
+    static_assert(MT == 1 && NPT > 0 && EPI == kEpiNone && MRG == 0, "pre-scale: the plain PRO GEMV");
+    if (S > wk)
+      launch((int4wo_gemv_prescale_kernel<RPW, WPE, true, NPT>), dim3(grid), dim3(threads), lds,
+             stream, x, reinterpret_cast<const uint4*>(packed),
+             reinterpret_cast<const uint32_t*>(sz), bias, y, M, N, K, gshift, wk, sh.g, S, fu);
+    else
+      launch((int4wo_gemv_prescale_kernel<RPW, WPE, false, NPT>), dim3(grid), dim3(threads), lds,
+             stream, x, reinterpret_cast<const uint4*>(packed),
+             reinterpret_cast<const uint32_t*>(sz), bias, y, M, N, K, gshift, wk, sh.g, S, fu);
+    return check_launch("int4wo_gemv_prescale_kernel");
+  }
   if (S > wk)
     launch((int4wo_gemv_kernel<MT, RPW, WPE, true, NPT, EPI, MRG>), dim3(grid), dim3(threads), lds,
            stream, x, reinterpret_cast<const uint4*>(packed),
@@ -816,7 +885,7 @@ int try_gemv_static(const uint16_t* x, const uint32_t* packed, const uint16_t* s
   return -1;
 }
 
-template <int NPT, int EPI>
+template <int NPT, int EPI, bool PSC = false>
 int launch_decode_rows(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
                        uint16_t* y, int N, int K, int gs, hipStream_t stream, const GemvFuse& fu,
                        const M1Shape& c) {
@@ -828,14 +897,15 @@ int launch_decode_rows(const uint16_t* x, const uint32_t* packed, const uint16_t
   // slices' loads live across it) does not fit 64 VGPRs, so it runs at <= 4 waves per SIMD
   if (c.rpw <= 2) {
     if constexpr (NPT > 0)
-      return launch_gemv<1, 2, 4, NPT, EPI>(x, packed, sz, nullptr, y, 1, N, K, gs, c.sh, stream,
-                                            fu);
+      return launch_gemv<1, 2, 4, NPT, EPI, 0, PSC>(x, packed, sz, nullptr, y, 1, N, K, gs, c.sh,
+                                                    stream, fu);
     else
       return launch_gemv<1, 2, 8, NPT, EPI>(x, packed, sz, nullptr, y, 1, N, K, gs, c.sh, stream,
                                             fu);
   }
   if (c.occ == 4 || NPT > 0)
-    return launch_gemv<1, 4, 4, NPT, EPI>(x, packed, sz, nullptr, y, 1, N, K, gs, c.sh, stream, fu);
+    return launch_gemv<1, 4, 4, NPT, EPI, 0, PSC>(x, packed, sz, nullptr, y, 1, N, K, gs, c.sh,
+                                                  stream, fu);
   return launch_gemv<1, 4, 8, 0, EPI>(x, packed, sz, nullptr, y, 1, N, K, gs, c.sh, stream, fu);
 }
 
@@ -890,7 +960,7 @@ int launch_attn_out(const float* part, const uint32_t* packed, const uint16_t* s
                                                 stream, fu);
 }
 
-template <bool PRO, int EPI>
+template <bool PRO, int EPI, bool PSC = false>
 int launch_decode(const uint16_t* x, const uint32_t* packed, const uint16_t* sz, uint16_t* y,
                   int N, int K, int gs, hipStream_t stream, const GemvFuse& fu) {
   const int S = (K / 32 + 63) / 64;
@@ -900,8 +970,8 @@ int launch_decode(const uint16_t* x, const uint32_t* packed, const uint16_t* sz,
     const int wk = c.sh.wk < S ? c.sh.wk : S;
     const int threads = 64 * wk * c.sh.g;
     if (threads * 8 * 2 >= K)
-      return launch_decode_rows<2, EPI>(x, packed, sz, y, N, K, gs, stream, fu, c);
-    return launch_decode_rows<4, EPI>(x, packed, sz, y, N, K, gs, stream, fu, c);
+      return launch_decode_rows<2, EPI, PSC>(x, packed, sz, y, N, K, gs, stream, fu, c);
+    return launch_decode_rows<4, EPI, PSC>(x, packed, sz, y, N, K, gs, stream, fu, c);
   } else {
     return launch_decode_rows<0, EPI>(x, packed, sz, y, N, K, gs, stream, fu, c);
   }
@@ -1054,6 +1124,60 @@ extern "C" int tao_int4wo_attn_out_bf16(const float* partial, int64_t splits, in
                                  gs, st);
 }
 
+extern "C" int tao_act_prescale_bf16(const uint16_t* x, const uint16_t* scale, uint16_t* y,
+                                     int64_t M, int64_t K, void* stream) {
+  TAO_CHECK_ARG(M >= 0 && K >= 0 && M < (1LL << 31) && K < (1LL << 31), "act_prescale: size out of range");
+  TAO_CHECK_ARG(K % 8 == 0, "act_prescale: K (%lld) must be a multiple of 8", (long long)K);
+  if (M == 0 || K == 0) return TAO_OK;
+  TAO_CHECK_ARG(x != nullptr && scale != nullptr && y != nullptr,
+                "act_prescale: x, scale and y are required");
+  TAO_CHECK_ALIGN(x, 16, "x");
+  TAO_CHECK_ALIGN(scale, 16, "scale");
+  TAO_CHECK_ALIGN(y, 16, "y");
+  const int nx = (int)(K / 8);
+  const unsigned rows = (unsigned)(M < 4096 ? M : 4096);
+  tao::launch(tao::act_prescale_kernel, dim3((unsigned)((nx + 255) / 256), rows), dim3(256), 0,
+              tao::as_stream(stream), reinterpret_cast<const uint4*>(x),
+              reinterpret_cast<const uint4*>(scale), reinterpret_cast<uint4*>(y), (int)M, nx);
+  return tao::check_launch("act_prescale_kernel");
+}
+
+// The op-level route of the AWQ int4 linear. At M = 1 in one process (experiments/bench_awq.py,
+// profiles/awq_bench.jsonl, awq_bench_boundary.jsonl; us per linear, one launch vs act_prescale +
+// the plain GEMV): 4096x2048 3.82 vs 4.85, 8192x2048 4.80 vs 6.03, 2048x4096 4.06 vs 4.75,
+// 4096x4096 5.50 vs 5.55; 5120x4096 6.32 vs 6.21, 6144x4096 6.57 vs 6.43, 14336x4096 10.95 vs
+// 9.68, 4096x5120 7.14 vs 6.79, 1024x8192 5.73 vs 5.48, 2048x8192 6.40 vs 6.42, 4096x14336 11.15
+// vs 10.27. The one launch runs on pro_shape's whole-row shape (one wave walks a row); past
+// K = 4096, and past 2^24 weights at K = 4096, the plain linear's m1_shape choices beat that shape
+// by more than the second launch costs.
+extern "C" int tao_int4wo_prescaled_linear_fused(int64_t M, int64_t N, int64_t K, int has_bias) {
+  return M == 1 && !has_bias && K > 0 && K <= 4096 && N > 0 && N * K <= (1LL << 24) ? 1 : 0;
+}
+
+extern "C" int tao_int4wo_prescaled_linear_bf16(const uint16_t* x, const uint16_t* act_scale,
+                                                const uint32_t* packed,
+                                                const uint16_t* scales_and_zeros,
+                                                const uint16_t* bias, uint16_t* y, int64_t M,
+                                                int64_t N, int64_t K, int64_t group_size,
+                                                void* stream) {
+  int rc = tao::int4_check_linear_args(x, packed, scales_and_zeros, y, M, N, K, group_size);
+  if (rc != TAO_OK) return rc;
+  TAO_CHECK_ARG(M <= 1, "int4 prescaled linear: one token (M <= 1, got %lld); more tokens are "
+                "tao_act_prescale_bf16 then tao_int4wo_linear_bf16", (long long)M);
+  TAO_CHECK_ARG(bias == nullptr, "int4 prescaled linear: a bias takes the two launches "
+                "(tao_act_prescale_bf16 then tao_int4wo_linear_bf16)");
+  TAO_CHECK_ARG(K <= 8 * tao::kMaxNormPT * 512,
+                "int4 prescaled linear: the pre-scale prologue needs K <= %d",
+                8 * tao::kMaxNormPT * 512);
+  if (M == 0 || N == 0) return TAO_OK;
+  TAO_CHECK_ARG(act_scale != nullptr, "int4 prescaled linear: act_scale is required");
+  TAO_CHECK_ALIGN(act_scale, 16, "act_scale");
+  tao::GemvFuse fu{};
+  fu.norm_w = act_scale;
+  return tao::launch_decode<true, tao::kEpiNone, true>(x, packed, scales_and_zeros, y, (int)N,
+                                                       (int)K, tao::gshift_of(group_size),
+                                                       tao::as_stream(stream), fu);
+}
 
 extern "C" int tao_tune_int4_lds(int bytes) {
   TAO_CHECK_ARG(bytes >= 0 && bytes <= 160 * 1024, "tune: int4_lds bytes must be 0..163840");

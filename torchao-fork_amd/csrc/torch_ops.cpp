@@ -5,7 +5,8 @@
 // fp8_scaled_mm, fp8_dyn_linear, the MXFP8 set mx_quantize_rows, mx_scaled_mm, mx_dyn_linear, and the
 // MXFP4-weight set mxfp4_quantize_rows, mxfp4w_scaled_mm, mxfp4w_dyn_linear, and the blockwise
 // float8 set blockfp8_quantize_act, blockfp8_quantize_weight, blockfp8_dequantize_weight,
-// blockfp8_scaled_mm, blockfp8_dyn_linear.
+// blockfp8_scaled_mm, blockfp8_dyn_linear, and the activation pre-scale set act_prescale,
+// int4_prescaled_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -103,6 +104,79 @@ Tensor int4_weight_only_linear(const Tensor& x, const Tensor& packed_w, const Te
                                   b ? cptr<uint16_t>(*b) : nullptr, mptr<uint16_t>(y), M, N, K,
                                   group_size, stream_of(x)),
            "tao_int4wo_linear_bf16");
+  return y.reshape(out_shape(x, N));
+}
+
+// ---- activation pre-scale (AWQ / SmoothQuant equalization; ops.py _act_prescale_cuda) -----------
+Tensor check_act_scale(const Tensor& x, const Tensor& scale, int64_t K, const char* op) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, op, " (HIP) needs bf16 x, got ", x.scalar_type());
+  TORCH_CHECK(scale.scalar_type() == at::kBFloat16, op, " (HIP) needs a bf16 scale, got ",
+              scale.scalar_type());
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "x last dim ", x.dim() ? x.size(-1) : 0, " != K ",
+              K);
+  TORCH_CHECK(scale.numel() == K, "scale must have K = ", K, " elements, got ", scale.numel());
+  check_device(x, scale, "scale");
+  Tensor s = scale.reshape({-1});
+  if (!s.is_contiguous() || reinterpret_cast<uintptr_t>(s.data_ptr()) % 16) s = s.contiguous();
+  return s;
+}
+
+Tensor act_prescale(const Tensor& x, const Tensor& scale) {
+  const int64_t K = scale.numel();
+  const Tensor s = check_act_scale(x, scale, K, "act_prescale");
+  TORCH_CHECK(K % 8 == 0, "act_prescale needs K % 8 == 0, got K = ", K);
+  const Tensor x2 = rows_of(x, K);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty(x2.sizes(), x.options());
+  check_rc(tao_act_prescale_bf16(cptr<uint16_t>(x2), cptr<uint16_t>(s), mptr<uint16_t>(y),
+                                 x2.size(0), K, stream_of(x)),
+           "tao_act_prescale_bf16");
+  return y.reshape(x.sizes());
+}
+
+// One token without a bias, where tao_int4wo_prescaled_linear_fused says so (K <= 4096, N * K <=
+// 2^24): the fused launch. Otherwise the pre-scale into a buffer of the caching allocator, then the
+// plain linear (bit-identical to calling the two ops).
+Tensor int4_prescaled_linear(const Tensor& x, const Tensor& act_scale, const Tensor& packed_w,
+                             const Tensor& sz, int64_t group_size,
+                             const std::optional<Tensor>& bias) {
+  TORCH_CHECK(packed_w.dim() == 2 && packed_w.scalar_type() == at::kInt,
+              "packed weight must be a 2D int32 [N, K/8] tensor");
+  const int64_t N = packed_w.size(0), K = packed_w.size(1) * 8;
+  TORCH_CHECK(group_size == 32 || group_size == 64 || group_size == 128 || group_size == 256,
+              "qGroupSize must be 32, 64, 128, or 256");
+  TORCH_CHECK(K % group_size == 0, "K (", K, ") must be divisible by qGroupSize");
+  TORCH_CHECK(sz.scalar_type() == at::kBFloat16, "scales_and_zeros must be bfloat16");
+  TORCH_CHECK(sz.dim() == 3 && sz.size(0) == N && sz.size(1) == K / group_size && sz.size(2) == 2,
+              "scales_and_zeros must be [N, K/g, 2] = (", N, ", ", K / group_size, ", 2), got ",
+              sz.sizes());
+  const Tensor s = check_act_scale(x, act_scale, K, "int4_prescaled_linear");
+  TORCH_CHECK(packed_w.is_contiguous(), "packed_w must be contiguous");
+  TORCH_CHECK(sz.is_contiguous(), "scales_and_zeros must be contiguous");
+  check_device(x, packed_w, "packed_w");
+  check_device(x, sz, "scales_and_zeros");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options());
+  if (tao_int4wo_prescaled_linear_fused(M, N, K, b ? 1 : 0)) {
+    check_rc(tao_int4wo_prescaled_linear_bf16(cptr<uint16_t>(x2), cptr<uint16_t>(s),
+                                              cptr<uint32_t>(packed_w), cptr<uint16_t>(sz),
+                                              nullptr, mptr<uint16_t>(y), 1, N, K, group_size,
+                                              stream_of(x)),
+             "tao_int4wo_prescaled_linear_bf16");
+  } else if (M > 0) {
+    Tensor xs = at::empty({M, K}, x.options());
+    check_rc(tao_act_prescale_bf16(cptr<uint16_t>(x2), cptr<uint16_t>(s), mptr<uint16_t>(xs), M,
+                                   K, stream_of(x)),
+             "tao_act_prescale_bf16");
+    check_rc(tao_int4wo_linear_bf16(cptr<uint16_t>(xs), cptr<uint32_t>(packed_w),
+                                    cptr<uint16_t>(sz), b ? cptr<uint16_t>(*b) : nullptr,
+                                    mptr<uint16_t>(y), M, N, K, group_size, stream_of(x)),
+             "tao_int4wo_linear_bf16");
+  }
   return y.reshape(out_shape(x, N));
 }
 
@@ -680,6 +754,8 @@ TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
   m.impl("blockfp8_scaled_mm", &blockfp8_scaled_mm);
   m.impl("blockfp8_dyn_linear", &blockfp8_dyn_linear);
   m.impl("int4_weight_only_linear", &int4_weight_only_linear);
+  m.impl("act_prescale", &act_prescale);
+  m.impl("int4_prescaled_linear", &int4_prescaled_linear);
   m.impl("int8_weight_only_linear", &int8_weight_only_linear);
   m.impl("int8_quantize_per_token", &int8_quantize_per_token);
   m.impl("int8_scaled_mm", &int8_scaled_mm);
@@ -722,6 +798,11 @@ extern "C" const char* tao_torch_ops_served_mx(void) {
 extern "C" const char* tao_torch_ops_served_blockfp8(void) {
   return "blockfp8_quantize_act,blockfp8_quantize_weight,blockfp8_dequantize_weight,"
          "blockfp8_scaled_mm,blockfp8_dyn_linear";
+}
+
+// The activation pre-scale ops (AWQ) served here, a set of their own as well.
+extern "C" const char* tao_torch_ops_served_awq(void) {
+  return "act_prescale,int4_prescaled_linear";
 }
 
 // The MXFP4-weight ops served here, a set of their own as well.

@@ -35,6 +35,9 @@ _SIGNATURES = {
     "tao_profile_begin": [_int],
     "tao_profile_end": [_p, _int, _p],
     "tao_int4wo_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p],
+    "tao_act_prescale_bf16": [_p, _p, _p, _i64, _i64, _p],
+    "tao_int4wo_prescaled_linear_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p],
+    "tao_int4wo_prescaled_linear_fused": [_i64, _i64, _i64, _int],
     "tao_int4wo_linear_swiglu_bf16": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p],
     "tao_int4wo_linear_rope_kv_bf16": [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _i64,
                                        _i64, _i64, _i64, _i64, _p],

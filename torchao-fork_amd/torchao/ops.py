@@ -45,6 +45,13 @@ Operators:
     ``blockfp8_scaled_mm`` / ``blockfp8_dyn_linear`` — the blockwise float8 recipe (e4m3fn codes,
     fp32 scales per 1 x 128 activation block and 128 x 128 weight block, csrc/block_fp8.hip);
     replace the Triton kernels of prototype/blockwise_fp8_inference/blockwise_quantization.py.
+  * ``act_prescale`` — ``bf16(x / scale)`` over the input channels (IEEE fp32 division, one
+    rounding); replaces the division of ``WeightTensorWithLinearActivationScaleMetadata``
+    (quantization/linear_activation_scale.py:61-70), the AWQ / SmoothQuant equalization scale.
+  * ``int4_prescaled_linear`` — that division and ``int4_weight_only_linear`` from a bf16 input
+    (one token without a bias at K <= 4096 and N * K <= 2^24: one launch, the quotient formed
+    while the GEMV stages x in LDS), bit-identical to ``act_prescale`` ->
+    ``int4_weight_only_linear``.
 """
 
 import ctypes
@@ -147,6 +154,13 @@ lib_blockfp8.define(
     "-> Tensor")
 lib_blockfp8.define(
     "blockfp8_dyn_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias=None) -> Tensor")
+# The activation pre-scale ops (AWQ: torchao.prototype.awq, quantization/linear_activation_scale.py),
+# on a fragment of their own; opchecked in tests/test_gpu_awq.py. bf16 only.
+lib_awq = torch.library.Library("torchao", "FRAGMENT")
+lib_awq.define("act_prescale(Tensor x, Tensor scale) -> Tensor")
+lib_awq.define(
+    "int4_prescaled_linear(Tensor x, Tensor act_scale, Tensor packed_w, Tensor scales_and_zeros, "
+    "int group_size, Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -503,6 +517,89 @@ def _int4_linear_cuda(x, packed_w, scales_and_zeros, group_size, bias=None):
     with torch.cuda.device(x.device):
         _lib.call("tao_int4wo_linear_bf16", _ptr(x2), _ptr(packed_w), _ptr(scales_and_zeros),
                   _ptr(bias), _ptr(y), M, N, K, group_size, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
+# ---------------------------------------------------------------------------------------------
+# activation pre-scale (AWQ / SmoothQuant equalization scale)
+# ---------------------------------------------------------------------------------------------
+def _check_act_scale(x: Tensor, scale: Tensor, K: int, op: str):
+    torch._check(x.dtype is torch.bfloat16, lambda: f"{op} (HIP) needs bf16 x, got {x.dtype}")
+    torch._check(scale.dtype is torch.bfloat16,
+                 lambda: f"{op} (HIP) needs a bf16 scale, got {scale.dtype}")
+    torch._check(x.dim() >= 1 and x.size(-1) == K,
+                 lambda: f"x last dim {x.size(-1) if x.dim() else 0} != K {K}")
+    torch._check(scale.numel() == K,
+                 lambda: f"scale must have K = {K} elements, got {scale.numel()}")
+
+
+def _scale_row(scale: Tensor) -> Tensor:
+    s = scale.reshape(-1)
+    if not s.is_contiguous() or s.data_ptr() % 16:
+        s = s.contiguous()
+    return s
+
+
+@torch.library.register_fake("torchao::act_prescale")
+def _(x, scale):
+    K = scale.numel()
+    _check_act_scale(x, scale, K, "act_prescale")
+    torch._check(K % 8 == 0, lambda: f"act_prescale needs K % 8 == 0, got K = {K}")
+    return x.new_empty(x.shape)
+
+
+def _act_prescale_cuda(x, scale):
+    """bf16(x / scale) over the last dimension: IEEE fp32 division, one rounding (what
+    ``input_tensor / scale`` gives for bf16 operands, linear_activation_scale.py:61-70)."""
+    K = scale.numel()
+    _check_act_scale(x, scale, K, "act_prescale")
+    torch._check(K % 8 == 0, lambda: f"act_prescale needs K % 8 == 0, got K = {K}")
+    _same_device(x, scale=scale)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    s = _scale_row(scale)
+    y = torch.empty_like(x2)
+    with torch.cuda.device(x.device):
+        _lib.call("tao_act_prescale_bf16", _ptr(x2), _ptr(s), _ptr(y), x2.size(0), K, _stream(x))
+    return y.reshape(x.shape)
+
+
+@torch.library.register_fake("torchao::int4_prescaled_linear")
+def _(x, act_scale, packed_w, scales_and_zeros, group_size, bias=None):
+    N, K = _check_int4_weight(packed_w, scales_and_zeros, group_size)
+    _check_act_scale(x, act_scale, K, "int4_prescaled_linear")
+    return x.new_empty(_linear_out_shape(x, N))
+
+
+def _int4_prescaled_linear_cuda(x, act_scale, packed_w, scales_and_zeros, group_size, bias=None):
+    """The AWQ int4 linear from a bf16 activation. One token without a bias at K <= 4096 and
+    N * K <= 2^24 (tao_int4wo_prescaled_linear_fused): the division and the GEMV in one launch.
+    Otherwise act_prescale into a buffer of the caching allocator, then int4_weight_only_linear;
+    bit-identical to calling the two ops."""
+    N, K = _check_int4_weight(packed_w, scales_and_zeros, group_size)
+    _check_act_scale(x, act_scale, K, "int4_prescaled_linear")
+    _same_device(x, act_scale=act_scale, packed_w=packed_w, scales_and_zeros=scales_and_zeros,
+                 bias=bias)
+    _require_contig(packed_w, "packed_w")
+    _require_contig(scales_and_zeros, "scales_and_zeros")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    s = _scale_row(act_scale)
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if _lib.lib().tao_int4wo_prescaled_linear_fused(M, N, K, int(bias is not None)):
+            _lib.call("tao_int4wo_prescaled_linear_bf16", _ptr(x2), _ptr(s), _ptr(packed_w),
+                      _ptr(scales_and_zeros), _ptr(None), _ptr(y), 1, N, K, group_size, _stream(x))
+        elif M > 0:
+            xs = torch.empty_like(x2)
+            _lib.call("tao_act_prescale_bf16", _ptr(x2), _ptr(s), _ptr(xs), M, K, _stream(x))
+            _lib.call("tao_int4wo_linear_bf16", _ptr(xs), _ptr(packed_w), _ptr(scales_and_zeros),
+                      _ptr(bias), _ptr(y), M, N, K, group_size, _stream(x))
     return y.reshape(_linear_out_shape(x, N))
 
 
@@ -1238,6 +1335,7 @@ _native_served_float8_dyn: frozenset = frozenset()
 _native_served_mx: frozenset = frozenset()
 _native_served_mxfp4: frozenset = frozenset()
 _native_served_blockfp8: frozenset = frozenset()
+_native_served_awq: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -1263,6 +1361,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_blockfp8
         _served.restype = ctypes.c_char_p
         _native_served_blockfp8 = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_awq
+        _served.restype = ctypes.c_char_p
+        _native_served_awq = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -1296,6 +1397,11 @@ def native_dispatch_mxfp4() -> frozenset:
 def native_dispatch_blockfp8() -> frozenset:
     """The blockwise float8 ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_blockfp8
+
+
+def native_dispatch_awq() -> frozenset:
+    """The activation pre-scale (AWQ) ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_awq
 
 
 for _name, _fn in [
@@ -1352,6 +1458,12 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_blockfp8:
         lib_blockfp8.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("act_prescale", _act_prescale_cuda),
+    ("int4_prescaled_linear", _int4_prescaled_linear_cuda),
+]:
+    if _name not in _native_served_awq:
+        lib_awq.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")

@@ -6,6 +6,10 @@ from torchao.quantization.linear_activation_quantized_tensor import (
     LinearActivationQuantizedTensor,
     to_linear_activation_quantized,
 )
+from torchao.quantization.linear_activation_scale import (
+    WeightTensorWithLinearActivationScaleMetadata,
+    to_weight_tensor_with_linear_activation_scale_metadata,
+)
 from torchao.quantization.quant_api import (
     Float8DynamicActivationFloat8WeightConfig,
     Float8WeightOnlyConfig,
@@ -48,6 +52,8 @@ __all__ = [
     "float8_dynamic_activation_float8_weight",
     "LinearActivationQuantizedTensor",
     "to_linear_activation_quantized",
+    "WeightTensorWithLinearActivationScaleMetadata",
+    "to_weight_tensor_with_linear_activation_scale_metadata",
     "MappingType",
     "ZeroPointDomain",
     "choose_qparams_affine",

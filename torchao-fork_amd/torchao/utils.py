@@ -200,3 +200,13 @@ def _device_arch(index: int = 0) -> str:
 def check_cpu_version(device) -> bool:
     return torch.device(device).type == "cpu"
 
+
+
+class DummyModule(torch.nn.Module):
+    """A module holding only a weight (and bias), to run a config's module handler on a tensor
+    (reference utils.py ``DummyModule``; used by the AWQ search and convert)."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.weight = weight
+        self.bias = bias
