@@ -2,9 +2,13 @@
 
     hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S csrc/gemm_mfma.hip -o new/gemm_mfma.s
     python experiments/asm_same.py --old old/*.s --new new/*.s [--csv profiles/x.csv]
+        [--rename REGEX=REPL ...]
 
 Kernels are keyed by mangled name, whichever file of a side holds them (so a kernel may move to
-another source). Two things are compared per kernel: the lines from `<name>:` to its
+another source). --rename (repeatable) rewrites the old side's names with re.sub(REGEX, REPL, name)
+before keying, so that a renamed kernel is compared against its predecessor, e.g.
+    --rename '_ZN3tao12_GLOBAL__N_114mx_gemv_kernelI(.*)EEvNS0_10MxGemvArgsE=_ZN3tao18scaled_gemv_kernelINS_12_GLOBAL__N_15MxFmtE\\1EEvNT_4ArgsE'
+Two things are compared per kernel: the lines from `<name>:` to its
 `.Lfunc_end` (labels and instructions, comments dropped), and its `.amdhsa_kernel ...
 .end_amdhsa_kernel` block. Only what depends on a kernel's position in its file is normalised
 first: the function number inside local labels (.LBB<n>_<m>, .Lfunc_end<n>, .Lfunc_begin<n>) and
@@ -33,8 +37,8 @@ def _norm(lines):
     return out
 
 
-def side(paths):
-    """mangled name -> (file, normalised body, normalised descriptor block, stats)"""
+def side(paths, renames=()):
+    """mangled name (after renames) -> (file, normalised body, normalised descriptor block, stats)"""
     res = {}
     for path in paths:
         text = open(path).read()
@@ -43,11 +47,17 @@ def side(paths):
             name = m.group(1)
             body = re.search(rf"^{re.escape(name)}:[^\n]*\n(.*?)^\.Lfunc_end\d+:", text,
                              re.S | re.M)
+            ins, md = stats.get(name, ([], {}))
+            parts = [_norm(body.group(1).splitlines()) if body else None,
+                     _norm(m.group(2).splitlines())]
+            was = name
+            for rx, repl in renames:
+                name = rx.sub(repl, name)
+            if name != was:  # the kernel's own name inside its text (.section, .amdhsa_kernel)
+                parts = [p and [t.replace(was, name) for t in p] for p in parts]
             if name in res:
                 sys.exit(f"{name} is in both {res[name][0]} and {path}")
-            ins, md = stats.get(name, ([], {}))
-            res[name] = (os.path.basename(path), _norm(body.group(1).splitlines()) if body else None,
-                         _norm(m.group(2).splitlines()), (len(ins), md))
+            res[name] = (os.path.basename(path), parts[0], parts[1], (len(ins), md))
     return res
 
 
@@ -56,8 +66,11 @@ def main():
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--csv")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="rewrite the old side's kernel names before keying (repeatable)")
     a = ap.parse_args()
-    old, new = side(a.old), side(a.new)
+    renames = [(re.compile(rx), repl) for rx, repl in (r.split("=", 1) for r in a.rename)]
+    old, new = side(a.old, renames), side(a.new)
     rows = ["kernel,old_file,new_file,same,instructions,vgpr,sgpr,scratch"]
     bad = 0
     for name in sorted(set(old) | set(new)):

@@ -1,6 +1,8 @@
 // Stand-alone host program for the sanitizers: runs the host-side arithmetic of the float8
 // dynamic-activation linear (csrc/fp8_dyn_host.h: GEMV launch shape, fused-prologue sizing, route
-// choice) over a sweep of arguments and checks the invariants the kernel relies on. No GPU call.
+// choice; with a chunk width and token-scale bytes, the launch shape of all four formats of
+// csrc/scaled_gemv.h) over a sweep of arguments and checks the invariants the kernels rely on.
+// No GPU call.
 //   hipcc --offload-arch=gfx950 -O1 -g -Xarch_host -fsanitize=address,undefined \
 //     -Xarch_host -fno-sanitize-recover=all -I torchao-fork_amd/csrc \
 //     -fsanitize=address,undefined experiments/sanitize_fp8dyn_host.hip \
@@ -23,6 +25,46 @@ int set_error(int code, const char*, ...) { return code; }
       return 1;                                                          \
     }                                                                    \
   } while (0)
+
+// The formats of scaled_gemv.h as its launcher describes them to fp8dyn_launch_shape: the k in a
+// 16-B weight chunk, the k in a scale block and the bytes of one stored token scale (per-row
+// scales: none kept in LDS).
+struct Fmt {
+  int chunk_k, block_k, scale_size;
+};
+static const Fmt kFmt[4] = {
+    {16, 16, 0},   // fp8dyn: per-row scales
+    {16, 32, 1},   // mx: an E8M0 byte per 32 k
+    {32, 32, 1},   // mxfp4w: the same, e2m1 weight chunks of 32 k
+    {16, 128, 4},  // blockfp8: an fp32 per 128 k
+};
+
+// The expectation: what each format's own launcher computed before the four kernels became one,
+// restated from those sources. fp8dyn, mx and blockfp8 called the 16-k launch shape and mx /
+// blockfp8 added their scale bytes to its lds; mxfp4w re-derived the whole shape for 32-k chunks.
+struct OldShape {
+  int S, Wk, G, grid, threads, per;
+  size_t lds;
+};
+static OldShape old_shape(int f, int N, int K, int rpw, int mt, int wk, int g, bool fq) {
+  const int nchunk = f == 2 ? K / 32 : K / 16;
+  OldShape o{(nchunk + 63) / 64, 0, g, 0, 0, 0, 0};
+  o.Wk = wk < o.S ? wk : o.S;
+  while (o.G > 1 && o.Wk * o.G > 8) o.G >>= 1;
+  while (fq && (int64_t)64 * o.Wk * o.G * 8 * 16 < K && o.Wk * o.G * 2 <= 8) o.G *= 2;
+  const int rows_per_wg = o.G * rpw;
+  o.grid = (int)(((int64_t)N + rows_per_wg - 1) / rows_per_wg);
+  const int nw = o.G * o.Wk;
+  o.threads = 64 * nw;
+  o.lds = (size_t)nw * rpw * mt * sizeof(float);
+  if (fq) {
+    o.lds = (((size_t)nw * rpw * mt + 8 + 3) & ~(size_t)3) * sizeof(float) + (size_t)K;
+    if (f == 1 || f == 2) o.lds += (size_t)((K / 32 + 15) & ~15);
+    if (f == 3) o.lds += (size_t)((K / 128 * 4 + 15) & ~15);
+    o.per = (K / 8 + o.threads - 1) / o.threads;
+  }
+  return o;
+}
 
 int main() {
   using namespace tao;
@@ -75,6 +117,33 @@ int main() {
           CHECK(off % 16 == 0 && off + (size_t)K == L.lds);
           lds[off + K - 1] = 1;
         }
+  // scaled_gemv.h's one host path: for every format, grid / threads / lds / per (and S, Wk, G)
+  // equal what that format's own launcher computed before the kernels were merged (old_shape)
+  const int fKs[] = {32, 128, 1024, 1056, 1152, 4096, 4224, 14336, 32768, 65536};
+  for (int f = 0; f < 4; ++f)
+    for (int K : fKs)
+      for (int N : Ns)
+        for (const auto& s : shapes)
+          for (int fq = 0; fq < 2; ++fq)
+            for (int mt : {1, 2, 4, 8}) {
+              if (K % kFmt[f].block_k != 0 || (fq && mt != 1)) continue;
+              const int rpw = fq ? s[0] : 8 / mt > s[0] ? s[0] : 8 / mt;
+              const int sb = K / kFmt[f].block_k * kFmt[f].scale_size;
+              const Fp8DynLaunch L = fp8dyn_launch_shape(N, K, rpw, mt, s[1], s[2], fq != 0, 16,
+                                                         kFmt[f].chunk_k, sb);
+              const OldShape o = old_shape(f, N, K, rpw, mt, s[1], s[2], fq != 0);
+              ++cases;
+              CHECK(L.S == o.S && L.Wk == o.Wk && L.G == o.G);
+              CHECK(L.grid == o.grid && L.threads == o.threads && L.lds == o.lds);
+              if (fq) {
+                CHECK(L.per == o.per);
+                // the kernel's carve-up: the scales start right behind the K code bytes
+                std::vector<unsigned char> lds(L.lds);
+                const size_t off = (((size_t)L.Wk * L.G * rpw * mt + 8 + 3) & ~(size_t)3) * 4;
+                CHECK(off + (size_t)K + (size_t)sb <= L.lds);
+                lds[off + K + sb - 1] = 1;  // the last scale byte (or code byte) is inside
+              }
+            }
   for (long long M : {0LL, 1LL, 2LL, 4LL, 5LL, 8LL, 9LL, 2147483647LL})
     for (long long N : {1LL, 4096LL, 14336LL, 2147483647LL})
       for (long long K : {16LL, 4096LL, 14336LL, 268435456LL})

@@ -33,15 +33,15 @@
 //      128 x 128 tile.
 //   3. tao_blockfp8_dequant_weight: blockfp8_dequant_weight_kernel, float(code) * s in fp32, stored
 //      as fp32 or rounded once to bf16.
-//   4. tao_blockfp8_scaled_mm_bf16: blockfp8_gemv_kernel up to the crossover, the BlockFp8 instance
-//      of gemm_mfma_kernel above it.
+//   4. tao_blockfp8_scaled_mm_bf16: up to the crossover scaled_gemv_kernel (scaled_gemv.h) under
+//      the policy BlockFp8Fmt below, recorded as "blockfp8_gemv_kernel"; the BlockFp8 instance of
+//      gemm_mfma_kernel above it.
 //   5. tao_blockfp8_dyn_linear_bf16 (one token): 1 and 4 in one launch; the token is quantised per
 //      block into LDS (a block's scale depends on that block alone: no row-wide reduction), then the
 //      GEMV runs on the codes. Bit-identical to 1 -> 4.
 #include "blockfp8_block.h"
-#include "fp8_dyn_host.h"
+#include "scaled_gemv.h"
 #include "tao_gemm.h"
-#include "tao_gemv.h"
 
 namespace tao {
 namespace {
@@ -98,21 +98,6 @@ __global__ __launch_bounds__(256) void blockfp8_quantize_weight_kernel(
   if (t == 0) scale[(size_t)nb * gridDim.x + kb] = s;
 }
 
-// codes (2 sel, 2 sel + 1) of a dword -> bf16 pair, exact (every finite e4m3fn value is a bf16)
-template <bool HI>
-__device__ __forceinline__ uint32_t bf8_pair_bf16(uint32_t w) {
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-}
-// the 16 codes of a 16-B chunk -> 8 bf16 pairs (k, k + 1) in k order
-__device__ __forceinline__ void bf8_chunk_bf16(const uint4 v, uint32_t (&p)[8]) {
-  const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    p[2 * j] = bf8_pair_bf16<false>(d[j]);
-    p[2 * j + 1] = bf8_pair_bf16<true>(d[j]);
-  }
-}
-
 // One thread per 16 codes of the flat [N][K] run: out = float(code) * s[n / 128][k / 128].
 template <bool BF16>
 __global__ __launch_bounds__(256) void blockfp8_dequant_weight_kernel(
@@ -124,7 +109,7 @@ __global__ __launch_bounds__(256) void blockfp8_dequant_weight_kernel(
   const int kc = (int)(c - n * cpr);
   const float s = scale[(n >> 7) * (cpr >> 3) + (kc >> 3)];
   uint32_t p[8];
-  bf8_chunk_bf16(q[c], p);
+  e4m3_chunk_bf16(q[c], p);
   float f[16];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -148,178 +133,29 @@ __global__ __launch_bounds__(256) void blockfp8_dequant_weight_kernel(
 }
 
 // ---- GEMV ------------------------------------------------------------------------------------------
-struct BlockFp8GemvArgs {
-  const void* x;         // e4m3fn codes [M][K] (FQ: the bf16 token [K])
-  const float* xs;       // [M][K/128] (unused with FQ)
-  const uint4* w;        // [N][K/16] e4m3fn codes
-  const float* ws;       // [ceil(N/128)][K/128]
-  const uint16_t* bias;  // [N] bf16 or null
-  uint16_t* y;           // [M][N]
-  int M, N, K, Wk, G, S;
+// scaled_gemv_kernel's policy: fp32 scales per 128-k block, the weight's shared by 128 rows. A
+// lane's 16-B chunk is an eighth of a block; its fp32 partial sum enters the accumulator as
+// fma(partial, xs * ws, acc). The fused launch quantises the token per block (sixteen consecutive
+// threads hold one; the arithmetic of blockfp8_quantize_act_kernel).
+struct BlockFp8Fmt {
+  using Args = ScaledGemvArgs<float>;  // xs [M][K/128], ws [ceil(N/128)][K/128]
+  using Scale = float;
+  static constexpr const char* name = "blockfp8_gemv_kernel";
+  static constexpr const char* what = "blockfp8";
+  static constexpr int kChunkShift = 4, kBlockShift = 7;
+  static constexpr bool kRowScales = false, kFp4Weights = false;
+  // row N - 1 lies in scale row ceil(N/128) - 1: a clamped row reads inside the array
+  static __device__ __forceinline__ size_t scale_row(size_t nn) { return nn >> 7; }
+  static __device__ __forceinline__ float token_scale(const uint4 xv) {
+    return blockfp8_scale(blockfp8_amax16(fp8_amax8(xv, 0.f)));
+  }
+  static __device__ __forceinline__ uint2 token_codes(const uint4 xv, float s) {
+    return blockfp8_quant8(xv, s);
+  }
+  static __device__ __forceinline__ float add(float d, float xf, float wf, float acc) {
+    return __builtin_fmaf(d, xf * wf, acc);
+  }
 };
-
-// mx_gemv_kernel's decomposition (mx_fp8.hip) with 128-wide blocks and fp32 scales: a lane's 16-B
-// chunk c is an eighth of block c >> 3; its fp32 partial sum enters the accumulator as
-// fma(partial, xs * ws, acc). The weight codes are read once.
-// NPT > 0 (FQ, M == 1): x is the bf16 token, NPT 16-B pieces of it per thread (K <= 8 NPT T).
-template <int MT, int RPW, int NPT>
-__global__ __launch_bounds__(512) void blockfp8_gemv_kernel(BlockFp8GemvArgs a) {
-  constexpr bool FQ = NPT > 0;
-  static_assert(!FQ || MT == 1, "the fused quantisation is one token");
-  constexpr int V = RPW * MT;
-  // [G][Wk][V] fp32 partials | (FQ) the token's codes [K] | (FQ) its scales [K/128]
-  extern __shared__ float lds_f[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
-  const int wk = wave % a.Wk;
-  const int rg = wave / a.Wk;
-  const int row0 = (blockIdx.x * a.G + rg) * RPW;
-  const int K = a.K, N = a.N, S = a.S, Wk = a.Wk;
-  const int nchunk = K >> 4;  // 16-B (16-k) chunks per row; chunk c lies in block c >> 3
-  const int nblk = K >> 7;
-  const int nw = a.G * a.Wk;
-  uint4* xl = reinterpret_cast<uint4*>(lds_f + ((nw * V + 8 + 3) & ~3));
-  float* xsl = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(xl) + K);
-
-  float acc[RPW][MT];
-#pragma unroll
-  for (int r = 0; r < RPW; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[r][m] = 0.f;
-
-  // a slice's codes and the scale of the lane's block; rows, scale rows and chunks clamped in
-  // bounds (row N - 1 lies in scale row ceil(N/128) - 1)
-  uint4 wv[RPW];
-  float wsf[RPW];
-  auto load_w = [&](int s) __attribute__((always_inline)) {
-    const int c = s * 64 + lane;
-    const int cc = c < nchunk ? c : nchunk - 1;
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      const int n = row0 + r;
-      const size_t nn = (size_t)(n < N ? n : N - 1);
-      wv[r] = ld_nt_u4(a.w + nn * nchunk + cc);
-      wsf[r] = a.ws[(nn >> 7) * nblk + (cc >> 3)];
-    }
-  };
-
-  if constexpr (FQ) {
-    // The token's pieces are loaded before the first slice's weights (loads retire in issue order),
-    // so the quantisation into LDS runs under the weight loads' latency. Sixteen consecutive
-    // threads hold one block (K / 8 is a multiple of 16, so a group is whole or clamped as a whole).
-    const uint4* xr = reinterpret_cast<const uint4*>(a.x);
-    const int nvec = K >> 3;
-    uint4 xv[NPT];
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int i = threadIdx.x + u * (int)blockDim.x;
-      xv[u] = xr[i < nvec ? i : nvec - 1];
-    }
-    load_w(wk);  // Wk <= S: every wave owns a slice
-    uint2* xq = reinterpret_cast<uint2*>(xl);
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int i = threadIdx.x + u * (int)blockDim.x;
-      const float s = blockfp8_scale(blockfp8_amax16(fp8_amax8(xv[u], 0.f)));
-      if (i < nvec) {
-        xq[i] = blockfp8_quant8(xv[u], s);
-        if ((i & 15) == 0) xsl[i >> 4] = s;
-      }
-    }
-    __syncthreads();
-  } else {
-    load_w(wk);
-  }
-
-  for (int s = wk; s < S; s += Wk) {
-    if (s != wk) load_w(s);
-    const int c = s * 64 + lane;
-    const bool cval = c < nchunk;
-    const int cc = cval ? c : nchunk - 1;
-    if (cval) {  // a lane past the row's last chunk skips the math
-      uint32_t wp[RPW][8];
-#pragma unroll
-      for (int r = 0; r < RPW; ++r) bf8_chunk_bf16(wv[r], wp[r]);
-      // x is streamed one row of M at a time
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        uint4 xc;
-        float xf;
-        if constexpr (FQ) {
-          xc = xl[cc];
-          xf = xsl[cc >> 3];
-        } else {
-          const size_t mm = (size_t)(m < a.M ? m : a.M - 1);
-          xc = reinterpret_cast<const uint4*>(a.x)[mm * nchunk + cc];
-          xf = a.xs[mm * nblk + (cc >> 3)];
-        }
-        uint32_t xp[8];
-        bf8_chunk_bf16(xc, xp);
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-          float d = 0.f;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) d = dot2_bf16(xp[i], wp[r][i], d);
-          acc[r][m] = __builtin_fmaf(d, xf * wsf[r], acc[r][m]);
-        }
-      }
-    }
-  }
-
-  float v[V];
-#pragma unroll
-  for (int r = 0; r < RPW; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) v[r * MT + m] = acc[r][m];
-  wave_reduce_scatter<V>(v, lane);
-
-  const WgTotal<float> t = wg_combine<V>(v[0], lds_f, lane, wk, rg, Wk);
-  if (t.writer) {
-    const int r = t.widx / MT, m = t.widx % MT;
-    const int n = row0 + r;
-    if (n < N && m < a.M) {
-      float o = t.total;
-      if (a.bias != nullptr) o = o + bf16_to_f32(a.bias[n]);
-      a.y[(size_t)m * N + n] = f32_to_bf16(o);
-    }
-  }
-}
-
-template <int MT, int RPW, int NPT>
-int launch_gemv_npt(BlockFp8GemvArgs a, int grid, int threads, size_t lds, hipStream_t stream) {
-  launch((blockfp8_gemv_kernel<MT, RPW, NPT>), dim3(grid), dim3(threads), lds, stream, a);
-  return check_launch("blockfp8_gemv_kernel");
-}
-
-// fp8dyn_gemv_kernel's launch shape (fp8_dyn_host.h); the fused launch keeps the token's K / 128
-// scales behind its codes.
-template <int MT, int RPW, bool FQ>
-int launch_gemv(BlockFp8GemvArgs a, int wk, int g, hipStream_t stream) {
-  const Fp8DynLaunch L = fp8dyn_launch_shape(a.N, a.K, RPW, MT, wk, g, FQ);
-  a.S = L.S;
-  a.Wk = L.Wk;
-  a.G = L.G;
-  if constexpr (!FQ) {
-    return launch_gemv_npt<MT, RPW, 0>(a, L.grid, L.threads, L.lds, stream);
-  } else {
-    const size_t lds = L.lds + (size_t)((a.K / 128 * 4 + 15) & ~15);
-    if (L.per <= 1) return launch_gemv_npt<MT, RPW, 1>(a, L.grid, L.threads, lds, stream);
-    if (L.per <= 2) return launch_gemv_npt<MT, RPW, 2>(a, L.grid, L.threads, lds, stream);
-    if (L.per <= 4) return launch_gemv_npt<MT, RPW, 4>(a, L.grid, L.threads, lds, stream);
-    if (L.per <= 8) return launch_gemv_npt<MT, RPW, 8>(a, L.grid, L.threads, lds, stream);
-    if (L.per <= 16) return launch_gemv_npt<MT, RPW, 16>(a, L.grid, L.threads, lds, stream);
-    TAO_CHECK_ARG(false, "blockfp8 dyn linear: K (%d) too long for the token prologue", a.K);
-  }
-  return TAO_OK;
-}
-
-// mx_gemv's shapes (mx_fp8.hip)
-int blockfp8_gemv(BlockFp8GemvArgs a, hipStream_t stream) {
-  if (a.M <= 1) return launch_gemv<1, 4, false>(a, 8, 1, stream);
-  if (a.M <= 2) return launch_gemv<2, 4, false>(a, 8, 8, stream);
-  if (a.M <= 4) return launch_gemv<4, 2, false>(a, 8, 8, stream);
-  return launch_gemv<8, 1, false>(a, 8, 8, stream);
-}
 
 int check_sizes(const char* what, int64_t M, int64_t N, int64_t K) {
   TAO_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "%s: negative size", what);
@@ -407,9 +243,9 @@ int tao_blockfp8_scaled_mm_bf16(const uint8_t* xq, const float* xs, const uint8_
   TAO_CHECK_ALIGN(xs, 4, "xs");
   TAO_CHECK_ALIGN(ws, 4, "ws");
   if (blockfp8_takes_gemv(M, N, K)) {
-    BlockFp8GemvArgs a{xq, xs, reinterpret_cast<const uint4*>(wq), ws, bias, y,
-                       (int)M, (int)N, (int)K, 0, 0, 0};
-    return blockfp8_gemv(a, as_stream(stream));
+    const BlockFp8Fmt::Args a{xq, xs, reinterpret_cast<const uint4*>(wq), ws, bias, y,
+                              (int)M, (int)N, (int)K, 0, 0, 0};
+    return scaled_gemv<BlockFp8Fmt>(a, as_stream(stream));
   }
   return blockfp8_scaled_mm_launch(xq, xs, wq, ws, bias, y, (int)M, (int)N, (int)K,
                                    as_stream(stream));
@@ -431,9 +267,9 @@ int tao_blockfp8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const flo
   TAO_CHECK_ALIGN(x, 16, "x");
   TAO_CHECK_ALIGN(wq, 16, "wq");
   TAO_CHECK_ALIGN(ws, 4, "ws");
-  BlockFp8GemvArgs a{x, nullptr, reinterpret_cast<const uint4*>(wq), ws, bias, y,
-                     1, (int)N, (int)K, 0, 0, 0};
-  return launch_gemv<1, 8, true>(a, 4, 2, as_stream(stream));
+  const BlockFp8Fmt::Args a{x, nullptr, reinterpret_cast<const uint4*>(wq), ws, bias, y,
+                            1, (int)N, (int)K, 0, 0, 0};
+  return scaled_gemv_fused<BlockFp8Fmt>(a, as_stream(stream));
 }
 
 }  // extern "C"

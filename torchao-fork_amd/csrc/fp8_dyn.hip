@@ -15,7 +15,7 @@
 //      _linear_fp8_act_fp8_weight_impl (torchao/dtypes/floatx/float8_layout.py:329-367).
 //      M above the GEMV crossover: the Fp8Dyn instance of the shared skinny-GEMM template
 //      (gemm_mfma.hip) on v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales; M at or below
-//      it: fp8dyn_gemv_kernel below.
+//      it: the decode GEMV (below).
 //   2. tao_fp8_dyn_linear_bf16 (one token): the activation quantisation
 //      (_input_activation_quant_func_fp8 -> tao_fp8_quantize_rows_bf16's arithmetic, fp8_quant_row.h)
 //      and the GEMV in one launch, as tao_int8_dyn_linear_bf16 does for int8: every workgroup
@@ -27,16 +27,13 @@
 //      the token before its quantisation and a SwiGLU or RoPE + KV-write row-pair epilogue
 //      (fp8dq_decode_kernel below).
 //
-// fp8dyn_gemv_kernel: the byte-weight decomposition of tao_gemv.h (a slice is 1024 k of one row).
-// Both code streams are decoded in hardware: v_cvt_scalef32_pk_bf16_fp8 with scale 1.0 is exact
-// (every finite e4m3fn value is a bf16 number), then one v_dot2c_f32_bf16 per code pair into an
-// fp32 accumulator, as in fp8wo_gemv_kernel. A lane past the row's last 16-B chunk loaded clamped,
-// in-bounds addresses and skips the math: either side's codes may be NaN, which 0 * w would not
-// cancel.
-#include "fp8_dyn_host.h"
-#include "fp8_quant_row.h"
+// The decode GEMV of 1 and 2 is scaled_gemv_kernel (scaled_gemv.h: decomposition, hardware decode
+// of both code streams, skipped tail lanes, the fused prologue's order of loads) under the policy
+// Fp8DynFmt below, recorded as "fp8dyn_gemv_kernel". This format's own part: a lane's fp32 partial
+// sums are added unscaled (a slice is 1024 k of one row); the two scales meet the workgroup's total
+// in the epilogue; the fused launch takes the token's amax across the whole row, through LDS.
+#include "scaled_gemv.h"
 #include "tao_gemm.h"
-#include "tao_gemv.h"
 
 // The epilogue is specified as separate fp32 roundings (mul, mul, add): no fused multiply-add.
 #pragma clang fp contract(off)
@@ -47,211 +44,36 @@ TAO_DECODE_ERROR_WORD(fp8dyn_decode_status)
 
 namespace {
 
-struct Fp8DynGemvArgs {
-  const void* x;         // e4m3fn codes [M][K] (FQ: the bf16 token [K])
-  const float* xs;       // [M] fp32 per-token scales (unused with FQ)
-  const uint4* w;        // [N][K/16] e4m3fn codes
-  const float* ws;       // [N] fp32
-  const uint16_t* bias;  // [N] bf16 or null
-  uint16_t* y;           // [M][N]
-  int M, N, K, Wk, G, S;
+// The per-row policy of scaled_gemv_kernel: one fp32 scale per token and per weight row, met with
+// the total in the epilogue (under this file's contract(off): two roundings, no fma with the bias).
+struct Fp8DynFmt {
+  using Args = ScaledGemvArgs<float>;  // xs [M], ws [N]
+  using Scale = float;
+  static constexpr const char* name = "fp8dyn_gemv_kernel";
+  static constexpr const char* what = "fp8";
+  static constexpr int kChunkShift = 4;
+  static constexpr bool kRowScales = true, kFp4Weights = false;
+  static constexpr int kBlockShift = 0;  // no blocks
+  static __device__ __forceinline__ float row_scaled(float total, float xs, float ws) {
+    return (total * xs) * ws;
+  }
 };
 
-// codes (2 sel, 2 sel + 1) of a dword -> bf16 pair, exact; NaN codes (0x7F, 0xFF) stay NaN
-template <bool HI>
-__device__ __forceinline__ uint32_t fp8_pair_bf16(uint32_t w) {
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-}
-// the 16 codes of a 16-B chunk -> 8 bf16 pairs (k, k + 1) in k order
-__device__ __forceinline__ void fp8_chunk_bf16(const uint4 v, uint32_t (&p)[8]) {
-  const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    p[2 * j] = fp8_pair_bf16<false>(d[j]);
-    p[2 * j + 1] = fp8_pair_bf16<true>(d[j]);
-  }
-}
-
-// NPT > 0 (FQ, M == 1): x is the bf16 token, NPT 16-B pieces of it per thread (K <= 8 NPT T).
-template <int MT, int RPW, int NPT>
-__global__ __launch_bounds__(512) void fp8dyn_gemv_kernel(Fp8DynGemvArgs a) {
-  constexpr bool FQ = NPT > 0;
-  static_assert(!FQ || MT == 1, "the fused quantisation is per token, M == 1");
-  constexpr int V = RPW * MT;
-  // [G][Wk][V] fp32 partials | (FQ) [8] wave maxima | (FQ) the token's codes [K]
-  extern __shared__ float lds_f[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
-  const int wk = wave % a.Wk;
-  const int rg = wave / a.Wk;
-  const int row0 = (blockIdx.x * a.G + rg) * RPW;
-  const int K = a.K, N = a.N, S = a.S, Wk = a.Wk;
-  const int nchunk = K >> 4;  // 16-B (16-k) chunks per row
-  const int nw = a.G * a.Wk;
-  float* wmax = lds_f + nw * V;
-  uint4* xl = reinterpret_cast<uint4*>(lds_f + ((nw * V + 8 + 3) & ~3));
-
-  float acc[RPW][MT];
-#pragma unroll
-  for (int r = 0; r < RPW; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[r][m] = 0.f;
-
-  uint4 wv[RPW];
-  auto load_w = [&](int s) __attribute__((always_inline)) {
-    const int c = s * 64 + lane;
-    const int cc = c < nchunk ? c : nchunk - 1;
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      const int n = row0 + r;
-      wv[r] = ld_nt_u4(a.w + (size_t)(n < N ? n : N - 1) * nchunk + cc);
-    }
-  };
-
-  float sx[MT];
-  if constexpr (FQ) {
-    // The token's pieces are loaded BEFORE the first slice's weights: vector loads retire in
-    // issue order, so the wait for x does not wait for the weights, and the amax, the barriers
-    // and the quantisation into LDS run under the weight loads' latency.
-    const uint4* xr = reinterpret_cast<const uint4*>(a.x);
-    const int nvec = K >> 3;
-    uint4 xv[NPT];
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int i = threadIdx.x + u * (int)blockDim.x;
-      xv[u] = xr[i < nvec ? i : nvec - 1];  // clamped duplicates do not change the max
-    }
-    load_w(wk);  // Wk <= S: every wave owns a slice
-    float m = 0.f;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) m = fp8_amax8(xv[u], m);
-    m = wave_max(m);
-    if (lane == 0) wmax[wave] = m;
-    __syncthreads();
-    float amax = wmax[0];
-    for (int w = 1; w < nw; ++w) amax = fmaxf(amax, wmax[w]);
-    const float st = fp8_row_scale(amax);
-    uint2* xq = reinterpret_cast<uint2*>(xl);
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int i = threadIdx.x + u * (int)blockDim.x;
-      if (i < nvec) xq[i] = fp8_quant8(xv[u], st);
-    }
-    __syncthreads();
-    sx[0] = st;
-  } else {
-    load_w(wk);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) sx[m] = a.xs[m < a.M ? m : a.M - 1];
-  }
-
-  for (int s = wk; s < S; s += Wk) {
-    if (s != wk) load_w(s);
-    const int c = s * 64 + lane;
-    const bool cval = c < nchunk;
-    const int cc = cval ? c : nchunk - 1;
-    if (cval) {
-      uint32_t wp[RPW][8];
-#pragma unroll
-      for (int r = 0; r < RPW; ++r) fp8_chunk_bf16(wv[r], wp[r]);
-      // x is streamed one row of M at a time
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        uint4 xc;
-        if constexpr (FQ) {
-          xc = xl[cc];
-        } else {
-          const int mm = m < a.M ? m : a.M - 1;
-          xc = reinterpret_cast<const uint4*>(a.x)[(size_t)mm * nchunk + cc];
-        }
-        uint32_t xp[8];
-        fp8_chunk_bf16(xc, xp);
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-          float d = 0.f;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) d = dot2_bf16(xp[i], wp[r][i], d);
-          acc[r][m] += d;
-        }
-      }
-    }
-  }
-
-  float v[V];
-#pragma unroll
-  for (int r = 0; r < RPW; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) v[r * MT + m] = acc[r][m];
-  wave_reduce_scatter<V>(v, lane);
-
-  const WgTotal<float> t = wg_combine<V>(v[0], lds_f, lane, wk, rg, Wk);
-  if (t.writer) {
-    const int r = t.widx / MT, m = t.widx % MT;
-    const int n = row0 + r;
-    if (n < N && m < a.M) {
-      // fp32: the sum times the token's scale, times the row's scale, plus the bias; one rounding
-      float xsm = sx[0];
-#pragma unroll
-      for (int i = 1; i < MT; ++i) xsm = (m == i) ? sx[i] : xsm;
-      float o = (t.total * xsm) * a.ws[n];
-      if (a.bias != nullptr) o = o + bf16_to_f32(a.bias[n]);
-      a.y[(size_t)m * N + n] = f32_to_bf16(o);
-    }
-  }
-}
-
-template <int MT, int RPW, int NPT>
-int launch_gemv_npt(Fp8DynGemvArgs a, int grid, int threads, size_t lds, hipStream_t stream) {
-  launch((fp8dyn_gemv_kernel<MT, RPW, NPT>), dim3(grid), dim3(threads), lds, stream, a);
-  return check_launch("fp8dyn_gemv_kernel");
-}
-
-template <int MT, int RPW, bool FQ>
-int launch_gemv(Fp8DynGemvArgs a, int wk, int g, hipStream_t stream) {
-  const Fp8DynLaunch L = fp8dyn_launch_shape(a.N, a.K, RPW, MT, wk, g, FQ);
-  a.S = L.S;
-  a.Wk = L.Wk;
-  a.G = L.G;
-  if constexpr (!FQ) {
-    return launch_gemv_npt<MT, RPW, 0>(a, L.grid, L.threads, L.lds, stream);
-  } else {
-    if (L.per <= 1) return launch_gemv_npt<MT, RPW, 1>(a, L.grid, L.threads, L.lds, stream);
-    if (L.per <= 2) return launch_gemv_npt<MT, RPW, 2>(a, L.grid, L.threads, L.lds, stream);
-    if (L.per <= 4) return launch_gemv_npt<MT, RPW, 4>(a, L.grid, L.threads, L.lds, stream);
-    if (L.per <= 8) return launch_gemv_npt<MT, RPW, 8>(a, L.grid, L.threads, L.lds, stream);
-    if (L.per <= 16) return launch_gemv_npt<MT, RPW, 16>(a, L.grid, L.threads, L.lds, stream);
-    TAO_CHECK_ARG(false, "fp8 dyn linear: K (%d) too long for the token prologue", a.K);
-  }
-  return TAO_OK;
-}
-
-// M == 1 on ready-made codes: rows per wave 4, Wk = min(S, 8), one row group (fp8wo_gemv_kernel's
-// default shape). The fused launch: 8 rows per wave, 4 waves along K, 2 row groups. Every
-// workgroup quantises the whole token (true fp32 divisions, for the byte-exact codes), so fewer,
-// larger workgroups pay: 9.1 -> 7.1 us at 4096^2, 20.4 -> 14.2 us at 14336 x 4096, best or within
-// 4% of the best of ten shapes on the four README shapes (profiles/fp8dyn_fused_shape_ab.jsonl).
-// Both are overridden by tao_tune_fp8_gemv.
+// M == 1, both overridden by tao_tune_fp8_gemv: on ready-made codes scaled_gemv's shape, the fused
+// launch scaled_gemv_fused's.
 template <bool FQ>
-int gemv_m1(Fp8DynGemvArgs a, hipStream_t stream) {
+int gemv_m1(const Fp8DynFmt::Args& a, hipStream_t stream) {
   const int rpw = tuning().fp8_rpw > 0 ? tuning().fp8_rpw : (FQ ? 8 : 4);
   const int wk = tuning().fp8_wk > 0 ? tuning().fp8_wk : (FQ ? 4 : 8);
   const int g = tuning().fp8_g > 0 ? tuning().fp8_g : (FQ ? 2 : 1);
-  if (rpw == 2) return launch_gemv<1, 2, FQ>(a, wk, g, stream);
-  if (rpw == 8) return launch_gemv<1, 8, FQ>(a, wk, g, stream);
-  return launch_gemv<1, 4, FQ>(a, wk, g, stream);
-}
-
-// M > 1 keeps V = RPW * MT = 8 partials per lane, 8 waves per workgroup
-int fp8dyn_gemv(Fp8DynGemvArgs a, hipStream_t stream) {
-  if (a.M <= 1) return gemv_m1<false>(a, stream);
-  if (a.M <= 2) return launch_gemv<2, 4, false>(a, 8, 8, stream);
-  if (a.M <= 4) return launch_gemv<4, 2, false>(a, 8, 8, stream);
-  return launch_gemv<8, 1, false>(a, 8, 8, stream);
+  if (rpw == 2) return scaled_gemv_launch<Fp8DynFmt, 1, 2, FQ>(a, wk, g, stream);
+  if (rpw == 8) return scaled_gemv_launch<Fp8DynFmt, 1, 8, FQ>(a, wk, g, stream);
+  return scaled_gemv_launch<Fp8DynFmt, 1, 4, FQ>(a, wk, g, stream);
 }
 
 // ---- decode-step fusions of the one-token launch (tao_fp8dq_decode_bf16) ---------------------
-// fp8dyn_gemv_kernel's FQ path (one token, quantised per row inside every workgroup) as a sibling
-// kernel with the fusions of tao_gemv.h: NORM, the RMSNorm of the token
+// scaled_gemv_kernel's fused path under Fp8DynFmt (one token, quantised per row inside every
+// workgroup) as a sibling kernel with the fusions of tao_gemv.h: NORM, the RMSNorm of the token
 // before its quantisation (rmsnorm_kernel's two roundings, then amax / scale / codes on the
 // normalised bf16 values: the bytes tao_rmsnorm_bf16 -> tao_fp8_quantize_rows_bf16 produce up to
 // the norm's fp32 sum order), and the row-pair epilogues on the linear's own bf16 output
@@ -347,11 +169,11 @@ __global__ __launch_bounds__(512) void fp8dq_decode_kernel(Fp8DqDecodeArgs a) {
     const int c = s * 64 + lane;
     if (c < nchunk) {  // tail lanes skip the math: clamped codes may be NaN
       uint32_t xp[8];
-      fp8_chunk_bf16(xl[c], xp);
+      e4m3_chunk_bf16(xl[c], xp);
 #pragma unroll
       for (int r = 0; r < RPW; ++r) {
         uint32_t wp[8];
-        fp8_chunk_bf16(wv[r], wp);
+        e4m3_chunk_bf16(wv[r], wp);
         float d = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) d = dot2_bf16(xp[i], wp[i], d);
@@ -438,9 +260,10 @@ int tao_fp8_scaled_mm_bf16(const uint8_t* xq, const float* xs, const uint8_t* wq
   TAO_CHECK_ALIGN(xs, 4, "xs");
   TAO_CHECK_ALIGN(ws, 4, "ws");
   if (fp8dyn_takes_gemv(M, N, K)) {
-    Fp8DynGemvArgs a{xq, xs, reinterpret_cast<const uint4*>(wq), ws, bias, y,
-                     (int)M, (int)N, (int)K, 0, 0, 0};
-    return fp8dyn_gemv(a, as_stream(stream));
+    const Fp8DynFmt::Args a{xq, xs, reinterpret_cast<const uint4*>(wq), ws, bias, y,
+                            (int)M, (int)N, (int)K, 0, 0, 0};
+    if (M <= 1) return gemv_m1<false>(a, as_stream(stream));
+    return scaled_gemv<Fp8DynFmt>(a, as_stream(stream));
   }
   return fp8_scaled_mm_launch(xq, xs, wq, ws, bias, y, (int)M, (int)N, (int)K, as_stream(stream));
 }
@@ -460,8 +283,8 @@ int tao_fp8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const float* w
   TAO_CHECK_ALIGN(x, 16, "x");
   TAO_CHECK_ALIGN(wq, 16, "wq");
   TAO_CHECK_ALIGN(ws, 4, "ws");
-  Fp8DynGemvArgs a{x, nullptr, reinterpret_cast<const uint4*>(wq), ws, bias, y,
-                   1, (int)N, (int)K, 0, 0, 0};
+  const Fp8DynFmt::Args a{x, nullptr, reinterpret_cast<const uint4*>(wq), ws, bias, y,
+                          1, (int)N, (int)K, 0, 0, 0};
   return gemv_m1<true>(a, as_stream(stream));
 }
 

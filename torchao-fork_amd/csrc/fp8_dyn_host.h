@@ -1,5 +1,6 @@
-// Host-side arithmetic of the float8 dynamic-activation linear (fp8_dyn.hip, gemm_mfma.hip): the
-// GEMV launch shape with the fused prologue's token-piece count, and the GEMV / MFMA route choice.
+// Host-side arithmetic of the float8-activation linears (scaled_gemv.h, fp8_dyn.hip,
+// gemm_mfma.hip): the GEMV launch shape with the fused prologue's token-piece count, for every
+// format of scaled_gemv.h, and the per-row format's GEMV / MFMA route choice.
 // Plain functions of their arguments, so that a stand-alone host program can run them under the
 // sanitizers (experiments/sanitize_fp8dyn_host.hip). Internal header.
 #pragma once
@@ -15,11 +16,14 @@ struct Fp8DynLaunch {
 
 // rpw rows per wave, mt tokens per lane set, (wk, g) the wanted waves along K and row groups;
 // fq: the fused one-token launch (the token's codes live in LDS behind the partials); max_per:
-// the most token pieces a thread of the kernel to be launched holds (fp8dyn_gemv_kernel 16; the
-// decode kernel 8, and 4 with the RMSNorm, whose weight pieces sit beside the token's)
+// the most token pieces a thread of the kernel to be launched holds (scaled_gemv_kernel 16; the
+// decode kernel 8, and 4 with the RMSNorm, whose weight pieces sit beside the token's); chunk_k:
+// the k in one 16-B weight chunk (16 e4m3fn codes, 32 e2m1 codes); scale_bytes: the token's block
+// scales, which a fused launch keeps behind the codes (rounded up to whole 16 B)
 static inline Fp8DynLaunch fp8dyn_launch_shape(int N, int K, int rpw, int mt, int wk, int g,
-                                               bool fq, int max_per = 16) {
-  const GemvLaunchShape sh = gemv_launch_shape(K / 16, wk, g);
+                                               bool fq, int max_per = 16, int chunk_k = 16,
+                                               int scale_bytes = 0) {
+  const GemvLaunchShape sh = gemv_launch_shape(K / chunk_k, wk, g);
   Fp8DynLaunch L{sh.S, sh.Wk, sh.G, 0, 0, 0, 0};
   // fq: the token must fit the workgroup's registers (K <= 8 x max_per pieces x threads); row
   // groups are added while they fit 8 waves
@@ -30,7 +34,8 @@ static inline Fp8DynLaunch fp8dyn_launch_shape(int N, int K, int rpw, int mt, in
   L.threads = 64 * nw;
   L.lds = (size_t)nw * rpw * mt * sizeof(float);
   if (fq) {
-    L.lds = (((size_t)nw * rpw * mt + 8 + 3) & ~(size_t)3) * sizeof(float) + (size_t)K;
+    L.lds = (((size_t)nw * rpw * mt + 8 + 3) & ~(size_t)3) * sizeof(float) + (size_t)K +
+            (size_t)((scale_bytes + 15) & ~15);
     L.per = (K / 8 + L.threads - 1) / L.threads;
   }
   return L;

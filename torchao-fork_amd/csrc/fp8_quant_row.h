@@ -1,5 +1,6 @@
 // Per-row e4m3fn quantisation arithmetic, shared by the row quantizer (fp8_quantize.hip) and the
-// one-token prologue of the float8 dynamic-activation GEMV (fp8_dyn.hip) so that both produce the
+// one-token prologues of the float8 dynamic-activation GEMVs (scaled_gemv.h with row scales,
+// fp8dq_decode_kernel in fp8_dyn.hip) so that all produce the
 // same bytes. Internal device header. The formulas are fp8_quantize.hip's header comment.
 #pragma once
 

@@ -1,5 +1,5 @@
-// The GEMV skeleton shared by the weight-only decode kernels (int4_gemv.hip, int8_gemv.hip,
-// int8_dyn.hip, fp8_gemv.hip). Internal header.
+// The GEMV skeleton shared by the decode kernels (int4_gemv.hip, int8_gemv.hip, int8_dyn.hip,
+// fp8_gemv.hip, scaled_gemv.h). Internal header.
 //
 // Work decomposition, common to all of them:
 //   * a "slice" is one 1-KiB wave load of one weight row: 64 lanes x 16 B (1024 k of int8 / fp8
@@ -22,6 +22,14 @@
 //     whether tail lanes skip it, the scale type and the final rounding), wo8_decode_shape (the
 //     launch shape as a plain function of N, K, the format's wanted shape and the norm; the two
 //     formats' rules are int8_decode_want / fp8_decode_want) and wo8_decode (checks, dispatch).
+// The float8-activation linears (fp8_dyn.hip, mx_fp8.hip, mx_fp4.hip, block_fp8.hip) share one
+// kernel and one host path at every M, in scaled_gemv.h: scaled_gemv_kernel over a format policy
+// (Fp8DynFmt, MxFmt, Mx4Fmt, BlockFp8Fmt, each in its format's file). A policy supplies where the
+// scales live (per row, or per block with the weight's scale row), how a token piece finds its
+// block's scale and codes in the fused one-token launch, how a chunk's partial sum enters the
+// accumulator (or the total meets the row scales), and for e2m1 weights the block arithmetic;
+// launcher, token-piece ladder and M dispatcher are scaled_gemv_launch / scaled_gemv, the launch
+// shape fp8dyn_launch_shape (fp8_dyn_host.h).
 #pragma once
 
 #include <type_traits>
