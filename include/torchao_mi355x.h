@@ -354,6 +354,40 @@ int tao_int8_dyn_linear_bf16(const uint16_t* x, const int8_t* wq, const uint16_t
                              const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                              void* stream);
 
+/* SmoothQuant activation quantization of x [M][K] bf16 in one launch: t = bf16(x / smooth)
+ * (tao_act_prescale_bf16's bits; smooth bf16 [K]; t is never written), then
+ *   act_scale == NULL (dynamic): s[m] = max(bf16(amax(|t[m]|) / 127), 2^-7), the default eps of
+ *     choose_qparams_affine for bf16, NOT the 1e-5 of tao_int8_quant_per_token;
+ *   act_scale != NULL (static): s[m] = act_scale[0], a per-tensor bf16 scale in device memory,
+ *     written to every row of scale so tao_int8_scaled_mm_bf16 takes it as it is;
+ *   q = clamp(rne(bf16(t * bf16(1/s))), -127, 127) (values past the calibrated range saturate).
+ * Replaces the division of linear_activation_scale.py:61-70 followed by
+ * _ActQuantizer.dynamic_quantize / .static_quantize (torchao/prototype/smoothquant/api.py:133-155:
+ * to_affine_quantized_intx / to_affine_quantized_intx_static, ~8 eager kernels).
+ * K % 16 == 0, K <= 65536; x, smooth 16-B aligned, q 8-B aligned; q int8 [M][K], scale bf16 [M]. */
+int tao_int8_smooth_quant_bf16(const uint16_t* x, const uint16_t* smooth,
+                               const uint16_t* act_scale, int8_t* q, uint16_t* scale, int64_t M,
+                               int64_t K, void* stream);
+
+/* One token (M <= 1): tao_int8_smooth_quant_bf16 and tao_int8_scaled_mm_bf16 in ONE launch (the
+ * division and the quantisation in the GEMV's prologue, under its first weight loads), bit-identical
+ * to the two calls. act_scale as above (NULL = dynamic). Replaces F.linear on SmoothQuant's
+ * converted weight at decode (torchao/prototype/smoothquant/api.py:176-231,
+ * linear_activation_scale.py:61-70). Served up to K = 16384 on the default launch shapes (the
+ * token and the factor fit the prologue's registers); a longer K returns the argument error and
+ * is the two calls, the caller owning q and scale between them. */
+int tao_int8_smooth_linear_bf16(const uint16_t* x, const uint16_t* smooth,
+                                const uint16_t* act_scale, const int8_t* wq, const uint16_t* ws,
+                                const uint16_t* bias, uint16_t* y, int64_t M, int64_t N,
+                                int64_t K, void* stream);
+
+/* 1 when a caller replacing the SmoothQuant linear (api.py:176-231) should take
+ * tao_int8_smooth_linear_bf16 for this call, 0 when it should take the two calls: one token whose
+ * K the one launch serves, and for the static recipe (is_static != 0) K <= 8192, past which the
+ * two calls are faster (measured: experiments/bench_smoothquant.py). Never
+ * fails. */
+int tao_int8_smooth_linear_fused(int64_t M, int64_t N, int64_t K, int is_static);
+
 /* Device-side faults of the decode kernels since the last call, read and cleared (synchronous:
  * call outside graph capture). bits & 1: a KV-cache position outside [0, T) reached
  * tao_rope_kv_bf16 / tao_int4wo_decode_bf16's rope_kv epilogue; those launches wrote no cache

@@ -48,19 +48,7 @@ __device__ __forceinline__ uint32_t mul_pair_bf16(uint32_t xv, uint32_t wv) {
   return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
 }
 
-// bf16(float(x) / float(s)) on a bf16 pair: the IEEE fp32 quotient (v_div_scale / v_div_fmas /
-// v_div_fixup, no reciprocal estimate), then one round-to-nearest-even. Shared by
-// tao_act_prescale_bf16 and the prologue of tao_int4wo_prescaled_linear_bf16, so both write the
-// same bits.
-__device__ __forceinline__ uint32_t div_pair_bf16(uint32_t xv, uint32_t sv) {
-  const float lo = bf16lo_to_f32(xv) / bf16lo_to_f32(sv);
-  const float hi = bf16hi_to_f32(xv) / bf16hi_to_f32(sv);
-  return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
-}
-__device__ __forceinline__ uint4 div_piece_bf16(uint4 xv, uint4 sv) {
-  return make_uint4(div_pair_bf16(xv.x, sv.x), div_pair_bf16(xv.y, sv.y),
-                    div_pair_bf16(xv.z, sv.z), div_pair_bf16(xv.w, sv.w));
-}
+// x / act_scale on bf16 pairs and pieces (div_pair_bf16, div_piece_bf16): tao_common.h
 
 // a * b rounded to fp32 on its own: never contracted into a neighbouring add
 __device__ __forceinline__ float mul_unfused(float a, float b) {

@@ -19,6 +19,15 @@ __device__ __forceinline__ float token_scale(float amax) {
   return s < eps ? eps : s;
 }
 
+// The same scale with the clamp choose_qparams_affine applies when its caller passes no eps:
+// torch.finfo(bfloat16).eps = 2^-7 (quant_primitives.py:1526-1527, 1565). SmoothQuant's
+// _ActQuantizer.dynamic_quantize (prototype/smoothquant/api.py:138-145) is such a caller, so an
+// all-zero or tiny token gets the scale 0.0078125 there, not bf16(1e-5).
+__device__ __forceinline__ float token_scale_default_eps(float amax) {
+  const float s = round_bf16(amax / 127.f);
+  return s < 0.0078125f ? 0.0078125f : s;
+}
+
 // q = clamp(round(bf16(x * r)), -127, 127) of one value, as the low byte of the result
 __device__ __forceinline__ uint32_t quant1(float xv, float r) {
   float t = rintf(round_bf16(xv * r));

@@ -118,6 +118,20 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 }
 __device__ __forceinline__ float round_bf16(float f) { return bf16_to_f32(f32_to_bf16(f)); }
 
+// bf16(float(x) / float(s)) on a bf16 pair: the IEEE fp32 quotient (v_div_scale / v_div_fmas /
+// v_div_fixup, no reciprocal estimate), then one round-to-nearest-even: torch's bf16 `x / s`.
+// Shared by tao_act_prescale_bf16, the prologue of tao_int4wo_prescaled_linear_bf16 and the
+// SmoothQuant quantizers and prologue (int8_dyn.hip), so all of them form the same bits.
+__device__ __forceinline__ uint32_t div_pair_bf16(uint32_t xv, uint32_t sv) {
+  const float lo = bf16lo_to_f32(xv) / bf16lo_to_f32(sv);
+  const float hi = bf16hi_to_f32(xv) / bf16hi_to_f32(sv);
+  return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
+}
+__device__ __forceinline__ uint4 div_piece_bf16(uint4 xv, uint4 sv) {
+  return make_uint4(div_pair_bf16(xv.x, sv.x), div_pair_bf16(xv.y, sv.y),
+                    div_pair_bf16(xv.z, sv.z), div_pair_bf16(xv.w, sv.w));
+}
+
 // acc + a.lo*b.lo + a.hi*b.hi on bf16 pairs (v_dot2c_f32_bf16).
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float acc) {
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a),

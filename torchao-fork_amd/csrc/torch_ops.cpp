@@ -6,7 +6,8 @@
 // MXFP4-weight set mxfp4_quantize_rows, mxfp4w_scaled_mm, mxfp4w_dyn_linear, and the blockwise
 // float8 set blockfp8_quantize_act, blockfp8_quantize_weight, blockfp8_dequantize_weight,
 // blockfp8_scaled_mm, blockfp8_dyn_linear, and the activation pre-scale set act_prescale,
-// int4_prescaled_linear.
+// int4_prescaled_linear, and the SmoothQuant set int8_smooth_quantize_per_token,
+// int8_smooth_quantize_static, int8_smooth_dyn_linear, int8_smooth_static_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -272,6 +273,101 @@ Tensor int8_dyn_linear(const Tensor& x, const Tensor& w_int8, const Tensor& w_sc
                                     stream_of(x)),
            "tao_int8_dyn_linear_bf16");
   return y.reshape(out_shape(x, N));
+}
+
+// ---- SmoothQuant on the int8 dynamic / static linear (ops.py _int8_smooth_*_cuda) ----------------
+// The per-tensor activation scale of the static recipe: one bf16 value on x's device.
+Tensor check_smooth_act_scale(const Tensor& x, const Tensor& act_scale, const char* op) {
+  TORCH_CHECK(act_scale.scalar_type() == at::kBFloat16 && act_scale.numel() == 1, op,
+              " needs a bf16 act_scale of one element, got ", act_scale.scalar_type(), " with ",
+              act_scale.numel());
+  check_device(x, act_scale, "act_scale");
+  return act_scale.reshape({1}).contiguous();
+}
+
+std::tuple<Tensor, Tensor> int8_smooth_quantize(const Tensor& x, const Tensor& smooth,
+                                                const Tensor* act_scale, const char* op) {
+  const int64_t K = smooth.numel();
+  const Tensor s = check_act_scale(x, smooth, K, op);
+  TORCH_CHECK(K % 16 == 0 && K > 0 && K <= 65536, op,
+              " needs K % 16 == 0 and 0 < K <= 65536, got K = ", K);
+  std::optional<Tensor> as;
+  if (act_scale != nullptr) as = check_smooth_act_scale(x, *act_scale, op);
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor q = at::empty({M, K}, x.options().dtype(at::kChar));
+  Tensor sc = at::empty({M}, x.options());
+  check_rc(tao_int8_smooth_quant_bf16(cptr<uint16_t>(x2), cptr<uint16_t>(s),
+                                      as ? cptr<uint16_t>(*as) : nullptr, mptr<int8_t>(q),
+                                      mptr<uint16_t>(sc), M, K, stream_of(x)),
+           "tao_int8_smooth_quant_bf16");
+  return {q.reshape(x.sizes()), sc};
+}
+
+std::tuple<Tensor, Tensor> int8_smooth_quantize_per_token(const Tensor& x, const Tensor& smooth) {
+  return int8_smooth_quantize(x, smooth, nullptr, "int8_smooth_quantize_per_token");
+}
+
+std::tuple<Tensor, Tensor> int8_smooth_quantize_static(const Tensor& x, const Tensor& smooth,
+                                                       const Tensor& act_scale) {
+  return int8_smooth_quantize(x, smooth, &act_scale, "int8_smooth_quantize_static");
+}
+
+// One token where tao_int8_smooth_linear_fused says so: the one launch. Otherwise the fused
+// quantizer into buffers of the caching allocator, then int8_scaled_mm's entry (the GEMV for
+// M <= 4, the MFMA above): bit-identical.
+Tensor int8_smooth_linear(const Tensor& x, const Tensor& smooth, const Tensor* act_scale,
+                          const Tensor& w_int8, const Tensor& w_scale,
+                          const std::optional<Tensor>& bias, const char* op) {
+  check_int8_weight(w_int8, w_scale);
+  const int64_t N = w_int8.size(0), K = w_int8.size(1);
+  const Tensor s = check_act_scale(x, smooth, K, op);
+  TORCH_CHECK(K % 16 == 0 && K > 0 && K <= 65536, op,
+              " needs K % 16 == 0 and 0 < K <= 65536, got K = ", K);
+  std::optional<Tensor> as;
+  if (act_scale != nullptr) as = check_smooth_act_scale(x, *act_scale, op);
+  check_device(x, w_int8, "w_int8");
+  check_device(x, w_scale, "w_scale");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const Tensor ws = w_scale.reshape({-1}).to(at::kBFloat16).contiguous();
+  const Tensor w = w_int8.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  const uint16_t* asp = as ? cptr<uint16_t>(*as) : nullptr;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options());
+  if (tao_int8_smooth_linear_fused(M, N, K, asp != nullptr)) {
+    check_rc(tao_int8_smooth_linear_bf16(cptr<uint16_t>(x2), cptr<uint16_t>(s), asp,
+                                         cptr<int8_t>(w), cptr<uint16_t>(ws),
+                                         b ? cptr<uint16_t>(*b) : nullptr, mptr<uint16_t>(y), 1, N,
+                                         K, stream_of(x)),
+             "tao_int8_smooth_linear_bf16");
+  } else if (M > 0) {
+    Tensor q = at::empty({M, K}, x.options().dtype(at::kChar));
+    Tensor sc = at::empty({M}, x.options());
+    check_rc(tao_int8_smooth_quant_bf16(cptr<uint16_t>(x2), cptr<uint16_t>(s), asp,
+                                        mptr<int8_t>(q), mptr<uint16_t>(sc), M, K, stream_of(x)),
+             "tao_int8_smooth_quant_bf16");
+    check_rc(tao_int8_scaled_mm_bf16(cptr<int8_t>(q), cptr<uint16_t>(sc), cptr<int8_t>(w),
+                                     cptr<uint16_t>(ws), b ? cptr<uint16_t>(*b) : nullptr,
+                                     mptr<uint16_t>(y), M, N, K, stream_of(x)),
+             "tao_int8_scaled_mm_bf16");
+  }
+  return y.reshape(out_shape(x, N));
+}
+
+Tensor int8_smooth_dyn_linear(const Tensor& x, const Tensor& smooth, const Tensor& w_int8,
+                              const Tensor& w_scale, const std::optional<Tensor>& bias) {
+  return int8_smooth_linear(x, smooth, nullptr, w_int8, w_scale, bias, "int8_smooth_dyn_linear");
+}
+
+Tensor int8_smooth_static_linear(const Tensor& x, const Tensor& smooth, const Tensor& act_scale,
+                                 const Tensor& w_int8, const Tensor& w_scale,
+                                 const std::optional<Tensor>& bias) {
+  return int8_smooth_linear(x, smooth, &act_scale, w_int8, w_scale, bias,
+                            "int8_smooth_static_linear");
 }
 
 // ---- float8 (e4m3fn) weight-only (ops.py _fp8wo_linear_cuda & co) -----------------------------
@@ -760,6 +856,10 @@ TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
   m.impl("int8_quantize_per_token", &int8_quantize_per_token);
   m.impl("int8_scaled_mm", &int8_scaled_mm);
   m.impl("int8_dyn_linear", &int8_dyn_linear);
+  m.impl("int8_smooth_quantize_per_token", &int8_smooth_quantize_per_token);
+  m.impl("int8_smooth_quantize_static", &int8_smooth_quantize_static);
+  m.impl("int8_smooth_dyn_linear", &int8_smooth_dyn_linear);
+  m.impl("int8_smooth_static_linear", &int8_smooth_static_linear);
   m.impl("fp8_weight_only_linear", &fp8_weight_only_linear);
   m.impl("fp8_quantize_rows", &fp8_quantize_rows);
   m.impl("fp8_dequantize", &fp8_dequantize);
@@ -803,6 +903,12 @@ extern "C" const char* tao_torch_ops_served_blockfp8(void) {
 // The activation pre-scale ops (AWQ) served here, a set of their own as well.
 extern "C" const char* tao_torch_ops_served_awq(void) {
   return "act_prescale,int4_prescaled_linear";
+}
+
+// The SmoothQuant ops served here, a set of their own as well.
+extern "C" const char* tao_torch_ops_served_smoothquant(void) {
+  return "int8_smooth_quantize_per_token,int8_smooth_quantize_static,int8_smooth_dyn_linear,"
+         "int8_smooth_static_linear";
 }
 
 // The MXFP4-weight ops served here, a set of their own as well.

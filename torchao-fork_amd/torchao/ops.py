@@ -52,6 +52,14 @@ Operators:
     (one token without a bias at K <= 4096 and N * K <= 2^24: one launch, the quotient formed
     while the GEMV stages x in LDS), bit-identical to ``act_prescale`` ->
     ``int4_weight_only_linear``.
+  * ``int8_smooth_quantize_per_token`` / ``int8_smooth_quantize_static`` — SmoothQuant's
+    activation side in one launch: ``bf16(x / smooth)``, then the per-token int8 codes of
+    ``to_affine_quantized_intx`` with its default eps (2^-7 for bf16) or the static codes of
+    ``to_affine_quantized_intx_static`` with one calibrated scale; replace the division above and
+    ``_ActQuantizer`` (prototype/smoothquant/api.py:133-155). The scale comes back as ``[M]``.
+  * ``int8_smooth_dyn_linear`` / ``int8_smooth_static_linear`` — those and ``int8_scaled_mm``
+    from a bf16 input at any M (one token up to K = 16384, static 8192: one launch, the division
+    and the quantisation in the GEMV's prologue), bit-identical to the two ops.
 """
 
 import ctypes
@@ -161,6 +169,20 @@ lib_awq.define("act_prescale(Tensor x, Tensor scale) -> Tensor")
 lib_awq.define(
     "int4_prescaled_linear(Tensor x, Tensor act_scale, Tensor packed_w, Tensor scales_and_zeros, "
     "int group_size, Tensor? bias=None) -> Tensor")
+# The SmoothQuant ops (torchao.prototype.smoothquant over the int8 dynamic / static linear), on a
+# fragment of their own; opchecked in tests/test_gpu_smoothquant.py. bf16 only; ``smooth`` is the
+# per-input-channel factor [K], ``act_scale`` the per-tensor scale of the static recipe (one bf16).
+lib_smoothquant = torch.library.Library("torchao", "FRAGMENT")
+lib_smoothquant.define(
+    "int8_smooth_quantize_per_token(Tensor x, Tensor smooth) -> (Tensor, Tensor)")
+lib_smoothquant.define(
+    "int8_smooth_quantize_static(Tensor x, Tensor smooth, Tensor act_scale) -> (Tensor, Tensor)")
+lib_smoothquant.define(
+    "int8_smooth_dyn_linear(Tensor x, Tensor smooth, Tensor w_int8, Tensor w_scale, "
+    "Tensor? bias=None) -> Tensor")
+lib_smoothquant.define(
+    "int8_smooth_static_linear(Tensor x, Tensor smooth, Tensor act_scale, Tensor w_int8, "
+    "Tensor w_scale, Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -714,6 +736,123 @@ def _int8_dyn_linear_cuda(x, w_int8, w_scale, bias=None):
         _lib.call("tao_int8_dyn_linear_bf16", _ptr(x2), _ptr(w_int8), _ptr(ws), _ptr(bias),
                   _ptr(y), 1, N, K, _stream(x))
     return y.reshape(_linear_out_shape(x, N))
+
+
+# ---------------------------------------------------------------------------------------------
+# SmoothQuant: fused smooth + quantize, and the linear on top (prototype/smoothquant)
+# ---------------------------------------------------------------------------------------------
+def _check_smooth(x: Tensor, smooth: Tensor, act_scale: Optional[Tensor], K: int, op: str):
+    _check_act_scale(x, smooth, K, op)
+    torch._check(K % 16 == 0 and 0 < K <= 65536,
+                 lambda: f"{op} needs K % 16 == 0 and 0 < K <= 65536, got K = {K}")
+    if act_scale is not None:
+        torch._check(act_scale.dtype is torch.bfloat16 and act_scale.numel() == 1,
+                     lambda: f"{op} needs a bf16 act_scale of one element, got "
+                             f"{act_scale.dtype} with {act_scale.numel()}")
+
+
+def _smooth_quant_fake(x, smooth, act_scale, op):
+    K = smooth.numel()
+    _check_smooth(x, smooth, act_scale, K, op)
+    return x.new_empty(x.shape, dtype=torch.int8), x.new_empty((x.numel() // K,))
+
+
+@torch.library.register_fake("torchao::int8_smooth_quantize_per_token")
+def _(x, smooth):
+    return _smooth_quant_fake(x, smooth, None, "int8_smooth_quantize_per_token")
+
+
+@torch.library.register_fake("torchao::int8_smooth_quantize_static")
+def _(x, smooth, act_scale):
+    return _smooth_quant_fake(x, smooth, act_scale, "int8_smooth_quantize_static")
+
+
+def _smooth_linear_fake(x, smooth, act_scale, w_int8, w_scale, op):
+    N, K = _check_int8_weight(w_int8, w_scale)
+    _check_smooth(x, smooth, act_scale, K, op)
+    return x.new_empty(_linear_out_shape(x, N))
+
+
+@torch.library.register_fake("torchao::int8_smooth_dyn_linear")
+def _(x, smooth, w_int8, w_scale, bias=None):
+    return _smooth_linear_fake(x, smooth, None, w_int8, w_scale, "int8_smooth_dyn_linear")
+
+
+@torch.library.register_fake("torchao::int8_smooth_static_linear")
+def _(x, smooth, act_scale, w_int8, w_scale, bias=None):
+    return _smooth_linear_fake(x, smooth, act_scale, w_int8, w_scale,
+                               "int8_smooth_static_linear")
+
+
+def _smooth_operands(x, smooth, act_scale, K):
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    if act_scale is not None:
+        act_scale = act_scale.reshape(1).contiguous()
+    return x2, _scale_row(smooth), act_scale
+
+
+def _int8_smooth_quant_cuda(x, smooth, act_scale, op):
+    """bf16(x / smooth), then the per-token (act_scale None; 2^-7 scale clamp) or static int8
+    codes, in one launch: (q int8 like x, scale bf16 [M])."""
+    K = smooth.numel()
+    _check_smooth(x, smooth, act_scale, K, op)
+    _same_device(x, smooth=smooth, act_scale=act_scale)
+    x2, s, a = _smooth_operands(x, smooth, act_scale, K)
+    M = x2.size(0)
+    q = torch.empty((M, K), dtype=torch.int8, device=x.device)
+    sc = torch.empty((M,), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("tao_int8_smooth_quant_bf16", _ptr(x2), _ptr(s), _ptr(a), _ptr(q), _ptr(sc), M,
+                  K, _stream(x))
+    return q.reshape(x.shape), sc
+
+
+def _int8_smooth_quant_per_token_cuda(x, smooth):
+    return _int8_smooth_quant_cuda(x, smooth, None, "int8_smooth_quantize_per_token")
+
+
+def _int8_smooth_quant_static_cuda(x, smooth, act_scale):
+    return _int8_smooth_quant_cuda(x, smooth, act_scale, "int8_smooth_quantize_static")
+
+
+def _int8_smooth_linear_cuda(x, smooth, act_scale, w_int8, w_scale, bias, op):
+    """The SmoothQuant int8 linear from a bf16 activation. One token where
+    tao_int8_smooth_linear_fused says so: one launch. Otherwise the fused quantizer into buffers
+    of the caching allocator, then int8_scaled_mm's entry; bit-identical."""
+    N, K = _check_int8_weight(w_int8, w_scale)
+    _check_smooth(x, smooth, act_scale, K, op)
+    _same_device(x, smooth=smooth, act_scale=act_scale, w_int8=w_int8, w_scale=w_scale, bias=bias)
+    x2, s, a = _smooth_operands(x, smooth, act_scale, K)
+    M = x2.size(0)
+    ws = w_scale.reshape(-1).to(torch.bfloat16).contiguous()
+    w_int8 = w_int8.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if _lib.lib().tao_int8_smooth_linear_fused(M, N, K, int(a is not None)):
+            _lib.call("tao_int8_smooth_linear_bf16", _ptr(x2), _ptr(s), _ptr(a), _ptr(w_int8),
+                      _ptr(ws), _ptr(bias), _ptr(y), 1, N, K, _stream(x))
+        elif M > 0:
+            q = torch.empty((M, K), dtype=torch.int8, device=x.device)
+            sc = torch.empty((M,), dtype=torch.bfloat16, device=x.device)
+            _lib.call("tao_int8_smooth_quant_bf16", _ptr(x2), _ptr(s), _ptr(a), _ptr(q), _ptr(sc),
+                      M, K, _stream(x))
+            _lib.call("tao_int8_scaled_mm_bf16", _ptr(q), _ptr(sc), _ptr(w_int8), _ptr(ws),
+                      _ptr(bias), _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
+def _int8_smooth_dyn_linear_cuda(x, smooth, w_int8, w_scale, bias=None):
+    return _int8_smooth_linear_cuda(x, smooth, None, w_int8, w_scale, bias,
+                                    "int8_smooth_dyn_linear")
+
+
+def _int8_smooth_static_linear_cuda(x, smooth, act_scale, w_int8, w_scale, bias=None):
+    return _int8_smooth_linear_cuda(x, smooth, act_scale, w_int8, w_scale, bias,
+                                    "int8_smooth_static_linear")
 
 
 @torch.library.register_fake("torchao::int4_quantize_pack")
@@ -1336,6 +1475,7 @@ _native_served_mx: frozenset = frozenset()
 _native_served_mxfp4: frozenset = frozenset()
 _native_served_blockfp8: frozenset = frozenset()
 _native_served_awq: frozenset = frozenset()
+_native_served_smoothquant: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -1364,6 +1504,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_awq
         _served.restype = ctypes.c_char_p
         _native_served_awq = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_smoothquant
+        _served.restype = ctypes.c_char_p
+        _native_served_smoothquant = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -1402,6 +1545,11 @@ def native_dispatch_blockfp8() -> frozenset:
 def native_dispatch_awq() -> frozenset:
     """The activation pre-scale (AWQ) ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_awq
+
+
+def native_dispatch_smoothquant() -> frozenset:
+    """The SmoothQuant ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_smoothquant
 
 
 for _name, _fn in [
@@ -1464,6 +1612,14 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_awq:
         lib_awq.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("int8_smooth_quantize_per_token", _int8_smooth_quant_per_token_cuda),
+    ("int8_smooth_quantize_static", _int8_smooth_quant_static_cuda),
+    ("int8_smooth_dyn_linear", _int8_smooth_dyn_linear_cuda),
+    ("int8_smooth_static_linear", _int8_smooth_static_linear_cuda),
+]:
+    if _name not in _native_served_smoothquant:
+        lib_smoothquant.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")

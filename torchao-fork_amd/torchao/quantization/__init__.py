@@ -1,7 +1,7 @@
 """Quantization workflows on the MI355X weight-only linear path."""
 
 from torchao.quantization.fuse import fuse_gate_up_
-from torchao.quantization.granularity import PerRow, PerTensor
+from torchao.quantization.granularity import PerAxis, PerRow, PerTensor
 from torchao.quantization.linear_activation_quantized_tensor import (
     LinearActivationQuantizedTensor,
     to_linear_activation_quantized,
@@ -42,6 +42,7 @@ __all__ = [
     "Int8DynamicActivationInt8WeightConfig",
     "Float8WeightOnlyConfig",
     "Float8DynamicActivationFloat8WeightConfig",
+    "PerAxis",
     "PerRow",
     "PerTensor",
     "ModuleFqnToConfig",

@@ -1,7 +1,8 @@
-"""Quantization granularities of the float8 configs.
+"""Quantization granularities of the float8 configs and of the min/max observers.
 
 Reference: torchao/quantization/granularity.py. Only the two granularities the float8 dynamic
-config names are defined; class paths and (empty) field sets are the reference's, so a
+config names and the ``PerAxis`` of torchao.quantization.observer (SmoothQuant) are defined; class
+paths and field sets are the reference's, so a
 ``quant_kwargs`` dict it pickled (``{"activation_granularity": PerRow(), ...}``) loads here with
 ``torch.load(weights_only=True)``.
 """
@@ -10,7 +11,7 @@ from dataclasses import dataclass
 
 import torch
 
-__all__ = ["Granularity", "PerTensor", "PerRow"]
+__all__ = ["Granularity", "PerTensor", "PerRow", "PerAxis"]
 
 
 @dataclass(frozen=True)
@@ -27,4 +28,11 @@ class PerRow(Granularity):
     """One scale per row: block size (1, ..., 1, shape[-1]), for activations and weights alike."""
 
 
-torch.serialization.add_safe_globals([Granularity, PerTensor, PerRow])
+@dataclass(frozen=True)
+class PerAxis(Granularity):
+    """One scale per index along ``axis`` (the observers of torchao.quantization.observer)."""
+
+    axis: int
+
+
+torch.serialization.add_safe_globals([Granularity, PerTensor, PerRow, PerAxis])

@@ -12,6 +12,10 @@ What changes is which kernels run:
 * inner weight a 2-D int4 ``TensorCoreTiledLayout`` AQT on the GPU, bf16 input and scale:
   ``torch.ops.torchao.int4_prescaled_linear`` (one token: the division happens while the GEMV
   stages x in LDS, one launch; more tokens: ``act_prescale`` then the int4 linear);
+* inner weight SmoothQuant's dynamic or static int8 wrapper (``_smoothquant_int8_linear``), bf16
+  input and factor on the GPU: ``torch.ops.torchao.int8_smooth_dyn_linear`` /
+  ``int8_smooth_static_linear`` (one token up to K = 16384, static 8192: division, activation quantization and
+  int8 GEMV in one launch; otherwise the fused smooth + quantize kernel, then the int8 GEMV / MFMA);
 * any other inner weight: ``torch.ops.torchao.act_prescale`` for bf16 GPU operands (plain
   ``x / scale`` otherwise), then ``F.linear`` on the inner weight, which keeps its own rules
   (including raising on the CPU).
@@ -39,6 +43,66 @@ def _prescale(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
             and scale.numel() == x.shape[-1] and scale.numel() % 8 == 0):
         return torch.ops.torchao.act_prescale(x, scale)
     return x / scale
+
+
+def _smoothquant_int8_linear(x, factor, inner, bias):
+    """SmoothQuant's converted weight (prototype/smoothquant/api.py) with bf16 GPU input and
+    factor: ``inner`` is a ``LinearActivationQuantizedTensor`` over
+    ``_ActQuantizer(torch.int8, -127).dynamic_quantize``, or the static wrapper over
+    ``.static_quantize`` with one bf16 scale and a zero (or no) zero point, around a 2-D int8
+    ``PlainLayout`` AQT with a bf16 per-channel scale. Then the division, the activation
+    quantization and the int8 linear are ``torch.ops.torchao.int8_smooth_dyn_linear`` /
+    ``int8_smooth_static_linear``, bit-identical to the reference's steps. Anything else returns
+    None and takes the generic path."""
+    from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
+    from torchao.dtypes.uintx.plain_layout import PlainLayout, _aqt_is_int8
+    from torchao.prototype.smoothquant.api import _ActQuantizer
+    from torchao.quantization.linear_activation_quantized_tensor import (
+        LinearActivationQuantizedTensor,
+    )
+    from torchao.quantization.weight_tensor_linear_activation_quantization import (
+        WeightTensorWithLinearActivationQuantizationMetadata,
+    )
+
+    if not (_is_plain_bf16_gpu(x) and _is_plain_bf16_gpu(factor) and x.numel() > 0):
+        return None
+    act_scale = None
+    if isinstance(inner, LinearActivationQuantizedTensor):
+        fn, method = inner.input_quant_func, _ActQuantizer.dynamic_quantize
+    elif isinstance(inner, WeightTensorWithLinearActivationQuantizationMetadata):
+        fn, method = inner.input_quant_func_static, _ActQuantizer.static_quantize
+        act_scale = inner.scale
+        if not (_is_plain_bf16_gpu(act_scale) and act_scale.numel() == 1):
+            return None
+        if inner.zero_point is not None:
+            # read back once per wrapper object, not per call (a device-to-host copy)
+            if not hasattr(inner, "_zero_point_is_zero"):
+                inner._zero_point_is_zero = not bool(inner.zero_point.any())
+            if not inner._zero_point_is_zero:
+                return None
+    else:
+        return None
+    quantizer = getattr(fn, "__self__", None)
+    if not (getattr(fn, "__func__", None) is method and type(quantizer) is _ActQuantizer
+            and quantizer.target_dtype == torch.int8 and quantizer.quant_min == -127
+            and not inner.quant_kwargs):
+        return None
+    w = inner.original_weight_tensor
+    K = x.shape[-1]
+    if not (isinstance(w, AffineQuantizedTensor) and _aqt_is_int8(w) and w.dtype == torch.bfloat16
+            and isinstance(w._layout, PlainLayout) and len(w.shape) == 2
+            and w.shape[1] == K == factor.numel() and K % 16 == 0 and K <= 65536):
+        return None
+    impl = w.tensor_impl
+    # (the weight's zero point is not read: _linear_int8_act_int8_weight_impl does not use it)
+    if not (impl.int_data.is_cuda and impl.scale.dtype == torch.bfloat16
+            and impl.scale.numel() == w.shape[0]):
+        return None
+    if act_scale is None:
+        return torch.ops.torchao.int8_smooth_dyn_linear(
+            x, factor, impl.int_data, impl.scale.reshape(-1), bias)
+    return torch.ops.torchao.int8_smooth_static_linear(
+        x, factor, act_scale, impl.int_data, impl.scale.reshape(-1), bias)
 
 
 class WeightTensorWithLinearActivationScaleMetadata(TorchAOBaseTensor):
@@ -91,6 +155,9 @@ class WeightTensorWithLinearActivationScaleMetadata(TorchAOBaseTensor):
             return torch.ops.torchao.int4_prescaled_linear(
                 input_tensor, scale, impl.packed_weight, impl.scale_and_zero, w.block_size[-1],
                 bias)
+        y = _smoothquant_int8_linear(input_tensor, scale, w, bias)
+        if y is not None:
+            return y
         return torch.nn.functional.linear(_prescale(input_tensor, scale), w, bias)
 
     @classmethod

@@ -27,6 +27,7 @@ __all__ = [
     "MappingType",
     "ZeroPointDomain",
     "choose_qparams_affine",
+    "choose_qparams_affine_with_min_max",
     "quantize_affine",
     "dequantize_affine",
     "_choose_qparams_affine_tinygemm",
@@ -177,6 +178,65 @@ def choose_qparams_affine(
     if zero_point_dtype is not None:
         zero_point = zero_point.to(dtype=zero_point_dtype)
     return scale.to(dtype=scale_dtype, device=input.device), zero_point
+
+
+@torch.no_grad()
+def choose_qparams_affine_with_min_max(
+    min_val: torch.Tensor,
+    max_val: torch.Tensor,
+    mapping_type: MappingType,
+    block_size: Tuple[int, ...],
+    target_dtype: torch.dtype,
+    quant_min: Optional[int] = None,
+    quant_max: Optional[int] = None,
+    eps: Optional[float] = None,
+    scale_dtype: Optional[torch.dtype] = None,
+    zero_point_dtype: Optional[torch.dtype] = None,
+    preserve_zero: bool = True,
+    zero_point_domain: ZeroPointDomain = ZeroPointDomain.INT,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """``choose_qparams_affine`` from already reduced per-block ``min_val`` / ``max_val`` (the
+    observers of torchao.quantization.observer; reference quant_primitives.py:1378-1494).
+    ``block_size`` is unused, as in the reference. Served: zero-preserving qparams in the integer
+    or the zero-point-free domain; dtypes and eps default to those of ``min_val``."""
+    if zero_point_domain is None:
+        raise ValueError("Please use ZeroPointDomain.NONE instead of None")
+    if not preserve_zero or zero_point_domain is ZeroPointDomain.FLOAT:
+        raise NotImplementedError(
+            "choose_qparams_affine_with_min_max serves preserve_zero=True with "
+            "ZeroPointDomain.INT or ZeroPointDomain.NONE")
+    quant_min, quant_max = _get_and_check_qmin_qmax(target_dtype, quant_min, quant_max)
+    assert min_val is not None and max_val is not None, "min_val and max_val are required"
+    assert min_val.dtype == max_val.dtype, (
+        f"min_val and max_val must share a dtype, got {min_val.dtype}, {max_val.dtype}")
+    scale_dtype = min_val.dtype if scale_dtype is None else scale_dtype
+    eps = torch.finfo(min_val.dtype).eps if eps is None else eps
+    mn_neg = torch.min(min_val, torch.zeros_like(min_val))
+    mx_pos = torch.max(max_val, torch.zeros_like(max_val))
+    if mapping_type in (MappingType.SYMMETRIC, MappingType.SYMMETRIC_NO_CLIPPING_ERR):
+        if mapping_type is MappingType.SYMMETRIC:
+            scale = torch.max(-mn_neg, mx_pos) / (float(quant_max - quant_min) / 2)
+        else:
+            smin = mn_neg / float(quant_min)
+            smax = mx_pos / float(quant_max)
+            scale = torch.where(smin > smax, smin, smax)
+        zero_point = None
+        if zero_point_domain is not ZeroPointDomain.NONE:
+            zero_point = torch.full_like(scale, int((quant_max + quant_min + 1) / 2))
+        scale = torch.clamp(scale, min=eps)
+    elif mapping_type is MappingType.ASYMMETRIC:
+        scale = (mx_pos - mn_neg) / torch.tensor(
+            float(quant_max - quant_min), dtype=scale_dtype, device=min_val.device)
+        scale = torch.clamp(scale, min=eps)
+        zero_point = None
+        if zero_point_domain is not ZeroPointDomain.NONE:
+            zero_point = torch.clamp(quant_min - _Round.apply(mn_neg / scale), quant_min, quant_max)
+            zero_point_dtype = torch.int32 if zero_point_dtype is None else zero_point_dtype
+    else:
+        raise ValueError(f"Unsupported mapping type: {mapping_type}")
+    if zero_point is not None:
+        zero_point = zero_point.to(dtype=zero_point_dtype)
+    return scale.to(dtype=scale_dtype, device=min_val.device), zero_point
 
 
 @torch.no_grad()
