@@ -415,6 +415,54 @@ int tao_int4_quantize_bf16(const uint16_t* w, uint32_t* packed, uint16_t* scales
 int tao_int8_quantize_rows_bf16(const uint16_t* w, int8_t* q, uint16_t* scale, int64_t rows,
                                 int64_t K, float eps, void* stream);
 
+/* ---- W4A8: int8 dynamic activation x int4 weight packed two per byte (csrc/w4a8.hip) ----------
+ * Int8DynamicActivationInt4WeightConfig(layout=CutlassInt4PackedLayout()): per-token symmetric
+ * int8 activations, per-output-channel symmetric int4 weights, both with fp32 scales and no zero
+ * point. Weight storage is the reference's: byte j of a row holds element 2 j in its low nibble
+ * and element 2 j + 1 in its high nibble, two's complement. */
+
+/* Per-token quantizer of x [M][K] bf16: s[m] = max(fp32(bf16(amax|x[m]| / 127.5)), 2^-23),
+ * q = clamp(rne(fp32(x) * (1 / s[m])), -128, 127), the reciprocal and the product in fp32. An
+ * all-zero token gets codes 0. q int8 [M][K], scale fp32 [M]. Replaces _int8_symm_cutlass_quant
+ * (torchao/quantization/quant_api.py:1299-1308: to_affine_quantized_intx, ~8 eager kernels), byte
+ * for byte. K % 8 == 0; x 16-B aligned, q 8-B aligned. */
+int tao_int8_quant_per_token_f32(const uint16_t* x, int8_t* q, float* scale, int64_t M, int64_t K,
+                                 void* stream);
+
+/* Per-row weight quantizer of w [rows][K] bf16 with packed output:
+ * s[r] = max(fp32(bf16(amax|w[r]| / 7.5)), 2^-23), q = clamp(rne(fp32(w) * (1 / s[r])), -8, 7),
+ * two codes per byte as above. An all-zero row gets zero bytes. q uint8 [rows][K/2], scale fp32
+ * [rows]. Replaces _int4_symm_cutlass_quant (torchao/quantization/quant_api.py:1311-1323) and
+ * Int4PackedTensorImpl.from_plain (torchao/dtypes/uintx/cutlass_int4_packed_layout.py:131-144),
+ * byte for byte. K % 8 == 0; w 16-B aligned, q 4-B aligned. */
+int tao_int4_quantize_rows_packed_bf16(const uint16_t* w, uint8_t* q, float* scale, int64_t rows,
+                                       int64_t K, void* stream);
+
+/* y[m][n] = bf16( fp32(fp32(fp32(acc) * xs[m]) * ws[n]) + fp32(bias[n]) ),
+ * acc[m][n] = sum_k xq[m][k] * wq[n][k] in exact int32: one rounding to bf16, with or without
+ * bias. xq int8 [M][K], xs f32 [M], wq uint8 [N][K/2] packed int4 codes, ws f32 [N], bias bf16 [N]
+ * or NULL. The result does not depend on the route (GEMV up to M = 2, and up to M = 4 for weights
+ * of at most 32 Mi elements; int8 MFMA above) or on any launch shape: every partial sum is an
+ * integer. Replaces
+ * torchao::rowwise_scaled_linear_cutlass_s8s4 behind _linear_int8_act_int4_weight_cutlass_impl
+ * (torchao/dtypes/uintx/cutlass_int4_packed_layout.py:176-189), a CUTLASS kernel the reference
+ * builds for sm80 only. K % 32 == 0, K < 131072 (the weights enter the dot products as int8 x 16;
+ * the factor leaves the int32 sum exactly), any N, M >= 0 (M == 0 is a no-op); xq, wq 16-B aligned,
+ * each operand below 4 GiB. */
+int tao_w4a8_scaled_mm_bf16(const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                            const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                            void* stream);
+
+/* One token (M <= 1): tao_int8_quant_per_token_f32 of the bf16 token x [K] and the product above
+ * in one launch, bit-identical to the two calls. Replaces LinearActivationQuantizedTensor's
+ * quantize-then-F.linear for this recipe at decode (_int8_symm_cutlass_quant,
+ * torchao/quantization/quant_api.py:1299-1308, then cutlass_int4_packed_layout.py:176-189). More
+ * tokens are the two calls, the caller owning the code buffer between them. K % 32 == 0,
+ * K <= 65536. */
+int tao_w4a8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const float* ws,
+                             const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                             void* stream);
+
 /* ---- int8 KV cache (AffineQuantizedKVCache, torchao/_models/llama/model.py:198-240) -----------
  * k_cache / v_cache [B][Hkv][T][128] int8 codes, k_scale / v_scale [B][Hkv][T] bf16, one scale per
  * row: symmetric, [-127, 127], eps 1e-5, the arithmetic of _quantize_activation_per_token_absmax in

@@ -1,10 +1,12 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// eight weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
+// nine weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
 //   Int4WO  : bf16 x, int4 group-quant W (gfx950 row-stream layout), v_mfma_f32_16x16x32_bf16
 //   Int8WO  : bf16 x, int8 per-channel W,                            v_mfma_f32_16x16x32_bf16
 //   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
 //   Int8Dyn : int8 x (per-token scale), int8 W (per-channel scale),   v_mfma_i32_16x16x64_i8
+//   Int8DynW4: int8 x (per-token fp32 scale), int4 W two per byte (per-channel fp32 scale),
+//             expanded to int8 x 16 in registers,                    v_mfma_i32_16x16x64_i8
 //   Fp8Dyn  : e4m3fn x (per-token scale), e4m3fn W (per-row scale),   v_mfma_scale_f32_16x16x128_f8f6f4
 //   MxFp8   : e4m3fn x and W, one E8M0 scale byte per 32-k block,    v_mfma_scale_f32_16x16x128_f8f6f4
 //   MxFp8Fp4: e4m3fn x, e2m1 W (two codes per byte), the same scales, the same MFMA (cbsz 0, blgp 4)
@@ -219,7 +221,12 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
   auto store_x = [&](const uint4 (&src)[XLOADS], int j) __attribute__((always_inline)) {
     const int st = abs_step(j);
     uint4* dst = xs + (j & 1) * TILE;
-    if (!ragged && st < s1) {
+    if constexpr (P::kXPerm) {
+      // (Int8DynW4) each piece's bytes in the B fragment's k order; the tail mask as below
+      const uint32_t keep = st < s1 && st * XSB + xslot_b < row_bytes ? ~0u : 0u;
+#pragma unroll
+      for (int i = 0; i < XLOADS; ++i) dst[xlds[i]] = and16(P::xperm(src[i]), keep);
+    } else if (!ragged && st < s1) {
 #pragma unroll
       for (int i = 0; i < XLOADS; ++i) dst[xlds[i]] = src[i];
     } else {
@@ -734,6 +741,17 @@ int blockfp8_scaled_mm_launch(const uint8_t* xq, const float* xs, const uint8_t*
                               const float* ws, const uint16_t* bias, uint16_t* y, int M, int N,
                               int K, hipStream_t stream) {
   BlockFp8 pol;
+  pol.w = reinterpret_cast<const uint4*>(wq);
+  pol.wscale = ws;
+  pol.xscale = xs;
+  return launch_gemm(xq, pol, bias, y, M, N, K, stream);
+}
+
+// W4A8 (w4a8.hip): every M above the GEMV's goes to the Int8DynW4 instance
+int w4a8_scaled_mm_launch(const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                          const uint16_t* bias, uint16_t* y, int M, int N, int K,
+                          hipStream_t stream) {
+  Int8DynW4 pol;
   pol.w = reinterpret_cast<const uint4*>(wq);
   pol.wscale = ws;
   pol.xscale = xs;

@@ -38,6 +38,7 @@ struct PolicyDefaults {
   static constexpr bool kBlockScaled = false;  // the MFMAs take per-block scale bytes
   static constexpr bool kScaleAligned = false;  // ... a row's 8 per step are one aligned 8-B word
   static constexpr bool kBlockF32 = false;     // fp32 scales per 128-k block, applied per MFMA
+  static constexpr bool kXPerm = false;        // x pieces pass through xperm() on their way to LDS
   typedef f32x4_t Acc;
   // x image mask (x_slot, gemm_mfma.hip)
   static __device__ __forceinline__ int xswz(int row) { return row & 15; }
@@ -332,6 +333,76 @@ struct Int8Dyn : ByteWeights<256> {
   __device__ __forceinline__ float epi(int acc, float xs, float ws) const {
     const float v = round_bf16(round_bf16((float)acc) * xs);
     return round_bf16(v * ws);
+  }
+};
+
+// Int8DynW4: int8 x (per-token fp32 scale), int4 W packed two per byte (per-row fp32 scale; W4A8,
+// w4a8.hip) on Int8Dyn's MFMA, x image size (16 slots of 16 int8 per row and step) and 256-k step.
+// W is 128 B per row and step, one full line: MxFp8Fp4's two loads per wave (LineLoader<128>),
+// regrouped through the 2-KiB stage so that lane (n, kq) holds the 16-B pieces kq and 4 + kq of
+// row n: k 32 kq .. + 32 and 128 + 32 kq .. + 32 of the step. MFMA s takes dwords (2 (s & 1),
+// 2 (s & 1) + 1) of piece s >> 1, i.e. the 16 k of x slot 8 (s >> 1) + 2 kq + (s & 1): Int8WO's
+// slot map on a 16-slot row, conflict-free under the plain row mask (x_slot, gemm_mfma.hip).
+// Expansion: for a dword w of eight nibbles (storage: element 2 j in the low nibble of byte j),
+// (w << 4) & 0xF0F0F0F0 and w & 0xF0F0F0F0 are its even and its odd elements times 16 as int8 lanes,
+// so the B fragment of 16 k holds them in the order 0 2 4 6 | 1 3 5 7 | 8 10 12 14 | 9 11 13 15.
+// A must agree per lane group: every 16-B x piece is permuted to that order once, on its way into
+// the LDS image (kXPerm / xperm(), four v_perm_b32 per piece per workgroup), not per MFMA. The
+// factor 16 leaves the exact int32 sum by an arithmetic shift in the epilogue; with it
+// |acc| <= 16384 K < 2^31 for K < 131072 (checked by the entry). A K tail reads the next row's
+// nibbles (or 0 past the buffer) against x zeroed at the LDS store: integers, adding exactly 0.
+struct Int8DynW4 : PolicyDefaults {
+  static constexpr int kPathId = 8;  // no measured table entries: the heuristic shapes
+  static constexpr int kABytes = 1;  // int8 x
+  static constexpr int kKStep = 256;
+  static constexpr int kMfma = 4;
+  static constexpr int kMaxBM = 128;
+  static constexpr int kPrefKG = 1;
+  static constexpr int kMinSlice = 4;
+  static constexpr bool kXPerm = true;
+  typedef i32x4_t Acc;
+  typedef LineLoader<128> Lines;  // rows l / 8 and 8 + l / 8, bytes 16 (l % 8) of the step's 128
+  static constexpr int kStage = Lines::kStage;
+  typedef Lines::Lane Lane;
+  typedef Lines::Chunk Chunk;
+  typedef Lines::Chunk Prep;  // v[h]: nibbles of k 128 h + 32 kq .. + 32 of row n
+  const uint4* w;        // [N][K/32] 16-B pieces of nibbles
+  const float* wscale;   // [N] fp32
+  const float* xscale;   // [M] fp32
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    return Lines::setup(w, (uint32_t)K >> 1, bn, lane, N);
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const { return Lines::load(L, st); }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    return Lines::regroup(ch, stage, lane);
+  }
+  static __device__ __forceinline__ int slot(int s, int kq) {
+    return (s >> 1) * 8 + kq * 2 + (s & 1);
+  }
+  // a 16-B x piece (16 int8 in element order) in the B fragment's order
+  static __device__ __forceinline__ uint4 xperm(const uint4& v) {
+    return make_uint4(__builtin_amdgcn_perm(v.y, v.x, 0x06040200u),
+                      __builtin_amdgcn_perm(v.y, v.x, 0x07050301u),
+                      __builtin_amdgcn_perm(v.w, v.z, 0x06040200u),
+                      __builtin_amdgcn_perm(v.w, v.z, 0x07050301u));
+  }
+  __device__ __forceinline__ i32x4_t frag(const Prep& p, int s) const {
+    const uint4& q = s < 2 ? p.v[0] : p.v[1];
+    const uint32_t d0 = (s & 1) ? q.z : q.x, d1 = (s & 1) ? q.w : q.y;
+    return i32x4_t{(int)((d0 << 4) & 0xF0F0F0F0u), (int)(d0 & 0xF0F0F0F0u),
+                   (int)((d1 << 4) & 0xF0F0F0F0u), (int)(d1 & 0xF0F0F0F0u)};
+  }
+  static __device__ __forceinline__ Acc mfma(const uint4& a, const i32x4_t& b, Acc c) {
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, a), b, c, 0, 0, 0);
+  }
+  // fp32(fp32(fp32(acc) * xs) * ws), acc the sum without the expansion's 16; the bias add and
+  // the one bf16 rounding follow in the kernel. No contraction, as Fp8Dyn::epi.
+  static constexpr bool kRowF = true, kColF = true;
+  __device__ __forceinline__ const float* row_factor() const { return xscale; }
+  __device__ __forceinline__ const float* col_factor() const { return wscale; }
+  __device__ __forceinline__ float epi(int acc, float xs, float ws) const {
+#pragma clang fp contract(off)
+    return ((float)(acc >> 4) * xs) * ws;
   }
 };
 

@@ -51,7 +51,7 @@ int launch_gemm32_int4(const uint16_t* x, const uint32_t* packed, const uint16_t
                        hipStream_t stream, int tbm = 0, int tsplits = 0);
 
 // gemm_mfma.hip: the skinny-M crossovers and the MFMA launches of the scaled-mm entries
-// (fp8_dyn.hip, mx_fp8.hip, mx_fp4.hip, block_fp8.hip, int8_dyn.hip)
+// (fp8_dyn.hip, mx_fp8.hip, mx_fp4.hip, block_fp8.hip, int8_dyn.hip, w4a8.hip)
 bool int4_linear_takes_gemv(int64_t M, int64_t N, int64_t K);
 bool fp8dyn_takes_gemv(int64_t M, int64_t N, int64_t K);
 bool mx_takes_gemv(int64_t M, int64_t N, int64_t K);
@@ -71,5 +71,8 @@ int blockfp8_scaled_mm_launch(const uint8_t* xq, const float* xs, const uint8_t*
 int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq,
                           const uint16_t* ws, const uint16_t* bias, uint16_t* y, int M, int N,
                           int K, hipStream_t stream);
+int w4a8_scaled_mm_launch(const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                          const uint16_t* bias, uint16_t* y, int M, int N, int K,
+                          hipStream_t stream);
 
 }  // namespace tao

@@ -7,7 +7,9 @@
 // float8 set blockfp8_quantize_act, blockfp8_quantize_weight, blockfp8_dequantize_weight,
 // blockfp8_scaled_mm, blockfp8_dyn_linear, and the activation pre-scale set act_prescale,
 // int4_prescaled_linear, and the SmoothQuant set int8_smooth_quantize_per_token,
-// int8_smooth_quantize_static, int8_smooth_dyn_linear, int8_smooth_static_linear.
+// int8_smooth_quantize_static, int8_smooth_dyn_linear, int8_smooth_static_linear, and the W4A8 set
+// rowwise_scaled_linear_cutlass_s8s4, int8_quantize_per_token_f32, int4_quantize_rows_packed,
+// w4a8_dyn_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -841,9 +843,130 @@ Tensor blockfp8_dyn_linear(const Tensor& x, const Tensor& wq, const Tensor& w_sc
   return y.reshape(out_shape(x, N));
 }
 
+// ---- W4A8: int8 dynamic activation x packed int4 weight (ops.py _w4a8_scaled_mm_cuda & co) ------
+void check_w4a8_weight(const Tensor& w, const Tensor& w_scale) {
+  TORCH_CHECK(w.dim() == 2 && (w.scalar_type() == at::kChar || w.scalar_type() == at::kByte),
+              "weight must be a 2D int8 [N, K/2] tensor of packed int4 codes");
+  TORCH_CHECK(w_scale.scalar_type() == at::kFloat, "weight_scale must be float32");
+  TORCH_CHECK(w_scale.dim() == 1 && w_scale.numel() == w.size(0),
+              "weight_scale must be [N] = (", w.size(0), "), got ", w_scale.sizes());
+  TORCH_CHECK((w.size(1) * 2) % 32 == 0, "K (", w.size(1) * 2, ") must be a multiple of 32");
+}
+
+Tensor rowwise_scaled_linear_cutlass_s8s4(const Tensor& input, const Tensor& input_scale,
+                                          const Tensor& weight, const Tensor& weight_scale,
+                                          const std::optional<Tensor>& bias,
+                                          std::optional<at::ScalarType> out_dtype) {
+  check_w4a8_weight(weight, weight_scale);
+  const int64_t N = weight.size(0), K = weight.size(1) * 2;
+  TORCH_CHECK(input.scalar_type() == at::kChar, "input must be int8");
+  TORCH_CHECK(input_scale.scalar_type() == at::kFloat, "input_scale must be float32");
+  TORCH_CHECK(input.dim() >= 1 && input.size(-1) == K, "input last dim ",
+              input.dim() ? input.size(-1) : 0, " != K ", K);
+  TORCH_CHECK(!out_dtype.has_value() || *out_dtype == at::kBFloat16,
+              "rowwise_scaled_linear_cutlass_s8s4 (HIP) gives bfloat16 output only");
+  TORCH_CHECK(!bias.has_value() || (bias->dim() == 1 && bias->numel() == N),
+              "bias must be [N] = (", N, ")");
+  check_device(input, input_scale, "input_scale");
+  check_device(input, weight, "weight");
+  check_device(input, weight_scale, "weight_scale");
+  check_device(input, bias, "bias");
+  const Tensor x2 = rows_of(input, K);
+  const int64_t M = x2.size(0);
+  const Tensor xs = input_scale.reshape({-1}).contiguous();
+  TORCH_CHECK(xs.numel() == M, "input_scale must have one entry per row");
+  const Tensor w = weight.contiguous();
+  const Tensor ws = weight_scale.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(input.device());
+  Tensor y = at::empty({M, N}, input.options().dtype(at::kBFloat16));
+  check_rc(tao_w4a8_scaled_mm_bf16(cptr<int8_t>(x2), cptr<float>(xs), cptr<uint8_t>(w),
+                                   cptr<float>(ws), b ? cptr<uint16_t>(*b) : nullptr,
+                                   mptr<uint16_t>(y), M, N, K, stream_of(input)),
+           "tao_w4a8_scaled_mm_bf16");
+  return y.reshape(out_shape(input, N));
+}
+
+std::tuple<Tensor, Tensor> int8_quantize_per_token_f32(const Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), "expected x on a HIP device, got ", x.device());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "int8_quantize_per_token_f32 (HIP) needs bf16 x");
+  TORCH_CHECK(x.dim() >= 1, "int8_quantize_per_token_f32: x must have at least one dimension");
+  const int64_t K = x.size(-1);
+  TORCH_CHECK(K % 8 == 0, "K (", K, ") must be a multiple of 8");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor q = at::empty({M, K}, x.options().dtype(at::kChar));
+  Tensor s = at::empty({M}, x.options().dtype(at::kFloat));
+  check_rc(tao_int8_quant_per_token_f32(cptr<uint16_t>(x2), mptr<int8_t>(q), mptr<float>(s), M, K,
+                                        stream_of(x)),
+           "tao_int8_quant_per_token_f32");
+  std::vector<int64_t> ss(x.sizes().begin(), x.sizes().end() - 1);
+  return {q.reshape(x.sizes()), s.reshape(ss)};
+}
+
+std::tuple<Tensor, Tensor> int4_quantize_rows_packed(const Tensor& w) {
+  TORCH_CHECK(w.is_cuda(), "expected w on a HIP device, got ", w.device());
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16, "int4_quantize_rows_packed (HIP) needs a bf16 weight");
+  TORCH_CHECK(w.dim() == 2, "int4_quantize_rows_packed: w must be [N, K]");
+  const int64_t R = w.size(0), K = w.size(1);
+  TORCH_CHECK(K % 8 == 0, "K (", K, ") must be a multiple of 8");
+  const Tensor w2 = rows_of(w, K);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+  Tensor q = at::empty({R, K / 2}, w.options().dtype(at::kChar));
+  Tensor s = at::empty({R}, w.options().dtype(at::kFloat));
+  check_rc(tao_int4_quantize_rows_packed_bf16(cptr<uint16_t>(w2), mptr<uint8_t>(q), mptr<float>(s),
+                                              R, K, stream_of(w)),
+           "tao_int4_quantize_rows_packed_bf16");
+  return {q, s};
+}
+
+Tensor w4a8_dyn_linear(const Tensor& x, const Tensor& weight, const Tensor& weight_scale,
+                       const std::optional<Tensor>& bias) {
+  check_w4a8_weight(weight, weight_scale);
+  const int64_t N = weight.size(0), K = weight.size(1) * 2;
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "w4a8_dyn_linear (HIP) needs bf16 x");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "x last dim ", x.dim() ? x.size(-1) : 0, " != K ",
+              K);
+  TORCH_CHECK(!bias.has_value() || (bias->dim() == 1 && bias->numel() == N),
+              "bias must be [N] = (", N, ")");
+  check_device(x, weight, "weight");
+  check_device(x, weight_scale, "weight_scale");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const Tensor w = weight.contiguous();
+  const Tensor ws = weight_scale.contiguous();
+  const std::optional<Tensor> b = bf16_bias(bias);
+  const uint16_t* bp = b ? cptr<uint16_t>(*b) : nullptr;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  if (M == 1 && K <= 65536) {
+    check_rc(tao_w4a8_dyn_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(w), cptr<float>(ws), bp,
+                                      mptr<uint16_t>(y), 1, N, K, stream_of(x)),
+             "tao_w4a8_dyn_linear_bf16");
+  } else if (M > 0) {
+    // the codes live in a buffer of the caching allocator between the two launches
+    Tensor q = at::empty({M, K}, x.options().dtype(at::kChar));
+    Tensor s = at::empty({M}, x.options().dtype(at::kFloat));
+    check_rc(tao_int8_quant_per_token_f32(cptr<uint16_t>(x2), mptr<int8_t>(q), mptr<float>(s), M,
+                                          K, stream_of(x)),
+             "tao_int8_quant_per_token_f32");
+    check_rc(tao_w4a8_scaled_mm_bf16(cptr<int8_t>(q), cptr<float>(s), cptr<uint8_t>(w),
+                                     cptr<float>(ws), bp, mptr<uint16_t>(y), M, N, K,
+                                     stream_of(x)),
+             "tao_w4a8_scaled_mm_bf16");
+  }
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
+  m.impl("rowwise_scaled_linear_cutlass_s8s4", &rowwise_scaled_linear_cutlass_s8s4);
+  m.impl("int8_quantize_per_token_f32", &int8_quantize_per_token_f32);
+  m.impl("int4_quantize_rows_packed", &int4_quantize_rows_packed);
+  m.impl("w4a8_dyn_linear", &w4a8_dyn_linear);
   m.impl("blockfp8_quantize_act", &blockfp8_quantize_act);
   m.impl("blockfp8_quantize_weight", &blockfp8_quantize_weight);
   m.impl("blockfp8_dequantize_weight", &blockfp8_dequantize_weight);
@@ -909,6 +1032,12 @@ extern "C" const char* tao_torch_ops_served_awq(void) {
 extern "C" const char* tao_torch_ops_served_smoothquant(void) {
   return "int8_smooth_quantize_per_token,int8_smooth_quantize_static,int8_smooth_dyn_linear,"
          "int8_smooth_static_linear";
+}
+
+// The W4A8 ops served here, a set of their own as well.
+extern "C" const char* tao_torch_ops_served_w4a8(void) {
+  return "rowwise_scaled_linear_cutlass_s8s4,int8_quantize_per_token_f32,"
+         "int4_quantize_rows_packed,w4a8_dyn_linear";
 }
 
 // The MXFP4-weight ops served here, a set of their own as well.

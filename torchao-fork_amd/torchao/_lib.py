@@ -87,6 +87,10 @@ _SIGNATURES = {
     "tao_int8_smooth_quant_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _p],
     "tao_int8_smooth_linear_bf16": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_int8_smooth_linear_fused": [_i64, _i64, _i64, _int],
+    "tao_int8_quant_per_token_f32": [_p, _p, _p, _i64, _i64, _p],
+    "tao_int4_quantize_rows_packed_bf16": [_p, _p, _p, _i64, _i64, _p],
+    "tao_w4a8_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_w4a8_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_tune_int8_gemv": [_int, _int, _int],
     "tao_tune_int8_quant": [_int],
     "tao_fp8wo_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],

@@ -14,7 +14,13 @@ from .affine_quantized_tensor_ops import (
     register_aqt_quantized_linear_dispatch,
 )
 from .floatx import Float8AQTTensorImpl, Float8Layout, Float8MMConfig
-from .uintx import PlainAQTTensorImpl, TensorCoreTiledAQTTensorImpl, TensorCoreTiledLayout
+from .uintx import (
+    CutlassInt4PackedLayout,
+    Int4PackedTensorImpl,
+    PlainAQTTensorImpl,
+    TensorCoreTiledAQTTensorImpl,
+    TensorCoreTiledLayout,
+)
 from .utils import AQTTensorImpl, Layout, PlainLayout
 
 __all__ = [
@@ -25,6 +31,8 @@ __all__ = [
     "PlainAQTTensorImpl",
     "TensorCoreTiledLayout",
     "TensorCoreTiledAQTTensorImpl",
+    "CutlassInt4PackedLayout",
+    "Int4PackedTensorImpl",
     "Float8Layout",
     "Float8AQTTensorImpl",
     "Float8MMConfig",

@@ -54,7 +54,12 @@ def _fused_weight_quant(x, mapping_type, block_size, target_dtype, quant_min, qu
         False, [0, 15], blocks (1, ..., g) -> torchao::int4_quantize_pack straight into the
         TensorCoreTiledLayout impl (no int32 [N, K] intermediate, no separate pack);
       * int8 symmetric per row (Int8WeightOnlyConfig, int8 dyn weights): SYMMETRIC, blocks
-        (1, ..., K), [-128, 127] -> torchao::int8_quantize_rows into the PlainLayout impl."""
+        (1, ..., K), [-128, 127] -> torchao::int8_quantize_rows into the PlainLayout impl;
+      * the two W4A8 recipes (Int8DynamicActivationInt4WeightConfig with CutlassInt4PackedLayout):
+        SYMMETRIC per row, no zero point, float32 scale, eps = finfo(float32).eps; int8 into
+        PlainLayout (the activation) -> torchao::int8_quantize_per_token_f32, [-8, 7] into
+        CutlassInt4PackedLayout (the weight) -> torchao::int4_quantize_rows_packed
+        (tests/test_gpu_w4a8.py)."""
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() in (2, 3) and eps is not None):
         return None
     if any(b != 1 for b in block_size[:-1]):
@@ -100,6 +105,32 @@ def _fused_weight_quant(x, mapping_type, block_size, target_dtype, quant_min, qu
         return AffineQuantizedTensor.get_tensor_impl_constructor(type(layout))(
             q, scale, zero_point, layout
         )
+    # The two W4A8 recipes (quant_api._int8_symm_cutlass_quant / _int4_symm_cutlass_quant):
+    # SYMMETRIC per row, no zero point, float32 scale clamped at finfo(float32).eps.
+    w4a8 = (
+        mapping_type is MappingType.SYMMETRIC
+        and zero_point_domain == ZeroPointDomain.NONE
+        and preserve_zero
+        and target_dtype == torch.int8
+        and g == K
+        and K % 8 == 0
+        and scale_dtype == torch.float32
+        and float(eps) == float(torch.finfo(torch.float32).eps)
+    )
+    if w4a8 and type(layout) is PlainLayout and quant_min in (None, -128) and quant_max in (None, 127):
+        q, scale = torch.ops.torchao.int8_quantize_per_token_f32(x)
+        return AffineQuantizedTensor.get_tensor_impl_constructor(type(layout))(
+            q, scale, None, layout
+        )
+    from torchao.dtypes.uintx.cutlass_int4_packed_layout import (
+        CutlassInt4PackedLayout,
+        Int4PackedTensorImpl,
+    )
+
+    if (w4a8 and isinstance(layout, CutlassInt4PackedLayout) and x.dim() == 2
+            and (quant_min, quant_max) == (-8, 7)):
+        packed, scale = torch.ops.torchao.int4_quantize_rows_packed(x)
+        return Int4PackedTensorImpl(packed, scale, layout)
     return None
 
 

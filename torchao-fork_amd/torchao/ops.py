@@ -60,6 +60,14 @@ Operators:
   * ``int8_smooth_dyn_linear`` / ``int8_smooth_static_linear`` — those and ``int8_scaled_mm``
     from a bf16 input at any M (one token up to K = 16384, static 8192: one launch, the division
     and the quantisation in the GEMV's prologue), bit-identical to the two ops.
+  * ``rowwise_scaled_linear_cutlass_s8s4`` — the reference's op name and schema (ops.py:28-30) for
+    int8 activations x packed int4 weights with fp32 row scales, on the int8 matrix cores
+    (csrc/w4a8.hip); the reference builds it for sm80 only.
+  * ``int8_quantize_per_token_f32`` / ``int4_quantize_rows_packed`` — its two quantizers,
+    ``_int8_symm_cutlass_quant`` and ``_int4_symm_cutlass_quant`` (quant_api.py:1299-1323), one
+    launch each, byte for byte.
+  * ``w4a8_dyn_linear`` — the activation quantisation and the product from a bf16 input (one
+    token: one launch), bit-identical to the two ops.
 """
 
 import ctypes
@@ -183,6 +191,18 @@ lib_smoothquant.define(
 lib_smoothquant.define(
     "int8_smooth_static_linear(Tensor x, Tensor smooth, Tensor act_scale, Tensor w_int8, "
     "Tensor w_scale, Tensor? bias=None) -> Tensor")
+# The W4A8 ops (Int8DynamicActivationInt4WeightConfig with CutlassInt4PackedLayout; csrc/w4a8.hip),
+# on a fragment of their own; opchecked in tests/test_gpu_w4a8.py. The first is the reference's
+# schema and name (torchao/ops.py:28-30, 666-695), served here on gfx950. Weight codes cross as int8
+# [N, K/2], two int4 per byte; all scales are float32.
+lib_w4a8 = torch.library.Library("torchao", "FRAGMENT")
+lib_w4a8.define(
+    "rowwise_scaled_linear_cutlass_s8s4(Tensor input, Tensor input_scale, Tensor weight, "
+    "Tensor weight_scale, Tensor? bias=None, ScalarType? out_dtype=None) -> Tensor")
+lib_w4a8.define("int8_quantize_per_token_f32(Tensor x) -> (Tensor, Tensor)")
+lib_w4a8.define("int4_quantize_rows_packed(Tensor w) -> (Tensor, Tensor)")
+lib_w4a8.define(
+    "w4a8_dyn_linear(Tensor x, Tensor weight, Tensor weight_scale, Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -1462,6 +1482,153 @@ def _blockfp8_dyn_linear_cuda(x, wq, w_scale, bias=None):
 
 
 # ---- register device impls ------------------------------------------------------------------
+# ---------------------------------------------------------------------------------------------
+# W4A8: int8 dynamic activation x packed int4 weight (csrc/w4a8.hip)
+# ---------------------------------------------------------------------------------------------
+def _check_w4a8_weight(weight, weight_scale):
+    torch._check(weight.dim() == 2 and weight.dtype in (torch.int8, torch.uint8),
+                 lambda: "weight must be a 2D int8 [N, K/2] tensor of packed int4 codes")
+    torch._check(weight_scale.dtype is torch.float32, lambda: "weight_scale must be float32")
+    N, K = weight.size(0), weight.size(1) * 2
+    torch._check(weight_scale.dim() == 1 and weight_scale.numel() == N,
+                 lambda: f"weight_scale must be [N] = ({N}), got {tuple(weight_scale.shape)}")
+    torch._check(K % 32 == 0, lambda: f"K ({K}) must be a multiple of 32")
+    return N, K
+
+
+def _check_w4a8_bias(bias, N):
+    torch._check(bias is None or (bias.dim() == 1 and bias.numel() == N),
+                 lambda: f"bias must be [N] = ({N})")
+
+
+@torch.library.register_fake("torchao::rowwise_scaled_linear_cutlass_s8s4")
+def _(input, input_scale, weight, weight_scale, bias=None, out_dtype=None):
+    N, K = _check_w4a8_weight(weight, weight_scale)
+    torch._check(input.dtype is torch.int8, lambda: "input must be int8")
+    torch._check(input.size(-1) == K, lambda: f"input last dim {input.size(-1)} != K {K}")
+    torch._check(out_dtype in (None, torch.bfloat16),
+                 lambda: "rowwise_scaled_linear_cutlass_s8s4 (HIP) gives bfloat16 output only")
+    return input.new_empty(_linear_out_shape(input, N), dtype=torch.bfloat16)
+
+
+def _w4a8_scaled_mm_cuda(input, input_scale, weight, weight_scale, bias=None, out_dtype=None):
+    """y = bf16(fp32(int32 acc) * input_scale[m] * weight_scale[n] + bias), fp32 up to the one
+    rounding (include/torchao_mi355x.h tao_w4a8_scaled_mm_bf16)."""
+    N, K = _check_w4a8_weight(weight, weight_scale)
+    torch._check(input.dtype is torch.int8, lambda: "input must be int8")
+    torch._check(input_scale.dtype is torch.float32, lambda: "input_scale must be float32")
+    torch._check(input.size(-1) == K, lambda: f"input last dim {input.size(-1)} != K {K}")
+    torch._check(out_dtype in (None, torch.bfloat16),
+                 lambda: "rowwise_scaled_linear_cutlass_s8s4 (HIP) gives bfloat16 output only")
+    _check_w4a8_bias(bias, N)
+    _same_device(input, input_scale=input_scale, weight=weight, weight_scale=weight_scale,
+                 bias=bias)
+    x2 = input.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    xs = input_scale.reshape(-1).contiguous()
+    torch._check(xs.numel() == M, lambda: "input_scale must have one entry per row")
+    weight = weight.contiguous()
+    ws = weight_scale.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=input.device)
+    with torch.cuda.device(input.device):
+        _lib.call("tao_w4a8_scaled_mm_bf16", _ptr(x2), _ptr(xs), _ptr(weight), _ptr(ws),
+                  _ptr(bias), _ptr(y), M, N, K, _stream(input))
+    return y.reshape(_linear_out_shape(input, N))
+
+
+@torch.library.register_fake("torchao::int8_quantize_per_token_f32")
+def _(x):
+    torch._check(x.size(-1) % 8 == 0, lambda: f"K ({x.size(-1)}) must be a multiple of 8")
+    return (x.new_empty(x.shape, dtype=torch.int8),
+            x.new_empty(x.shape[:-1], dtype=torch.float32))
+
+
+def _int8_quant_f32_cuda(x: Tensor):
+    """bf16 x [..., K] -> (int8 [..., K], per-token scale fp32 [...]): _int8_symm_cutlass_quant."""
+    torch._check(x.dtype is torch.bfloat16,
+                 lambda: "int8_quantize_per_token_f32 (HIP) needs bf16 x")
+    K = x.size(-1)
+    torch._check(K % 8 == 0, lambda: f"K ({K}) must be a multiple of 8")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    q = torch.empty((M, K), dtype=torch.int8, device=x.device)
+    s = torch.empty((M,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("tao_int8_quant_per_token_f32", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+    return q.reshape(x.shape), s.reshape(x.shape[:-1])
+
+
+@torch.library.register_fake("torchao::int4_quantize_rows_packed")
+def _(w):
+    torch._check(w.dim() == 2, lambda: "int4_quantize_rows_packed: w must be [N, K]")
+    torch._check(w.size(1) % 8 == 0, lambda: f"K ({w.size(1)}) must be a multiple of 8")
+    return (w.new_empty((w.size(0), w.size(1) // 2), dtype=torch.int8),
+            w.new_empty((w.size(0),), dtype=torch.float32))
+
+
+def _int4_quantize_rows_packed_cuda(w: Tensor):
+    """bf16 W [N, K] -> (int8 [N, K/2] packed int4 codes, per-row scale fp32 [N]):
+    _int4_symm_cutlass_quant and CutlassInt4PackedLayout's from_plain in one pass."""
+    torch._check(w.dtype is torch.bfloat16,
+                 lambda: "int4_quantize_rows_packed (HIP) needs a bf16 weight")
+    torch._check(w.dim() == 2, lambda: "int4_quantize_rows_packed: w must be [N, K]")
+    R, K = w.shape
+    torch._check(K % 8 == 0, lambda: f"K ({K}) must be a multiple of 8")
+    if not w.is_contiguous() or w.data_ptr() % 16:
+        w = w.contiguous()
+    q = torch.empty((R, K // 2), dtype=torch.int8, device=w.device)
+    s = torch.empty((R,), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("tao_int4_quantize_rows_packed_bf16", _ptr(w), _ptr(q), _ptr(s), R, K,
+                  _stream(w))
+    return q, s
+
+
+@torch.library.register_fake("torchao::w4a8_dyn_linear")
+def _(x, weight, weight_scale, bias=None):
+    N, K = _check_w4a8_weight(weight, weight_scale)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N), dtype=torch.bfloat16)
+
+
+def _w4a8_dyn_linear_cuda(x, weight, weight_scale, bias=None):
+    """The whole linear from a bf16 activation. One token: quantisation + GEMV in one launch.
+    More: int8_quantize_per_token_f32 into a buffer of the caching allocator, then the scaled mm;
+    bit-identical to calling the two ops."""
+    N, K = _check_w4a8_weight(weight, weight_scale)
+    torch._check(x.dtype is torch.bfloat16, lambda: "w4a8_dyn_linear (HIP) needs bf16 x")
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    _check_w4a8_bias(bias, N)
+    _same_device(x, weight=weight, weight_scale=weight_scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    weight = weight.contiguous()
+    ws = weight_scale.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if M == 1 and K <= 65536:
+            _lib.call("tao_w4a8_dyn_linear_bf16", _ptr(x2), _ptr(weight), _ptr(ws), _ptr(bias),
+                      _ptr(y), 1, N, K, _stream(x))
+        elif M > 0:
+            q = torch.empty((M, K), dtype=torch.int8, device=x.device)
+            s = torch.empty((M,), dtype=torch.float32, device=x.device)
+            _lib.call("tao_int8_quant_per_token_f32", _ptr(x2), _ptr(q), _ptr(s), M, K,
+                      _stream(x))
+            _lib.call("tao_w4a8_scaled_mm_bf16", _ptr(q), _ptr(s), _ptr(weight), _ptr(ws),
+                      _ptr(bias), _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
 # M = 1, profiles/r2_eager_overhead*.json). The Python impls below serve the rest, and these
@@ -1476,6 +1643,7 @@ _native_served_mxfp4: frozenset = frozenset()
 _native_served_blockfp8: frozenset = frozenset()
 _native_served_awq: frozenset = frozenset()
 _native_served_smoothquant: frozenset = frozenset()
+_native_served_w4a8: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -1507,6 +1675,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_smoothquant
         _served.restype = ctypes.c_char_p
         _native_served_smoothquant = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_w4a8
+        _served.restype = ctypes.c_char_p
+        _native_served_w4a8 = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -1550,6 +1721,11 @@ def native_dispatch_awq() -> frozenset:
 def native_dispatch_smoothquant() -> frozenset:
     """The SmoothQuant ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_smoothquant
+
+
+def native_dispatch_w4a8() -> frozenset:
+    """The W4A8 ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
+    return _native_served_w4a8
 
 
 for _name, _fn in [
@@ -1620,6 +1796,14 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_smoothquant:
         lib_smoothquant.impl(_name, _fn, "CUDA")
+for _name, _fn in [
+    ("rowwise_scaled_linear_cutlass_s8s4", _w4a8_scaled_mm_cuda),
+    ("int8_quantize_per_token_f32", _int8_quant_f32_cuda),
+    ("int4_quantize_rows_packed", _int4_quantize_rows_packed_cuda),
+    ("w4a8_dyn_linear", _w4a8_dyn_linear_cuda),
+]:
+    if _name not in _native_served_w4a8:
+        lib_w4a8.impl(_name, _fn, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")
@@ -1650,6 +1834,21 @@ def pack_tensor_core_tiled_layout(int_data: Tensor, inner_k_tiles: int,
     aten._convert_weight_to_int4pack of the same nibbles, bit for bit)."""
     return torch.ops.torchao.pack_tensor_core_tiled_layout.default(
         int_data, inner_k_tiles, _tile_format(tile_format))
+
+
+def rowwise_scaled_linear_cutlass_s8s4(
+    input: Tensor,
+    input_scale: Tensor,
+    weight: Tensor,
+    weight_scale: Tensor,
+    bias: Optional[Tensor] = None,
+    out_dtype: Optional[torch.dtype] = None,
+) -> Tensor:
+    """The reference's wrapper (torchao/ops.py:666-695): int8 ``input`` [..., K] with per-row fp32
+    ``input_scale`` [...], int4 ``weight`` packed two per byte in int8 [N, K/2] with per-row fp32
+    ``weight_scale`` [N]; bf16 output. Served by the gfx950 kernels of csrc/w4a8.hip."""
+    return torch.ops.torchao.rowwise_scaled_linear_cutlass_s8s4.default(
+        input, input_scale, weight, weight_scale, bias, out_dtype)
 
 
 def int4_weight_only_linear(x, packed_w, scales_and_zeros, group_size, bias=None):

@@ -14,12 +14,14 @@ from torchao.quantization.quant_api import (
     Float8DynamicActivationFloat8WeightConfig,
     Float8WeightOnlyConfig,
     Int4WeightOnlyConfig,
+    Int8DynamicActivationInt4WeightConfig,
     Int8DynamicActivationInt8WeightConfig,
     Int8WeightOnlyConfig,
     ModuleFqnToConfig,
     float8_dynamic_activation_float8_weight,
     float8_weight_only,
     int4_weight_only,
+    int8_dynamic_activation_int4_weight,
     int8_dynamic_activation_int8_weight,
     int8_weight_only,
     quantize_,
@@ -40,6 +42,7 @@ __all__ = [
     "Int4WeightOnlyConfig",
     "Int8WeightOnlyConfig",
     "Int8DynamicActivationInt8WeightConfig",
+    "Int8DynamicActivationInt4WeightConfig",
     "Float8WeightOnlyConfig",
     "Float8DynamicActivationFloat8WeightConfig",
     "PerAxis",
@@ -49,6 +52,7 @@ __all__ = [
     "int4_weight_only",
     "int8_weight_only",
     "int8_dynamic_activation_int8_weight",
+    "int8_dynamic_activation_int4_weight",
     "float8_weight_only",
     "float8_dynamic_activation_float8_weight",
     "LinearActivationQuantizedTensor",

@@ -142,8 +142,38 @@ def _fused_fp8_dyn_decode(x, weight_tensor, bias):
     return torch.ops.torchao.fp8_dyn_linear(x, impl.float8_data, impl.scale.reshape(-1), bias)
 
 
+def _fused_w4a8_dyn_decode(x, weight_tensor, bias):
+    """The same for Int8DynamicActivationInt4WeightConfig(layout=CutlassInt4PackedLayout()): one
+    bf16 token on the GPU goes through ``torch.ops.torchao.w4a8_dyn_linear`` (per-token int8
+    quantisation + int8 x int4 GEMV in one launch), bit-identical to quantising the input and
+    dispatching to ``_linear_int8_act_int4_weight_cutlass_impl``."""
+    from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
+    from torchao.dtypes.uintx.cutlass_int4_packed_layout import (
+        CutlassInt4PackedLayout,
+        _aqt_is_int4,
+    )
+    from torchao.quantization.quant_api import _int8_symm_cutlass_quant
+
+    if weight_tensor.input_quant_func is not _int8_symm_cutlass_quant:
+        return None
+    if weight_tensor.quant_kwargs or type(x) is not torch.Tensor:
+        return None
+    K = x.shape[-1]
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and K % 32 == 0 and x.numel() == K
+            and x.dim() >= 2 and K <= 65536):
+        return None
+    w = weight_tensor.original_weight_tensor
+    if not (isinstance(w, AffineQuantizedTensor) and isinstance(w._layout, CutlassInt4PackedLayout)
+            and _aqt_is_int4(w) and w.dtype == torch.bfloat16 and len(w.shape) == 2
+            and w.shape[1] == K and w.tensor_impl.int_data.is_cuda
+            and (bias is None or (bias.dtype == torch.bfloat16 and bias.dim() == 1))):
+        return None
+    impl = w.tensor_impl
+    return torch.ops.torchao.w4a8_dyn_linear(x, impl.int_data, impl.scale, bias)
+
+
 # the one-token recipes tried before the reference path, in order
-_FUSED_ONE_TOKEN = (_fused_int8_dyn_decode, _fused_fp8_dyn_decode)
+_FUSED_ONE_TOKEN = (_fused_int8_dyn_decode, _fused_fp8_dyn_decode, _fused_w4a8_dyn_decode)
 
 implements = LinearActivationQuantizedTensor.implements
 

@@ -10,6 +10,10 @@ Configs on the MI355X hot path, with the reference defaults:
 * ``Int8WeightOnlyConfig`` (:1200-1255): int8 symmetric per-channel -> int8 GEMV / MFMA;
 * ``Int8DynamicActivationInt8WeightConfig`` (:1352-1449): int8 per-channel weight + per-token
   reduced-range int8 activation quantized on the fly -> HIP quant kernel + int8 MFMA GEMM;
+* ``Int8DynamicActivationInt4WeightConfig`` (:608-708) with ``CutlassInt4PackedLayout()`` and
+  symmetric activations: int4 per-channel weight packed two per byte + per-token int8 activation,
+  fp32 scales -> HIP quant kernels + int8 GEMV / MFMA (``rowwise_scaled_linear_cutlass_s8s4``);
+  its other layouts raise;
 * ``Float8WeightOnlyConfig`` (:1465-1530): e4m3fn symmetric per-channel, fp32 scales,
   ``Float8Layout`` -> fp8 GEMV / MFMA. Its ``version`` defaults to 1 here (the
   ``AffineQuantizedTensor`` form); the reference's default 2 (``Float8Tensor``) raises.
@@ -34,6 +38,7 @@ from torchao.dtypes.affine_quantized_tensor import (
     to_affine_quantized_intx,
 )
 from torchao.dtypes.floatx.float8_layout import Float8Layout, Float8MMConfig
+from torchao.dtypes.uintx.cutlass_int4_packed_layout import CutlassInt4PackedLayout
 from torchao.dtypes.uintx.plain_layout import PlainAQTTensorImpl
 from torchao.dtypes.uintx.tensor_core_tiled_layout import TensorCoreTiledLayout
 from torchao.dtypes.utils import Layout, PlainLayout
@@ -59,6 +64,8 @@ __all__ = [
     "int8_weight_only",
     "Int8DynamicActivationInt8WeightConfig",
     "int8_dynamic_activation_int8_weight",
+    "Int8DynamicActivationInt4WeightConfig",
+    "int8_dynamic_activation_int4_weight",
     "Float8WeightOnlyConfig",
     "float8_weight_only",
     "Float8DynamicActivationFloat8WeightConfig",
@@ -180,6 +187,13 @@ def quantize_(
             "Passing a generic Callable to `quantize_` is not supported; pass a workflow config"
         )
     handler = _QUANTIZE_CONFIG_HANDLER[type(config)]
+    # a handler may bring a precheck(module, config): what it refuses is raised for every
+    # selected module before the first weight is swapped
+    precheck = getattr(handler, "precheck", None)
+    if precheck is not None:
+        for fqn, mod in model.named_modules():
+            if filter_fn(mod, fqn):
+                precheck(mod, config)
     _replace_with_custom_fn_if_matches_filter(
         model, handler, filter_fn, device=device, extra_args=(config,)
     )
@@ -406,6 +420,124 @@ def _int8_dynamic_activation_int8_weight_transform(
     return _swap_weight(
         module, _int8_dynamic_activation_int8_weight_quantize_tensor(module.weight, config)
     )
+
+
+# ---------------------------------------------------------------------------------------------
+# int8 dynamic activation x int4 weight (W4A8, CutlassInt4PackedLayout)
+# ---------------------------------------------------------------------------------------------
+def _int8_symm_cutlass_quant(x: torch.Tensor) -> torch.Tensor:
+    """Per-token symmetric int8 in [-128, 127] with a float32 scale, eps = finfo(float32).eps and
+    no zero point (reference quant_api.py:1299-1308). bf16 activations on the GPU take the fused
+    HIP kernel inside ``to_affine_quantized_intx`` (``torchao::int8_quantize_per_token_f32``),
+    bit-identical to the torch-op formulation."""
+    return to_affine_quantized_intx(
+        x,
+        mapping_type=MappingType.SYMMETRIC,
+        block_size=_get_per_token_block_size(x),
+        target_dtype=torch.int8,
+        scale_dtype=torch.float32,
+        eps=torch.finfo(torch.float32).eps,
+        zero_point_domain=ZeroPointDomain.NONE,
+    )
+
+
+def _int4_symm_cutlass_quant(x: torch.Tensor) -> torch.Tensor:
+    """Per-row symmetric int4 in [-8, 7], float32 scale, packed two per byte
+    (reference quant_api.py:1311-1323); bf16 GPU weights take ``torchao::int4_quantize_rows_packed``."""
+    return to_affine_quantized_intx(
+        x,
+        mapping_type=MappingType.SYMMETRIC,
+        block_size=_get_per_token_block_size(x),
+        target_dtype=torch.int8,
+        quant_min=-8,
+        quant_max=7,
+        scale_dtype=torch.float32,
+        eps=torch.finfo(torch.float32).eps,
+        zero_point_domain=ZeroPointDomain.NONE,
+        _layout=CutlassInt4PackedLayout(),
+    )
+
+
+@dataclass
+class Int8DynamicActivationInt4WeightConfig(AOBaseConfig):
+    """int8 per-token dynamic activation x int4 weight (reference :608-632, same fields and
+    defaults). Served here: ``layout=CutlassInt4PackedLayout()`` with symmetric activations and
+    weights, i.e. ``Int8DynamicActivationInt4WeightConfig(layout=CutlassInt4PackedLayout(),
+    act_mapping_type=MappingType.SYMMETRIC)``, on 2-D bf16 weights with K % 32 == 0. As in the
+    reference, with that layout ``group_size`` only decides whether a linear is skipped
+    (``K % group_size != 0``); the scale is per output channel."""
+
+    group_size: int = 32
+    layout: Layout = PlainLayout()
+    mapping_type: MappingType = MappingType.SYMMETRIC
+    act_mapping_type: MappingType = MappingType.ASYMMETRIC
+    set_inductor_config: bool = True
+
+    def __post_init__(self):
+        torch._C._log_api_usage_once("torchao.quantization.Int8DynamicActivationInt4WeightConfig")
+
+
+int8_dynamic_activation_int4_weight = Int8DynamicActivationInt4WeightConfig
+
+_W4A8_SERVED = (
+    "served: Int8DynamicActivationInt4WeightConfig(layout=CutlassInt4PackedLayout(), "
+    "act_mapping_type=MappingType.SYMMETRIC, mapping_type=MappingType.SYMMETRIC) on 2-D bfloat16 "
+    "weights whose in_features is a multiple of 32"
+)
+
+
+def _w4a8_skips(weight, config) -> bool:
+    group_size = config.group_size
+    if group_size is None or group_size == -1:
+        group_size = weight.shape[-1]
+    return weight.shape[-1] % group_size != 0
+
+
+def _w4a8_precheck(module: nn.Module, config) -> None:
+    """Everything this config refuses, raised before ``quantize_`` swaps any weight."""
+    if not isinstance(config.layout, CutlassInt4PackedLayout):
+        raise NotImplementedError(
+            f"Int8DynamicActivationInt4WeightConfig with layout {config.layout!r} is not "
+            f"implemented on MI355X (the default PlainLayout's forward is dequantize + F.linear in "
+            f"the reference; MarlinQQQLayout and Int8DynamicActInt4WeightCPULayout are other "
+            f"kernels); {_W4A8_SERVED}")
+    if config.act_mapping_type != MappingType.SYMMETRIC:
+        raise NotImplementedError(
+            f"CutlassInt4PackedLayout takes symmetric activations, got act_mapping_type="
+            f"{config.act_mapping_type}; {_W4A8_SERVED}")
+    if config.mapping_type != MappingType.SYMMETRIC:
+        raise NotImplementedError(
+            f"CutlassInt4PackedLayout takes symmetric weights, got mapping_type="
+            f"{config.mapping_type}; {_W4A8_SERVED}")
+    weight = getattr(module, "weight", None)
+    if weight is None or _w4a8_skips(weight, config):
+        return
+    if weight.dim() != 2 or weight.dtype != torch.bfloat16:
+        raise NotImplementedError(
+            f"weight of shape {tuple(weight.shape)} and dtype {weight.dtype}; {_W4A8_SERVED}")
+    if weight.shape[-1] % 32 != 0:
+        raise NotImplementedError(
+            f"in_features {weight.shape[-1]} is not a multiple of 32; {_W4A8_SERVED}")
+
+
+@register_quantize_module_handler(Int8DynamicActivationInt4WeightConfig)
+def _int8_dynamic_activation_int4_weight_transform(
+    module: nn.Module, config: Int8DynamicActivationInt4WeightConfig
+) -> nn.Module:
+    _w4a8_precheck(module, config)
+    if config.set_inductor_config:
+        torchao.quantization.utils.recommended_inductor_config_setter()
+    weight = module.weight
+    if _w4a8_skips(weight, config):
+        return module
+    new_weight = to_linear_activation_quantized(
+        _int4_symm_cutlass_quant(weight), _int8_symm_cutlass_quant
+    )
+    return _swap_weight(module, new_weight)
+
+
+# quantize_ runs this over every selected module before the first swap
+_int8_dynamic_activation_int4_weight_transform.precheck = _w4a8_precheck
 
 
 # ---------------------------------------------------------------------------------------------
@@ -638,3 +770,4 @@ def _float8_dynamic_activation_float8_weight_transform(
 
 
 torch.serialization.add_safe_globals([_input_activation_quant_func_fp8, Float8MMConfig])
+torch.serialization.add_safe_globals([_int8_symm_cutlass_quant, _int4_symm_cutlass_quant])
