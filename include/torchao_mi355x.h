@@ -463,6 +463,47 @@ int tao_w4a8_dyn_linear_bf16(const uint16_t* x, const uint8_t* wq, const float* 
                              const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                              void* stream);
 
+/* ---- NF4 (QLoRA) weight-only (csrc/nf4.hip; torchao/dtypes/nf4tensor.py NF4Tensor) -------------
+ * The flattened weight is cut into blocks of 64; block b has a double-quantized scaler
+ *   s[b] = bf16( bf16( float(qscalers[b]) / qfactor[b / 256] ) + mean ),
+ * qscalers int8 [numel / 64], qfactor bf16 [ceil(numel / 16384)], mean one bf16, and a weight is
+ *   w^ = bf16( levels[code] * s[b] ),
+ * levels the tensor's own 16 bf16 values (never a compiled-in table), codes uint8 [numel / 2] with
+ * element 2 j in the HIGH nibble of byte j. Every operation is the eager torch op on bf16 tensors:
+ * evaluated in fp32, rounded to bf16 once. */
+
+/* First stage of NF4Tensor.from_tensor for w bf16 [numel], numel % 64 == 0, in one read:
+ * absmax[b] = max |w| over block b (bf16; a NaN in the block gives NaN) and the packed codes,
+ *   v = bf16(w / absmax[b]), code = first j minimising bf16(|bf16(v - levels[j])|),
+ * a NaN v (an all-zero block: 0 / 0) taking code 0 as torch.min returns the first NaN. Replaces
+ * get_block_absmax and convert_to_norm_float_weight (torchao/dtypes/nf4tensor.py:544-561, 790-827),
+ * whose quantize_tensor_nearest materialises a numel x 16 difference tensor in chunks; the
+ * double quantization of absmax (n_blocks values) stays torch ops on the device. w 16-B aligned,
+ * codes 4-B aligned. */
+int tao_nf4_quantize_blocks_bf16(const uint16_t* w, const uint16_t* levels, uint8_t* codes,
+                                 uint16_t* absmax, int64_t numel, void* stream);
+
+/* w[i] = w^ of element i for a flat tensor of numel weights (numel % 64 == 0; blocks may straddle
+ * the rows of a 2-D weight), bit-exact to NF4Tensor.get_original_weight (nf4tensor.py:829-855).
+ * codes and levels 4-B aligned, w 16-B aligned. */
+int tao_nf4_dequant_bf16(const uint8_t* codes, const int8_t* qscalers, const uint16_t* qfactor,
+                         const uint16_t* mean, const uint16_t* levels, uint16_t* w, int64_t numel,
+                         void* stream);
+
+/* y[m][n] = bf16( sum_k x[m][k] * w^[n][k] ), the sum in fp32 over the bf16-rounded w^; with a
+ * bias a second rounding, bf16(y + bias[n]) (the reference's out + bias). x bf16 [M][K], the
+ * weight [N][K] row-major in the flat layout above, y bf16 [M][N]. The decode GEMV
+ * (nf4_gemv_kernel): one launch up to 8 tokens, a sequence of 8-token launches beyond. The op
+ * torchao::nf4_linear calls it up to M = 4 and dequantizes + matmuls above
+ * (tao_nf4_linear_route, torchao_mi355x_tune.h). K % 64 == 0 (a row is whole blocks); any N, with
+ * ceil(N K / 16384) factors; M >= 0 (M == 0 is a no-op); x and codes 16-B aligned. Replaces
+ * F.linear(x, weight.to(x.dtype)) of LinearNF4.forward (nf4tensor.py:1037-1042), which rebuilds and
+ * re-reads a bf16 copy of W on every call. */
+int tao_nf4_linear_bf16(const uint16_t* x, const uint8_t* codes, const int8_t* qscalers,
+                        const uint16_t* qfactor, const uint16_t* mean, const uint16_t* levels,
+                        const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                        void* stream);
+
 /* ---- int8 KV cache (AffineQuantizedKVCache, torchao/_models/llama/model.py:198-240) -----------
  * k_cache / v_cache [B][Hkv][T][128] int8 codes, k_scale / v_scale [B][Hkv][T] bf16, one scale per
  * row: symmetric, [-127, 127], eps 1e-5, the arithmetic of _quantize_activation_per_token_absmax in

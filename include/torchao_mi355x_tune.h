@@ -210,6 +210,15 @@ int tao_tune_mx_mfma(int on);
  * tao_tune_linear_crossover moves, the MFMA kernel above it), 1 = the MFMA kernel at every M, so
  * that tests and A/B runs reach it below the crossover too. Calling thread only. */
 int tao_tune_blockfp8_mfma(int on);
+/* The route torchao::nf4_linear takes for this call under the calling thread's tao_tune_nf4:
+ * 1 = the GEMV, tao_nf4_linear_bf16 (M <= 4 by default); 2 = tao_nf4_dequant_bf16 into a temporary
+ * and the bf16 matmul, which needs an allocator and lives in the op (csrc/torch_ops.cpp). */
+int tao_nf4_linear_route(int64_t M, int64_t N, int64_t K);
+/* Route and launch shape of the NF4 linear (calling thread only; tests and A/B runs): route 0 =
+ * built-in rule (tao_nf4_linear_route), 1 = the GEMV at every M, 2 = dequantize + bf16 matmul at
+ * every M; max_gemv_m > 0 moves the built-in boundary; rows per wave 2/4/8 at M == 1, waves along
+ * K and row groups at every M (waves_k * row_groups <= 8; 0 = built-in). */
+int tao_tune_nf4(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups);
 /* Per-token int8 quantisation kernel (A/B only): 0 = one wave per token, the token held in
  * registers (default, K <= 8192); 1 = one 256-thread workgroup per token. Bit-identical. */
 int tao_tune_int8_quant(int block);

@@ -84,6 +84,8 @@ struct Tuning {
   int sf_loaders = 0;  // single-fetch GEMMs: loader waves (0 built-in, 1 off, 2 on, 3 eight)
   int attn_prefill_nw = 0;  // prefill attention: waves per query block (0 built-in, 1, 2, 4)
   int gemv_lds = 0;  // int4 GEMV: minimum dynamic LDS per workgroup (caps residency; tao_tune_int4_lds)
+  int nf4_route = 0, nf4_max_m = 0;              // NF4 linear route and GEMV boundary (tao_tune_nf4)
+  int nf4_rpw = 0, nf4_wk = 0, nf4_g = 0;        // NF4 GEMV launch shape (tao_tune_nf4)
 };
 Tuning& tuning();
 

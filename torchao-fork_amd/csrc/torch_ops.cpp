@@ -9,7 +9,7 @@
 // int4_prescaled_linear, and the SmoothQuant set int8_smooth_quantize_per_token,
 // int8_smooth_quantize_static, int8_smooth_dyn_linear, int8_smooth_static_linear, and the W4A8 set
 // rowwise_scaled_linear_cutlass_s8s4, int8_quantize_per_token_f32, int4_quantize_rows_packed,
-// w4a8_dyn_linear.
+// w4a8_dyn_linear, and the NF4 set nf4_quantize_blocks, nf4_dequantize, nf4_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -26,6 +26,7 @@
 #include <torch/library.h>
 
 #include "../../include/torchao_mi355x.h"
+#include "../../include/torchao_mi355x_tune.h"  // tao_nf4_linear_route
 
 namespace {
 
@@ -960,9 +961,130 @@ Tensor w4a8_dyn_linear(const Tensor& x, const Tensor& weight, const Tensor& weig
   return y.reshape(out_shape(x, N));
 }
 
+// ---- NF4 (QLoRA) weight-only (torchao/dtypes/nf4tensor.py; csrc/nf4.hip) ------------------------
+// The five stored tensors of an NF4Tensor: codes uint8 [numel / 2], qscalers int8 [numel / 64],
+// qfactor bf16 [numel / 16384], mean bf16 0-dim, levels bf16 [16]
+struct Nf4Parts {
+  Tensor codes, qs, qf, mean, levels;
+};
+Nf4Parts check_nf4(const Tensor& codes, const Tensor& qscalers, const Tensor& qfactor,
+                   const Tensor& mean, const Tensor& levels, int64_t numel, const char* op) {
+  TORCH_CHECK(codes.is_cuda(), op, ": expected codes on a HIP device, got ", codes.device());
+  TORCH_CHECK(codes.scalar_type() == at::kByte, op, ": codes must be uint8, got ",
+              codes.scalar_type());
+  TORCH_CHECK(qscalers.scalar_type() == at::kChar, op, ": qscalers must be int8, got ",
+              qscalers.scalar_type());
+  TORCH_CHECK(qfactor.scalar_type() == at::kBFloat16 && mean.scalar_type() == at::kBFloat16 &&
+                  levels.scalar_type() == at::kBFloat16,
+              op, " (HIP) needs bf16 qfactor, mean and levels");
+  TORCH_CHECK(numel % 64 == 0, op, ": numel (", numel, ") must be a multiple of the block size 64");
+  TORCH_CHECK(codes.numel() == numel / 2, op, ": codes must have numel / 2 = ", numel / 2,
+              " bytes, got ", codes.numel());
+  TORCH_CHECK(qscalers.numel() == numel / 64, op, ": qscalers must have numel / 64 = ", numel / 64,
+              " elements, got ", qscalers.numel());
+  TORCH_CHECK(qfactor.numel() == (numel + 16383) / 16384, op,
+              ": qfactor must have ceil(numel / 16384) = ", (numel + 16383) / 16384,
+              " elements, got ", qfactor.numel());
+  TORCH_CHECK(mean.numel() == 1, op, ": mean must have one element, got ", mean.numel());
+  TORCH_CHECK(levels.numel() == 16, op, ": levels must have 16 elements, got ", levels.numel());
+  check_device(codes, qscalers, "qscalers");
+  check_device(codes, qfactor, "qfactor");
+  check_device(codes, mean, "mean");
+  check_device(codes, levels, "levels");
+  auto flat = [](const Tensor& t, uintptr_t align) {
+    Tensor f = t.reshape({-1});
+    if (!f.is_contiguous() || reinterpret_cast<uintptr_t>(f.data_ptr()) % align) f = f.clone();
+    return f;
+  };
+  return {flat(codes, 16), flat(qscalers, 1), flat(qfactor, 2), flat(mean, 2), flat(levels, 4)};
+}
+
+std::tuple<Tensor, Tensor> nf4_quantize_blocks(const Tensor& w, const Tensor& levels) {
+  TORCH_CHECK(w.is_cuda(), "nf4_quantize_blocks: expected w on a HIP device, got ", w.device());
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && levels.scalar_type() == at::kBFloat16,
+              "nf4_quantize_blocks (HIP) needs a bf16 weight and bf16 levels");
+  TORCH_CHECK(levels.numel() == 16, "nf4_quantize_blocks: levels must have 16 elements, got ",
+              levels.numel());
+  check_device(w, levels, "levels");
+  const int64_t numel = w.numel();
+  TORCH_CHECK(numel % 64 == 0, "nf4_quantize_blocks: numel (", numel,
+              ") must be a multiple of the block size 64");
+  Tensor wf = w.reshape({-1});
+  if (!wf.is_contiguous() || reinterpret_cast<uintptr_t>(wf.data_ptr()) % 16) wf = wf.clone();
+  const Tensor lv = levels.reshape({-1}).contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+  Tensor codes = at::empty({numel / 2}, w.options().dtype(at::kByte));
+  Tensor absmax = at::empty({numel / 64}, w.options());
+  check_rc(tao_nf4_quantize_blocks_bf16(cptr<uint16_t>(wf), cptr<uint16_t>(lv),
+                                        mptr<uint8_t>(codes), mptr<uint16_t>(absmax), numel,
+                                        stream_of(w)),
+           "tao_nf4_quantize_blocks_bf16");
+  return {codes, absmax};
+}
+
+Tensor nf4_dequantize_flat(const Nf4Parts& p, int64_t numel) {
+  Tensor w = at::empty({numel}, p.codes.options().dtype(at::kBFloat16));
+  check_rc(tao_nf4_dequant_bf16(cptr<uint8_t>(p.codes), cptr<int8_t>(p.qs), cptr<uint16_t>(p.qf),
+                                cptr<uint16_t>(p.mean), cptr<uint16_t>(p.levels),
+                                mptr<uint16_t>(w), numel, stream_of(p.codes)),
+           "tao_nf4_dequant_bf16");
+  return w;
+}
+
+Tensor nf4_dequantize(const Tensor& codes, const Tensor& qscalers, const Tensor& qfactor,
+                      const Tensor& mean, const Tensor& levels, at::IntArrayRef shape) {
+  int64_t numel = 1;
+  for (const int64_t d : shape) {
+    TORCH_CHECK(d >= 0, "nf4_dequantize: shape must be non-negative, got ", shape);
+    numel *= d;
+  }
+  const Nf4Parts p = check_nf4(codes, qscalers, qfactor, mean, levels, numel, "nf4_dequantize");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(codes.device());
+  return nf4_dequantize_flat(p, numel).reshape(shape);
+}
+
+Tensor nf4_linear(const Tensor& x, const Tensor& codes, const Tensor& qscalers,
+                  const Tensor& qfactor, const Tensor& mean, const Tensor& levels, int64_t N,
+                  const std::optional<Tensor>& bias) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "nf4_linear (HIP) needs bf16 x, got ",
+              x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1, "nf4_linear: x must have at least one dimension");
+  TORCH_CHECK(N >= 0, "nf4_linear: N must be non-negative, got ", N);
+  const int64_t K = x.size(-1);
+  TORCH_CHECK(K > 0 && K % 64 == 0, "nf4_linear: K (", K,
+              ") must be a positive multiple of the block size 64");
+  check_device(x, codes, "codes");
+  const Nf4Parts p = check_nf4(codes, qscalers, qfactor, mean, levels, N * K, "nf4_linear");
+  TORCH_CHECK(!bias.has_value() || bias->numel() == N, "nf4_linear: bias must have N = ", N,
+              " elements");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  if (M > 0 && N > 0 && tao_nf4_linear_route(M, N, K) == 2) {
+    // the reference's own form with a fast dequantizer: W^ into a temporary of the caching
+    // allocator, then the bf16 matmul; the bias is a second rounding, as on the other route
+    const Tensor w = nf4_dequantize_flat(p, N * K).reshape({N, K});
+    Tensor y = at::linear(x2, w);
+    if (b) y = y + *b;
+    return y.reshape(out_shape(x, N));
+  }
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  check_rc(tao_nf4_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(p.codes), cptr<int8_t>(p.qs),
+                               cptr<uint16_t>(p.qf), cptr<uint16_t>(p.mean),
+                               cptr<uint16_t>(p.levels), b ? cptr<uint16_t>(*b) : nullptr,
+                               mptr<uint16_t>(y), M, N, K, stream_of(x)),
+           "tao_nf4_linear_bf16");
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
+  m.impl("nf4_quantize_blocks", &nf4_quantize_blocks);
+  m.impl("nf4_dequantize", &nf4_dequantize);
+  m.impl("nf4_linear", &nf4_linear);
   m.impl("rowwise_scaled_linear_cutlass_s8s4", &rowwise_scaled_linear_cutlass_s8s4);
   m.impl("int8_quantize_per_token_f32", &int8_quantize_per_token_f32);
   m.impl("int4_quantize_rows_packed", &int4_quantize_rows_packed);
@@ -1021,6 +1143,11 @@ extern "C" const char* tao_torch_ops_served_mx(void) {
 extern "C" const char* tao_torch_ops_served_blockfp8(void) {
   return "blockfp8_quantize_act,blockfp8_quantize_weight,blockfp8_dequantize_weight,"
          "blockfp8_scaled_mm,blockfp8_dyn_linear";
+}
+
+// The NF4 ops served here; they have no Python kernels, so torchao.ops requires them.
+extern "C" const char* tao_torch_ops_served_nf4(void) {
+  return "nf4_quantize_blocks,nf4_dequantize,nf4_linear";
 }
 
 // The activation pre-scale ops (AWQ) served here, a set of their own as well.

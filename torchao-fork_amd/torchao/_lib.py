@@ -91,6 +91,11 @@ _SIGNATURES = {
     "tao_int4_quantize_rows_packed_bf16": [_p, _p, _p, _i64, _i64, _p],
     "tao_w4a8_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_w4a8_dyn_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_nf4_quantize_blocks_bf16": [_p, _p, _p, _p, _i64, _p],
+    "tao_nf4_dequant_bf16": [_p, _p, _p, _p, _p, _p, _i64, _p],
+    "tao_nf4_linear_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_nf4_linear_route": [_i64, _i64, _i64],
+    "tao_tune_nf4": [_int, _int, _int, _int, _int],
     "tao_tune_int8_gemv": [_int, _int, _int],
     "tao_tune_int8_quant": [_int],
     "tao_fp8wo_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],

@@ -13,6 +13,7 @@ from .affine_quantized_tensor_ops import (
     deregister_aqt_quantized_linear_dispatch,
     register_aqt_quantized_linear_dispatch,
 )
+from .nf4tensor import NF4Tensor, to_nf4
 from .floatx import Float8AQTTensorImpl, Float8Layout, Float8MMConfig
 from .uintx import (
     CutlassInt4PackedLayout,
@@ -43,4 +44,6 @@ __all__ = [
     "to_affine_quantized_floatx",
     "to_affine_quantized_intx",
     "to_affine_quantized_intx_static",
+    "NF4Tensor",
+    "to_nf4",
 ]

@@ -43,6 +43,8 @@ _KNOBS = {
     "gemm_sf_xmap": ("tao_tune_gemm_sf_xmap", 1),
     "attn_prefill_nw": ("tao_tune_attn_prefill_nw", 1),
     "cnt_stride": ("tao_tune_cnt_stride", 1),
+    # (route 0 auto / 1 gemv / 2 dequant + mm, max_gemv_m, rows per wave, waves along K, row groups)
+    "nf4": ("tao_tune_nf4", 5),
 }
 
 

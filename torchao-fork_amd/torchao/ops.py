@@ -203,6 +203,18 @@ lib_w4a8.define("int8_quantize_per_token_f32(Tensor x) -> (Tensor, Tensor)")
 lib_w4a8.define("int4_quantize_rows_packed(Tensor w) -> (Tensor, Tensor)")
 lib_w4a8.define(
     "w4a8_dyn_linear(Tensor x, Tensor weight, Tensor weight_scale, Tensor? bias=None) -> Tensor")
+# The NF4 ops (NF4Tensor / NF4WeightOnlyConfig, torchao/dtypes/nf4tensor.py; csrc/nf4.hip), on a
+# fragment of their own; opchecked in tests/test_gpu_nf4.py. bf16 HIP tensors only: everything else
+# runs the plain-torch formulation in nf4tensor.py. Their CUDA kernels exist in C++ only
+# (csrc/torch_ops.cpp), so without libtorchao_ops.so a call raises instead of falling back.
+lib_nf4 = torch.library.Library("torchao", "FRAGMENT")
+lib_nf4.define("nf4_quantize_blocks(Tensor w, Tensor levels) -> (Tensor, Tensor)")
+lib_nf4.define(
+    "nf4_dequantize(Tensor codes, Tensor qscalers, Tensor qfactor, Tensor mean, Tensor levels, "
+    "int[] shape) -> Tensor")
+lib_nf4.define(
+    "nf4_linear(Tensor x, Tensor codes, Tensor qscalers, Tensor qfactor, Tensor mean, "
+    "Tensor levels, int N, Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -1629,6 +1641,49 @@ def _w4a8_dyn_linear_cuda(x, weight, weight_scale, bias=None):
     return y.reshape(_linear_out_shape(x, N))
 
 
+# ---------------------------------------------------------------------------------------------
+# NF4 (csrc/nf4.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
+# ---------------------------------------------------------------------------------------------
+def _check_nf4_parts(codes, qscalers, qfactor, mean, levels, numel, op):
+    torch._check(codes.dtype is torch.uint8, lambda: f"{op}: codes must be uint8")
+    torch._check(qscalers.dtype is torch.int8, lambda: f"{op}: qscalers must be int8")
+    torch._check(numel % 64 == 0,
+                 lambda: f"{op}: numel ({numel}) must be a multiple of the block size 64")
+    torch._check(codes.numel() == numel // 2,
+                 lambda: f"{op}: codes must have numel / 2 = {numel // 2} bytes")
+    torch._check(qscalers.numel() == numel // 64,
+                 lambda: f"{op}: qscalers must have numel / 64 = {numel // 64} elements")
+    torch._check(qfactor.numel() == (numel + 16383) // 16384,
+                 lambda: f"{op}: qfactor must have ceil(numel / 16384) elements")
+    torch._check(mean.numel() == 1 and levels.numel() == 16,
+                 lambda: f"{op}: mean must have one element and levels 16")
+
+
+@torch.library.register_fake("torchao::nf4_quantize_blocks")
+def _(w, levels):
+    torch._check(w.numel() % 64 == 0,
+                 lambda: f"nf4_quantize_blocks: numel ({w.numel()}) must be a multiple of 64")
+    return (w.new_empty((w.numel() // 2,), dtype=torch.uint8),
+            w.new_empty((w.numel() // 64,), dtype=torch.bfloat16))
+
+
+@torch.library.register_fake("torchao::nf4_dequantize")
+def _(codes, qscalers, qfactor, mean, levels, shape):
+    numel = 1
+    for d in shape:
+        numel *= d
+    _check_nf4_parts(codes, qscalers, qfactor, mean, levels, numel, "nf4_dequantize")
+    return codes.new_empty(tuple(shape), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("torchao::nf4_linear")
+def _(x, codes, qscalers, qfactor, mean, levels, N, bias=None):
+    K = x.shape[-1]
+    torch._check(K % 64 == 0, lambda: f"nf4_linear: K ({K}) must be a multiple of 64")
+    _check_nf4_parts(codes, qscalers, qfactor, mean, levels, N * K, "nf4_linear")
+    return x.new_empty((*x.shape[:-1], N), dtype=torch.bfloat16)
+
+
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
 # M = 1, profiles/r2_eager_overhead*.json). The Python impls below serve the rest, and these
@@ -1644,6 +1699,7 @@ _native_served_blockfp8: frozenset = frozenset()
 _native_served_awq: frozenset = frozenset()
 _native_served_smoothquant: frozenset = frozenset()
 _native_served_w4a8: frozenset = frozenset()
+_native_served_nf4: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -1678,6 +1734,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_w4a8
         _served.restype = ctypes.c_char_p
         _native_served_w4a8 = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_nf4
+        _served.restype = ctypes.c_char_p
+        _native_served_nf4 = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -1721,6 +1780,11 @@ def native_dispatch_awq() -> frozenset:
 def native_dispatch_smoothquant() -> frozenset:
     """The SmoothQuant ops whose CUDA kernel is C++ (libtorchao_ops.so)."""
     return _native_served_smoothquant
+
+
+def native_dispatch_nf4() -> frozenset:
+    """The NF4 ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
+    return _native_served_nf4
 
 
 def native_dispatch_w4a8() -> frozenset:
