@@ -504,6 +504,41 @@ int tao_nf4_linear_bf16(const uint16_t* x, const uint8_t* codes, const int8_t* q
                         const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                         void* stream);
 
+/* ---- FP6 weight-only (csrc/fp6.hip; FPXWeightOnlyConfig, torchao/dtypes/floatx) ---------------
+ * (ebits, mbits) = (3, 2) or (2, 3), the OCP FP6 formats (no inf, no NaN; max 28 / 7.5); any other
+ * pair is refused. A weight [N][K] is codes uint32 [N][K * 6 / 32], code k of a row at bits
+ * 6 k .. 6 k + 5 of the row's little-endian bit stream (32 codes = 6 dwords), and one bf16 scale
+ * per row. */
+
+/* Per row, in one read of w bf16 [rows][K], K % 32 == 0:
+ *   scale = bf16( max(amax|w|, 1e-12) / max_normal )          the IEEE fp32 quotient
+ *   code  = round-to-nearest-even of float(w) / float(scale), saturated at +-max_normal,
+ *           subnormals and the sign of zero kept
+ * (the reference's _choose_qparams_affine_floatx + _quantize_affine_floatx,
+ * torchao/quantization/quant_primitives.py:2114-2158, bit for bit on finite rows, straight into
+ * the native storage: replaces them and pack_tc_floatx of floatx_tensor_core_layout.py:210-213).
+ * A NaN weight does not enter amax and takes an unspecified code; an inf gives scale = inf
+ * and unspecified codes. w 16-B aligned, codes 8-B aligned. */
+int tao_fp6_quantize_rows_bf16(const uint16_t* w, uint32_t* codes, uint16_t* scale, int64_t rows,
+                               int64_t K, int ebits, int mbits, void* stream);
+
+/* w[n][k] = bf16( float(value(code[n][k])) * float(scale[n]) ), the reference's
+ * _dequantize_affine_floatx (quant_primitives.py:2161-2171) to bf16 bit for bit. K % 32 == 0; codes 8-B aligned, w 16-B aligned. */
+int tao_fp6_dequant_bf16(const uint32_t* codes, const uint16_t* scale, uint16_t* w, int64_t N,
+                         int64_t K, int ebits, int mbits, void* stream);
+
+/* y[m][n] = bf16( float(sum_k x[m][k] * value(code[n][k])) * float(scale[n]) ), the sum in fp32;
+ * with a bias a second rounding, bf16(y + bias[n]). x bf16 [M][K], y bf16 [M][N]. The decode GEMV
+ * (fp6wo_gemv_kernel): one launch up to 8 tokens, a sequence of 8-token launches beyond. The op
+ * torchao::fp6_weight_only_linear calls it up to the boundary of tao_fp6_linear_route
+ * (torchao_mi355x_tune.h) and dequantizes + matmuls above. K % 64 == 0; any N >= 0; M >= 0 (M == 0
+ * is a no-op); x and codes 16-B aligned. Replaces quant_llm_linear of
+ * _linear_f16_bf16_act_floatx_weight_impl (torchao/dtypes/floatx/floatx_tensor_core_layout.py:
+ * 641-666), a CUDA kernel the reference's ROCm build does not compile. */
+int tao_fp6_linear_bf16(const uint16_t* x, const uint32_t* codes, const uint16_t* scale,
+                        const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                        int ebits, int mbits, void* stream);
+
 /* ---- int8 KV cache (AffineQuantizedKVCache, torchao/_models/llama/model.py:198-240) -----------
  * k_cache / v_cache [B][Hkv][T][128] int8 codes, k_scale / v_scale [B][Hkv][T] bf16, one scale per
  * row: symmetric, [-127, 127], eps 1e-5, the arithmetic of _quantize_activation_per_token_absmax in

@@ -219,6 +219,16 @@ int tao_nf4_linear_route(int64_t M, int64_t N, int64_t K);
  * every M; max_gemv_m > 0 moves the built-in boundary; rows per wave 2/4/8 at M == 1, waves along
  * K and row groups at every M (waves_k * row_groups <= 8; 0 = built-in). */
 int tao_tune_nf4(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups);
+/* The route torchao::fp6_weight_only_linear takes for this call under the calling thread's
+ * tao_tune_fp6: 1 = the GEMV, tao_fp6_linear_bf16 (up to the built-in boundary M of
+ * csrc/fp6_host.h); 2 = tao_fp6_dequant_bf16 into a temporary and the bf16 matmul, which needs an
+ * allocator and lives in the op (csrc/torch_ops.cpp). */
+int tao_fp6_linear_route(int64_t M, int64_t N, int64_t K);
+/* Route and launch shape of the FP6 linear (calling thread only; tests and A/B runs): the first
+ * five arguments as tao_tune_nf4's; chunk_groups = 32-code groups per lane chunk of the GEMV:
+ * 0 = built-in, 1 = 24 B (a 2048-code wave slice), 2 = 48 B (a 4096-code wave slice). */
+int tao_tune_fp6(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups,
+                 int chunk_groups);
 /* Per-token int8 quantisation kernel (A/B only): 0 = one wave per token, the token held in
  * registers (default, K <= 8192); 1 = one 256-thread workgroup per token. Bit-identical. */
 int tao_tune_int8_quant(int block);

@@ -86,6 +86,9 @@ struct Tuning {
   int gemv_lds = 0;  // int4 GEMV: minimum dynamic LDS per workgroup (caps residency; tao_tune_int4_lds)
   int nf4_route = 0, nf4_max_m = 0;              // NF4 linear route and GEMV boundary (tao_tune_nf4)
   int nf4_rpw = 0, nf4_wk = 0, nf4_g = 0;        // NF4 GEMV launch shape (tao_tune_nf4)
+  int fp6_route = 0, fp6_max_m = 0;              // FP6 linear route and GEMV boundary (tao_tune_fp6)
+  int fp6_rpw = 0, fp6_wk = 0, fp6_g = 0;        // FP6 GEMV launch shape (tao_tune_fp6)
+  int fp6_groups = 0;                            // FP6 GEMV 32-code groups per lane chunk
 };
 Tuning& tuning();
 

@@ -9,7 +9,8 @@
 // int4_prescaled_linear, and the SmoothQuant set int8_smooth_quantize_per_token,
 // int8_smooth_quantize_static, int8_smooth_dyn_linear, int8_smooth_static_linear, and the W4A8 set
 // rowwise_scaled_linear_cutlass_s8s4, int8_quantize_per_token_f32, int4_quantize_rows_packed,
-// w4a8_dyn_linear, and the NF4 set nf4_quantize_blocks, nf4_dequantize, nf4_linear.
+// w4a8_dyn_linear, and the NF4 set nf4_quantize_blocks, nf4_dequantize, nf4_linear, and the FP6 set
+// fp6_quantize_rows, fp6_dequantize, fp6_weight_only_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -26,7 +27,8 @@
 #include <torch/library.h>
 
 #include "../../include/torchao_mi355x.h"
-#include "../../include/torchao_mi355x_tune.h"  // tao_nf4_linear_route
+#include "../../include/torchao_mi355x_tune.h"  // tao_nf4_linear_route, tao_fp6_linear_route
+#include "fp6_host.h"
 
 namespace {
 
@@ -1079,9 +1081,113 @@ Tensor nf4_linear(const Tensor& x, const Tensor& codes, const Tensor& qscalers,
   return y.reshape(out_shape(x, N));
 }
 
+// ---- FP6 weight-only (torchao/dtypes/floatx/floatx_tensor_core_layout.py; csrc/fp6.hip) ---------
+// codes int32 [N, K * 6 / 32] (native storage), scale bf16 [N]
+void check_fp6_format(int64_t ebits, int64_t mbits, const char* op) {
+  TORCH_CHECK(tao::fp6_format_of(ebits, mbits) >= 0, op, ": (ebits, mbits) = (", ebits, ", ",
+              mbits, ") is not served; served: (3, 2) and (2, 3)");
+}
+
+struct Fp6Weight {
+  Tensor codes, scale;
+  int64_t N, K;
+};
+Fp6Weight check_fp6_weight(const Tensor& codes, const Tensor& scale, const char* op) {
+  TORCH_CHECK(codes.is_cuda(), op, ": expected codes on a HIP device, got ", codes.device());
+  TORCH_CHECK(codes.dim() == 2 && codes.scalar_type() == at::kInt, op,
+              ": codes must be a 2D int32 [N, K * 6 / 32] tensor, got ", codes.scalar_type(), " ",
+              codes.sizes());
+  TORCH_CHECK(codes.size(1) % 6 == 0, op,
+              ": codes must hold whole 32-code groups of 6 dwords, got ", codes.size(1),
+              " dwords per row");
+  const int64_t N = codes.size(0), K = codes.size(1) / 6 * 32;
+  TORCH_CHECK(scale.scalar_type() == at::kBFloat16, op, " (HIP) needs a bf16 scale, got ",
+              scale.scalar_type());
+  TORCH_CHECK(scale.numel() == N, op, ": scale must have N = ", N, " elements, got ",
+              scale.numel());
+  check_device(codes, scale, "scale");
+  Tensor c = codes;
+  if (!c.is_contiguous() || reinterpret_cast<uintptr_t>(c.data_ptr()) % 16) c = c.clone();
+  return {c, scale.reshape({-1}).contiguous(), N, K};
+}
+
+std::tuple<Tensor, Tensor> fp6_quantize_rows(const Tensor& w, int64_t ebits, int64_t mbits) {
+  check_fp6_format(ebits, mbits, "fp6_quantize_rows");
+  TORCH_CHECK(w.is_cuda(), "fp6_quantize_rows: expected w on a HIP device, got ", w.device());
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16, "fp6_quantize_rows (HIP) needs a bf16 weight, got ",
+              w.scalar_type());
+  TORCH_CHECK(w.dim() == 2, "fp6_quantize_rows: w must be 2D, got ", w.dim(), "D");
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(K % 32 == 0, "fp6_quantize_rows: K (", K, ") must be a multiple of 32");
+  Tensor wc = w;
+  if (!wc.is_contiguous() || reinterpret_cast<uintptr_t>(wc.data_ptr()) % 16) wc = wc.clone();
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+  Tensor codes = at::empty({N, tao::fp6_row_dwords(K)}, w.options().dtype(at::kInt));
+  Tensor scale = at::empty({N}, w.options());
+  check_rc(tao_fp6_quantize_rows_bf16(cptr<uint16_t>(wc), mptr<uint32_t>(codes),
+                                      mptr<uint16_t>(scale), N, K, (int)ebits, (int)mbits,
+                                      stream_of(w)),
+           "tao_fp6_quantize_rows_bf16");
+  return {codes, scale};
+}
+
+Tensor fp6_dequantize_checked(const Fp6Weight& p, int64_t ebits, int64_t mbits) {
+  Tensor w = at::empty({p.N, p.K}, p.codes.options().dtype(at::kBFloat16));
+  check_rc(tao_fp6_dequant_bf16(cptr<uint32_t>(p.codes), cptr<uint16_t>(p.scale),
+                                mptr<uint16_t>(w), p.N, p.K, (int)ebits, (int)mbits,
+                                stream_of(p.codes)),
+           "tao_fp6_dequant_bf16");
+  return w;
+}
+
+Tensor fp6_dequantize(const Tensor& codes, const Tensor& scale, int64_t ebits, int64_t mbits) {
+  check_fp6_format(ebits, mbits, "fp6_dequantize");
+  const Fp6Weight p = check_fp6_weight(codes, scale, "fp6_dequantize");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(codes.device());
+  return fp6_dequantize_checked(p, ebits, mbits);
+}
+
+Tensor fp6_weight_only_linear(const Tensor& x, const Tensor& codes, const Tensor& scale,
+                              int64_t ebits, int64_t mbits, const std::optional<Tensor>& bias) {
+  check_fp6_format(ebits, mbits, "fp6_weight_only_linear");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "fp6_weight_only_linear (HIP) needs bf16 x, got ",
+              x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1, "fp6_weight_only_linear: x must have at least one dimension");
+  check_device(x, codes, "codes");
+  const Fp6Weight p = check_fp6_weight(codes, scale, "fp6_weight_only_linear");
+  const int64_t N = p.N, K = p.K;
+  TORCH_CHECK(K > 0 && K % 64 == 0, "fp6_weight_only_linear: K (", K,
+              ") must be a positive multiple of 64");
+  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
+  TORCH_CHECK(!bias.has_value() || bias->numel() == N, "fp6_weight_only_linear: bias must have N = ",
+              N, " elements");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  if (M > 0 && N > 0 && tao_fp6_linear_route(M, N, K) == 2) {
+    // W^ into a temporary of the caching allocator, then the bf16 matmul; the bias is a second
+    // rounding, as on the other route
+    const Tensor w = fp6_dequantize_checked(p, ebits, mbits);
+    Tensor y = at::linear(x2, w);
+    if (b) y = y + *b;
+    return y.reshape(out_shape(x, N));
+  }
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  check_rc(tao_fp6_linear_bf16(cptr<uint16_t>(x2), cptr<uint32_t>(p.codes),
+                               cptr<uint16_t>(p.scale), b ? cptr<uint16_t>(*b) : nullptr,
+                               mptr<uint16_t>(y), M, N, K, (int)ebits, (int)mbits, stream_of(x)),
+           "tao_fp6_linear_bf16");
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
+  m.impl("fp6_quantize_rows", &fp6_quantize_rows);
+  m.impl("fp6_dequantize", &fp6_dequantize);
+  m.impl("fp6_weight_only_linear", &fp6_weight_only_linear);
   m.impl("nf4_quantize_blocks", &nf4_quantize_blocks);
   m.impl("nf4_dequantize", &nf4_dequantize);
   m.impl("nf4_linear", &nf4_linear);
@@ -1148,6 +1254,11 @@ extern "C" const char* tao_torch_ops_served_blockfp8(void) {
 // The NF4 ops served here; they have no Python kernels, so torchao.ops requires them.
 extern "C" const char* tao_torch_ops_served_nf4(void) {
   return "nf4_quantize_blocks,nf4_dequantize,nf4_linear";
+}
+
+// The FP6 ops served here; they have no Python kernels either.
+extern "C" const char* tao_torch_ops_served_fp6(void) {
+  return "fp6_quantize_rows,fp6_dequantize,fp6_weight_only_linear";
 }
 
 // The activation pre-scale ops (AWQ) served here, a set of their own as well.

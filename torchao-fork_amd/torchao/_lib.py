@@ -96,6 +96,11 @@ _SIGNATURES = {
     "tao_nf4_linear_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
     "tao_nf4_linear_route": [_i64, _i64, _i64],
     "tao_tune_nf4": [_int, _int, _int, _int, _int],
+    "tao_fp6_quantize_rows_bf16": [_p, _p, _p, _i64, _i64, _int, _int, _p],
+    "tao_fp6_dequant_bf16": [_p, _p, _p, _i64, _i64, _int, _int, _p],
+    "tao_fp6_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p],
+    "tao_fp6_linear_route": [_i64, _i64, _i64],
+    "tao_tune_fp6": [_int, _int, _int, _int, _int, _int],
     "tao_tune_int8_gemv": [_int, _int, _int],
     "tao_tune_int8_quant": [_int],
     "tao_fp8wo_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],

@@ -5,6 +5,7 @@ from .affine_quantized_tensor import (
     AffineQuantizedTensor,
     register_layout,
     to_affine_quantized_floatx,
+    to_affine_quantized_fpx,
     to_affine_quantized_intx,
     to_affine_quantized_intx_static,
 )
@@ -14,7 +15,13 @@ from .affine_quantized_tensor_ops import (
     register_aqt_quantized_linear_dispatch,
 )
 from .nf4tensor import NF4Tensor, to_nf4
-from .floatx import Float8AQTTensorImpl, Float8Layout, Float8MMConfig
+from .floatx import (
+    Float8AQTTensorImpl,
+    Float8Layout,
+    Float8MMConfig,
+    FloatxTensorCoreAQTTensorImpl,
+    FloatxTensorCoreLayout,
+)
 from .uintx import (
     CutlassInt4PackedLayout,
     Int4PackedTensorImpl,
@@ -41,7 +48,10 @@ __all__ = [
     "register_aqt_quantized_linear_dispatch",
     "deregister_aqt_quantized_linear_dispatch",
     "register_layout",
+    "FloatxTensorCoreLayout",
+    "FloatxTensorCoreAQTTensorImpl",
     "to_affine_quantized_floatx",
+    "to_affine_quantized_fpx",
     "to_affine_quantized_intx",
     "to_affine_quantized_intx_static",
     "NF4Tensor",

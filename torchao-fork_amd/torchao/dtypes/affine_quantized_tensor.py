@@ -4,9 +4,9 @@ Mirrors the reference (torchao/dtypes/affine_quantized_tensor.py:57-614) for the
 workflows on the hot path: ``from_hp_to_intx`` (pre_process -> choose_qparams -> quantize ->
 post_process -> layout constructor, :231-373), ``from_hp_to_intx_static``, ``dequantize``
 (:134-196), flatten/unflatten (:198-229), ``to`` and ``_apply_fn_to_data``, and the float8
-weight-only constructor ``from_hp_to_floatx`` (:449-480; e4m3fn, ``Float8Layout``). The
-static float8, floatx (fp6) and HQQ constructors belong to out-of-scope workflows and are not
-provided.
+weight-only constructor ``from_hp_to_floatx`` (:449-480; e4m3fn, ``Float8Layout``) and the FP6
+constructor ``from_hp_to_fpx`` (:526-553; ``FloatxTensorCoreLayout``). The static float8 and HQQ
+constructors belong to out-of-scope workflows and are not provided.
 """
 
 import logging
@@ -18,8 +18,12 @@ from torchao.dtypes.utils import AQTTensorImpl, Layout, PlainLayout
 from torchao.quantization.quant_primitives import (
     MappingType,
     ZeroPointDomain,
+    FLOATX_SERVED,
     FP8_TYPES,
+    _choose_qparams_affine_floatx,
     _choose_qparams_affine_tinygemm,
+    _dequantize_affine_floatx,
+    _quantize_affine_floatx,
     _choose_scale_float8,
     _dequantize_affine_float8,
     _dequantize_affine_no_zero_point,
@@ -42,6 +46,7 @@ __all__ = [
     "to_affine_quantized_intx",
     "to_affine_quantized_intx_static",
     "to_affine_quantized_floatx",
+    "to_affine_quantized_fpx",
 ]
 
 
@@ -211,6 +216,8 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
     def dequantize(self, output_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """High-precision tensor of ``self.shape``: get_plain() -> the domain's dequant formula."""
         output_dtype = self.dtype if output_dtype is None else output_dtype
+        if hasattr(self.tensor_impl, "packed_floatx_data"):
+            return self._dequantize_floatx(output_dtype)
         data, scale, zero_point = self.tensor_impl.get_plain()
         if data.dtype in FP8_TYPES:
             return self._dequantize_float8(data, scale, output_dtype)
@@ -252,6 +259,17 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
         else:
             dq = _dequantize_affine_float8(data, scale, output_dtype)
         return dq.t() if getattr(self.tensor_impl, "transposed", False) else dq
+
+    def _dequantize_floatx(self, output_dtype):
+        """bf16(fp32(value(code)) * fp32(scale)) of an FP6 weight (_dequantize_affine_floatx,
+        reference :140-148). Native storage on the GPU with a bf16 scale and result runs the HIP
+        kernel (``torchao::fp6_dequantize``), bit-identical to the torch-op formulation."""
+        impl = self.tensor_impl
+        ebits, mbits = impl._layout.ebits, impl._layout.mbits
+        if impl.is_cuda and output_dtype == torch.bfloat16 and impl.scale.dtype == torch.bfloat16:
+            return torch.ops.torchao.fp6_dequantize(impl._native(), impl.scale, ebits, mbits)
+        codes, scale = impl.get_plain()
+        return _dequantize_affine_floatx(codes, scale, ebits, mbits, output_dtype=output_dtype)
 
     def __tensor_flatten__(self):
         with torch._C.DisableTorchFunctionSubclass():
@@ -455,6 +473,48 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
         )
         return cls(tensor_impl, block_size, original_shape, dtype=input_float.dtype)
 
+    @classmethod
+    def from_hp_to_fpx(cls, input_float: torch.Tensor, _layout: Layout):
+        """Quantize a 2-D high-precision tensor into an FP6 AQT (reference :526-553; ``_layout``
+        a ``FloatxTensorCoreLayout`` of (3, 2) or (2, 3)): one scale per row in the tensor's dtype,
+        codes rounded to nearest even and saturated.
+
+        bf16 CUDA weights with K % 32 == 0 run the fused HIP quantizer
+        (``torchao::fp6_quantize_rows``) straight into the native storage; everything else runs
+        the torch-op formulation. The two agree bit for bit on finite rows
+        (tests/test_gpu_fp6.py)."""
+        from torchao.dtypes.floatx.floatx_tensor_core_layout import (
+            FloatxTensorCoreAQTTensorImpl,
+            FloatxTensorCoreLayout,
+        )
+
+        assert isinstance(_layout, FloatxTensorCoreLayout), (
+            f"Only FloatxTensorCoreLayout is supported for floatx, got {_layout}"
+        )
+        ebits, mbits = _layout.ebits, _layout.mbits
+        if (ebits, mbits) not in FLOATX_SERVED:
+            raise NotImplementedError(
+                f"floatx (ebits, mbits) = ({ebits}, {mbits}) is not served; served: the FP6 "
+                f"formats (3, 2) and (2, 3)")
+        assert input_float.dim() == 2, f"floatx only works for 2-d Tensor, got: {input_float.dim()}"
+        original_shape = input_float.shape
+        input_float = _layout.pre_process(input_float)
+        # one scale per row (the reference spells this block size [N, 1])
+        block_size = list(input_float.shape)
+        block_size[1] = 1
+        if (input_float.is_cuda and input_float.dtype == torch.bfloat16
+                and input_float.shape[1] % 32 == 0):
+            packed, scale = torch.ops.torchao.fp6_quantize_rows(input_float, ebits, mbits)
+            tensor_impl = FloatxTensorCoreAQTTensorImpl(packed, scale, _layout)
+        else:
+            scale = _choose_qparams_affine_floatx(input_float, ebits, mbits)
+            codes = _quantize_affine_floatx(input_float, scale, ebits, mbits)
+            codes, scale, _ = _layout.post_process(codes, scale, None, block_size)
+            tensor_impl = cls.get_tensor_impl_constructor(type(_layout))(
+                codes, scale, None, _layout
+            )
+        return cls(tensor_impl, block_size, original_shape, dtype=input_float.dtype)
+
     def to(self, *args, **kwargs):
         kwargs = self._get_to_kwargs(*args, **kwargs)
         device = kwargs.pop("device")
@@ -486,5 +546,6 @@ get_tensor_impl_constructor = AffineQuantizedTensor.get_tensor_impl_constructor
 to_affine_quantized_intx = AffineQuantizedTensor.from_hp_to_intx
 to_affine_quantized_intx_static = AffineQuantizedTensor.from_hp_to_intx_static
 to_affine_quantized_floatx = AffineQuantizedTensor.from_hp_to_floatx
+to_affine_quantized_fpx = AffineQuantizedTensor.from_hp_to_fpx
 
 torch.serialization.add_safe_globals([AffineQuantizedTensor])

@@ -10,7 +10,7 @@ subclass usable inside ``nn.Linear``, ``DTensor.from_local`` and state-dict load
 The pairs registered here are the MI355X ones, in the reference's order of precedence:
 int8 dynamic-activation x int8 weight, int8 weight-only, int4 weight-only (gfx950 layout),
 float8 (e4m3fn) weight-only, float8 dynamic-activation, int8 dynamic-activation x packed int4
-weight (CutlassInt4PackedLayout).
+weight (CutlassInt4PackedLayout), FP6 weight-only (FloatxTensorCoreLayout, bf16 activations).
 """
 
 import logging
@@ -24,6 +24,10 @@ from torchao.dtypes.floatx.float8_layout import (
     _linear_fp8_act_fp8_weight_impl,
     _linear_fp_act_fp8_weight_check,
     _linear_fp_act_fp8_weight_impl,
+)
+from torchao.dtypes.floatx.floatx_tensor_core_layout import (
+    _linear_bf16_act_floatx_weight_check,
+    _linear_bf16_act_floatx_weight_impl,
 )
 from torchao.dtypes.uintx.cutlass_int4_packed_layout import (
     _linear_int8_act_int4_weight_cutlass_check,
@@ -84,6 +88,7 @@ for _cond, _impl in [
     (_linear_fp_act_fp8_weight_check, _linear_fp_act_fp8_weight_impl),
     (_linear_fp8_act_fp8_weight_check, _linear_fp8_act_fp8_weight_impl),
     (_linear_int8_act_int4_weight_cutlass_check, _linear_int8_act_int4_weight_cutlass_impl),
+    (_linear_bf16_act_floatx_weight_check, _linear_bf16_act_floatx_weight_impl),
 ]:
     register_aqt_quantized_linear_dispatch(_cond, _impl)
 

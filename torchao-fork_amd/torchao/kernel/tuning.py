@@ -45,6 +45,9 @@ _KNOBS = {
     "cnt_stride": ("tao_tune_cnt_stride", 1),
     # (route 0 auto / 1 gemv / 2 dequant + mm, max_gemv_m, rows per wave, waves along K, row groups)
     "nf4": ("tao_tune_nf4", 5),
+    # (route, max_gemv_m, rows per wave, waves along K, row groups as for nf4; 32-code groups per
+    # lane chunk: 0 built-in, 1 = 24 B, 2 = 48 B)
+    "fp6": ("tao_tune_fp6", 6),
 }
 
 

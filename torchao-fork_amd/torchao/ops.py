@@ -215,6 +215,17 @@ lib_nf4.define(
 lib_nf4.define(
     "nf4_linear(Tensor x, Tensor codes, Tensor qscalers, Tensor qfactor, Tensor mean, "
     "Tensor levels, int N, Tensor? bias=None) -> Tensor")
+# The FP6 ops (FPXWeightOnlyConfig, torchao/dtypes/floatx/floatx_tensor_core_layout.py;
+# csrc/fp6.hip), on a fragment of their own; opchecked in tests/test_gpu_fp6.py. (ebits, mbits) is
+# (3, 2) or (2, 3); codes are the native storage, int32 [N, K * 6 / 32]; scale is bf16 [N]. bf16
+# HIP tensors only. Their CUDA kernels exist in C++ only (csrc/torch_ops.cpp), so without
+# libtorchao_ops.so a call raises instead of falling back.
+lib_fp6 = torch.library.Library("torchao", "FRAGMENT")
+lib_fp6.define("fp6_quantize_rows(Tensor w, int ebits, int mbits) -> (Tensor, Tensor)")
+lib_fp6.define("fp6_dequantize(Tensor codes, Tensor scale, int ebits, int mbits) -> Tensor")
+lib_fp6.define(
+    "fp6_weight_only_linear(Tensor x, Tensor codes, Tensor scale, int ebits, int mbits, "
+    "Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -1684,6 +1695,52 @@ def _(x, codes, qscalers, qfactor, mean, levels, N, bias=None):
     return x.new_empty((*x.shape[:-1], N), dtype=torch.bfloat16)
 
 
+# ---------------------------------------------------------------------------------------------
+# FP6 (csrc/fp6.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
+# ---------------------------------------------------------------------------------------------
+def _check_fp6_format(ebits, mbits, op):
+    torch._check((ebits, mbits) in ((3, 2), (2, 3)),
+                 lambda: f"{op}: (ebits, mbits) = ({ebits}, {mbits}) is not served; served: "
+                         f"(3, 2) and (2, 3)")
+
+
+def _check_fp6_weight(codes, scale, op):
+    torch._check(codes.dtype is torch.int32 and codes.dim() == 2,
+                 lambda: f"{op}: codes must be a 2D int32 [N, K * 6 / 32] tensor")
+    torch._check(codes.shape[1] % 6 == 0,
+                 lambda: f"{op}: codes must hold whole 32-code groups of 6 dwords, got "
+                         f"{codes.shape[1]} dwords per row")
+    torch._check(scale.numel() == codes.shape[0],
+                 lambda: f"{op}: scale must have N = {codes.shape[0]} elements")
+
+
+@torch.library.register_fake("torchao::fp6_quantize_rows")
+def _(w, ebits, mbits):
+    _check_fp6_format(ebits, mbits, "fp6_quantize_rows")
+    torch._check(w.dim() == 2 and w.shape[1] % 32 == 0,
+                 lambda: "fp6_quantize_rows: w must be 2D with K a multiple of 32")
+    return (w.new_empty((w.shape[0], w.shape[1] // 32 * 6), dtype=torch.int32),
+            w.new_empty((w.shape[0],), dtype=torch.bfloat16))
+
+
+@torch.library.register_fake("torchao::fp6_dequantize")
+def _(codes, scale, ebits, mbits):
+    _check_fp6_format(ebits, mbits, "fp6_dequantize")
+    _check_fp6_weight(codes, scale, "fp6_dequantize")
+    return codes.new_empty((codes.shape[0], codes.shape[1] // 6 * 32), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("torchao::fp6_weight_only_linear")
+def _(x, codes, scale, ebits, mbits, bias=None):
+    _check_fp6_format(ebits, mbits, "fp6_weight_only_linear")
+    _check_fp6_weight(codes, scale, "fp6_weight_only_linear")
+    K = codes.shape[1] // 6 * 32
+    torch._check(K % 64 == 0,
+                 lambda: f"fp6_weight_only_linear: K ({K}) must be a multiple of 64")
+    torch._check(x.shape[-1] == K, lambda: f"x last dim {x.shape[-1]} != K {K}")
+    return x.new_empty((*x.shape[:-1], codes.shape[0]), dtype=torch.bfloat16)
+
+
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
 # M = 1, profiles/r2_eager_overhead*.json). The Python impls below serve the rest, and these
@@ -1700,6 +1757,7 @@ _native_served_awq: frozenset = frozenset()
 _native_served_smoothquant: frozenset = frozenset()
 _native_served_w4a8: frozenset = frozenset()
 _native_served_nf4: frozenset = frozenset()
+_native_served_fp6: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -1737,6 +1795,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_nf4
         _served.restype = ctypes.c_char_p
         _native_served_nf4 = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_fp6
+        _served.restype = ctypes.c_char_p
+        _native_served_fp6 = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -1785,6 +1846,11 @@ def native_dispatch_smoothquant() -> frozenset:
 def native_dispatch_nf4() -> frozenset:
     """The NF4 ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
     return _native_served_nf4
+
+
+def native_dispatch_fp6() -> frozenset:
+    """The FP6 ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
+    return _native_served_fp6
 
 
 def native_dispatch_w4a8() -> frozenset:

@@ -13,6 +13,7 @@ from torchao.quantization.linear_activation_scale import (
 from torchao.quantization.quant_api import (
     Float8DynamicActivationFloat8WeightConfig,
     Float8WeightOnlyConfig,
+    FPXWeightOnlyConfig,
     Int4WeightOnlyConfig,
     Int8DynamicActivationInt4WeightConfig,
     Int8DynamicActivationInt8WeightConfig,
@@ -20,6 +21,7 @@ from torchao.quantization.quant_api import (
     ModuleFqnToConfig,
     float8_dynamic_activation_float8_weight,
     float8_weight_only,
+    fpx_weight_only,
     int4_weight_only,
     int8_dynamic_activation_int4_weight,
     int8_dynamic_activation_int8_weight,
@@ -45,6 +47,8 @@ __all__ = [
     "Int8DynamicActivationInt4WeightConfig",
     "Float8WeightOnlyConfig",
     "Float8DynamicActivationFloat8WeightConfig",
+    "FPXWeightOnlyConfig",
+    "fpx_weight_only",
     "PerAxis",
     "PerRow",
     "PerTensor",

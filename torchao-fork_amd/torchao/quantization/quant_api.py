@@ -68,6 +68,8 @@ __all__ = [
     "int8_dynamic_activation_int4_weight",
     "Float8WeightOnlyConfig",
     "float8_weight_only",
+    "FPXWeightOnlyConfig",
+    "fpx_weight_only",
     "Float8DynamicActivationFloat8WeightConfig",
     "float8_dynamic_activation_float8_weight",
     "ModuleFqnToConfig",
@@ -595,6 +597,65 @@ def _float8_weight_only_transform(module: nn.Module, config: Float8WeightOnlyCon
         torchao.quantization.utils.recommended_inductor_config_setter()
     assert hasattr(module, "weight"), "float8 weight-only quant requires a module with a weight"
     return _swap_weight(module, _float8_weight_only_quant_tensor(module.weight, config))
+
+
+# ---------------------------------------------------------------------------------------------
+# FP6 (floatx) weight-only
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class FPXWeightOnlyConfig(AOBaseConfig):
+    """Sub-byte floating point weight-only quantization, floatx(``ebits``, ``mbits``) with one
+    scale per output channel in the weight's dtype (reference :2090-2141, same fields and
+    defaults; the FP6-LLM recipe). Served here: the two FP6 formats, (3, 2) and (2, 3); any other
+    pair (the reference's fp5 forms included) raises ``NotImplementedError`` before ``quantize_``
+    touches a module. As in the reference, a linear whose ``in_features % 64 != 0`` or
+    ``out_features % 256 != 0`` is left as it is."""
+
+    ebits: int
+    mbits: int
+    set_inductor_config: bool = True
+
+    def __post_init__(self):
+        torch._C._log_api_usage_once("torchao.quantization.FPXWeightOnlyConfig")
+
+
+fpx_weight_only = FPXWeightOnlyConfig
+
+
+def _fpx_precheck(module: nn.Module, config: FPXWeightOnlyConfig) -> None:
+    """What this config refuses, raised before ``quantize_`` swaps any weight."""
+    if (config.ebits, config.mbits) not in ((3, 2), (2, 3)):
+        raise NotImplementedError(
+            f"FPXWeightOnlyConfig(ebits={config.ebits}, mbits={config.mbits}) is not implemented "
+            f"on MI355X; served: the FP6 formats FPXWeightOnlyConfig(3, 2) (e3m2) and "
+            f"FPXWeightOnlyConfig(2, 3) (e2m3)")
+
+
+@register_quantize_module_handler(FPXWeightOnlyConfig)
+def _fpx_weight_only_transform(module: nn.Module, config: FPXWeightOnlyConfig) -> nn.Module:
+    _fpx_precheck(module, config)
+    ebits, mbits = config.ebits, config.mbits
+    weight = module.weight
+    if config.set_inductor_config:
+        torchao.quantization.utils.recommended_inductor_config_setter()
+    from torchao.dtypes import to_affine_quantized_fpx
+    from torchao.dtypes.floatx import FloatxTensorCoreLayout
+
+    assert weight.dim() == 2, f"floatx only works for 2-d Tensor, got: {weight.dim()}"
+    out_dim, in_dim = weight.shape
+    if (in_dim % 64 != 0) or (out_dim % 256 != 0):
+        logger.info(
+            f"Skipping floatx quantization float{ebits + mbits + 1}_{ebits}_{mbits} because "
+            f"the shape is not compatible with the kernel: in_dim={in_dim}, out_dim={out_dim} "
+            "expected in_dim % 64 == 0 and out_dim % 256 == 0"
+        )
+        return module
+    new_weight = to_affine_quantized_fpx(weight, FloatxTensorCoreLayout(ebits, mbits))
+    return _swap_weight(module, new_weight)
+
+
+# quantize_ runs this over every selected module before the first swap
+_fpx_weight_only_transform.precheck = _fpx_precheck
 
 
 # ---------------------------------------------------------------------------------------------

@@ -13,11 +13,15 @@ bit-for-bit against fixtures generated from the reference, tests/golden/):
     (:779-1031)
   * ``_choose_scale_float8`` / ``_quantize_affine_float8`` / ``_dequantize_affine_float8`` /
     ``_expand_scale_to_tensor_shape``    (:2175-2312; float8 e4m3fn, fp32 scales)
+  * ``_choose_qparams_affine_floatx`` / ``_quantize_affine_floatx`` /
+    ``_dequantize_affine_floatx``        (:2114-2171; FP6 e3m2 / e2m3, one bf16 scale per row;
+    written here from the formats' definition, pinned against the reference by fixtures)
 
 These run with torch ops on whatever device the weight lives on: they execute once at
 quantization time, outside the per-token hot loop (which is the HIP kernels behind torchao.ops).
 """
 
+import functools
 from enum import Enum, auto
 from typing import List, Optional, Tuple, Union
 
@@ -42,6 +46,12 @@ __all__ = [
     "_quantize_affine_float8",
     "_dequantize_affine_float8",
     "_expand_scale_to_tensor_shape",
+    "FLOATX_SERVED",
+    "_floatx_max_normal",
+    "_floatx_code_values",
+    "_choose_qparams_affine_floatx",
+    "_quantize_affine_floatx",
+    "_dequantize_affine_floatx",
 ]
 
 
@@ -525,6 +535,90 @@ def _dequantize_affine_float8(
     """x = float(q) * scale in fp32, then one rounding to ``output_dtype``."""
     hp = tensor.to(torch.float32) * _expand_scale_to_tensor_shape(scale, tensor.shape)
     return hp.to(output_dtype)
+
+
+# ---- floatx (FP6 e3m2 / e2m3; FPXWeightOnlyConfig) -----------------------------------------------
+# A floatx(ebits, mbits) number is sign | ebits exponent | mbits mantissa with bias
+# 2^(ebits - 1) - 1, subnormals, and no inf or NaN (every exponent is a finite binade: OCP FP6).
+# Codes are uint8, 00SEEEMM for e3m2. Each row has one scale in the weight's dtype.
+FLOATX_SERVED = ((3, 2), (2, 3))
+
+
+def _floatx_check(ebits: int, mbits: int) -> None:
+    if (ebits, mbits) not in FLOATX_SERVED:
+        raise NotImplementedError(
+            f"floatx (ebits, mbits) = ({ebits}, {mbits}) is not served; served: the FP6 formats "
+            f"(3, 2) and (2, 3)")
+
+
+def _floatx_max_normal(ebits: int, mbits: int) -> float:
+    """Largest value: exponent and mantissa all ones (28 for e3m2, 7.5 for e2m3)."""
+    bias = 2 ** (ebits - 1) - 1
+    return 2.0 ** (2**ebits - 1 - bias) * (2.0 - 2.0 ** -mbits)
+
+
+@functools.lru_cache(maxsize=16)
+def _floatx_code_values(ebits: int, mbits: int, device=None) -> torch.Tensor:
+    """fp32 [2^(1 + ebits + mbits)]: the value of every code, from the definition (one shared,
+    read-only tensor per format and device, so that a graph capture does not meet its upload)."""
+    bias = 2 ** (ebits - 1) - 1
+    values = []
+    for code in range(2 ** (1 + ebits + mbits)):
+        e = (code >> mbits) & (2**ebits - 1)
+        m = code & (2**mbits - 1)
+        mag = m * 2.0 ** (1 - bias - mbits) if e == 0 else (1 + m / 2**mbits) * 2.0 ** (e - bias)
+        values.append(-mag if code >> (ebits + mbits) else mag)
+    return torch.tensor(values, dtype=torch.float32, device=device)
+
+
+@torch.no_grad()
+def _choose_qparams_affine_floatx(tensor: torch.Tensor, ebits: int, mbits: int) -> torch.Tensor:
+    """scale[n] = dtype(clamp(amax_fp32 |row n|, 1e-12) / max_normal): an fp32 true division (a
+    tensor divisor: torch turns a division by a Python scalar into a multiplication on the GPU),
+    rounded once to the weight's dtype."""
+    _floatx_check(ebits, mbits)
+    amax = tensor.to(torch.float32).abs().amax(1).clamp(min=1e-12)
+    max_normal = torch.full((), _floatx_max_normal(ebits, mbits), dtype=torch.float32,
+                            device=tensor.device)
+    return (amax / max_normal).to(tensor.dtype)
+
+
+@torch.no_grad()
+def _quantize_affine_floatx(tensor: torch.Tensor, scale: torch.Tensor, ebits: int,
+                            mbits: int) -> torch.Tensor:
+    """uint8 codes of float(x) / float(scale[n]) (an fp32 true division): round to nearest even,
+    saturated at +-max_normal, subnormals and the sign of zero kept. Integer arithmetic on the
+    fp32 bits; a NaN quotient takes an unspecified six-bit code."""
+    _floatx_check(ebits, mbits)
+    bias = 2 ** (ebits - 1) - 1
+    x = tensor.to(torch.float32) / scale.to(torch.float32).view(-1, 1)
+    bits = x.contiguous().view(torch.int32)
+    sign = (bits >> 31) & 1
+    ab = bits & 0x7FFFFFFF
+    a = ab.view(torch.float32)
+    shift = 23 - mbits
+    # normal range: add half an fp6 ulp (minus one, plus the kept bit's parity: ties to even),
+    # drop the fp32 mantissa's low bits, re-bias; a carry moves into the exponent by itself
+    normal = ((ab + ((1 << (shift - 1)) - 1) + ((ab >> shift) & 1)) >> shift) - (
+        (127 - bias) << mbits)
+    # below the smallest normal 2^(1 - bias): whole subnormal steps 2^(1 - bias - mbits);
+    # torch.round is half-to-even and the product is exact (2^mbits is the smallest normal's code)
+    sub = torch.round(a * 2.0 ** (bias - 1 + mbits)).to(torch.int32)
+    code = torch.where(a < 2.0 ** (1 - bias), sub, normal)
+    code = torch.where(a >= _floatx_max_normal(ebits, mbits),
+                       torch.full_like(code, 2 ** (ebits + mbits) - 1), code)
+    # (a NaN's normal branch is wider than the field: masked, as the HIP encoder does)
+    magnitude = code & (2 ** (ebits + mbits) - 1)
+    return (magnitude | (sign << (ebits + mbits))).to(torch.uint8)
+
+
+@torch.no_grad()
+def _dequantize_affine_floatx(tensor: torch.Tensor, scale: torch.Tensor, ebits: int, mbits: int,
+                              output_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """x = value(code) * float(scale[n]) in fp32, then one rounding to ``output_dtype``."""
+    _floatx_check(ebits, mbits)
+    values = _floatx_code_values(ebits, mbits, tensor.device)[tensor.long()]
+    return (values * scale.to(torch.float32).view(-1, 1)).to(output_dtype)
 
 
 # enums appear in flattened AQT metadata: allow weights_only=True checkpoint loads
