@@ -539,6 +539,47 @@ int tao_fp6_linear_bf16(const uint16_t* x, const uint32_t* codes, const uint16_t
                         const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                         int ebits, int mbits, void* stream);
 
+/* ---- MoE expert FFN over many tokens (csrc/moe_gemm.hip; torchao/prototype/moe_quant) ----------
+ * T tokens, A = top-k, R = T * A token activations, E experts. E <= 256, A <= 8. None of the three
+ * kernels waits on another workgroup; each result is a pure function of its inputs. */
+
+/* Stable counting sort of expert_indices int64 [R] (flat index = token * A + slot): offsets int32
+ * [E + 1], offsets[e] = number of activations whose expert is < e, offsets[E] = R; order int32 [R],
+ * order[p] = the flat index at sorted position p, ascending within an expert (argsort(stable=True));
+ * inverse int32 [R], inverse[order[p]] = p. An index outside [0, E) is clamped and reported by
+ * tao_decode_status (bits & 4). One launch, no global atomics. R % A == 0, R < 2^24. Replaces the
+ * argsort / div / floor / histc / cumsum of ConditionalFeedForwardAOQuantizable's many-token branch
+ * (prototype/moe_quant/quantizable_moe_modules.py:117-136) and its per-expert host-side slices. */
+int tao_moe_route(const int64_t* expert_indices, int64_t R, int64_t A, int64_t E,
+                  int32_t* offsets, int32_t* order, int32_t* inverse, void* stream);
+
+/* y[p][n] = bf16( sum_k x[row(p)][k] * W_e[n][k] ) for every sorted row p, e the expert with
+ * offsets[e] <= p < offsets[e + 1] and row(p) = src_row[p] / row_div (p itself when src_row is
+ * null): every expert's int4 linear (tao_int4wo_linear_bf16's weight format per expert: packed
+ * [E][N][K/8], scales_and_zeros [E][N][K/g][2]) over its own rows in one launch, the token gather
+ * x[indices] folded into the x load. x bf16 [x_rows][K], y bf16 [R][N]; the sum in fp32 in a fixed
+ * order. With packed_b / scales_and_zeros_b (a second stack of the same shape: gate and up in one
+ * launch) y[p][n] = bf16( bf16(silu(bf16 a)) * bf16 b ), a and b the two stacks' sums: the roundings
+ * of F.silu(F.linear(x, w1)) * F.linear(x, w3) on bf16 tensors. K % 32 == 0, K % group_size == 0,
+ * N * K / 2 a multiple of 16 and below 4 GiB; x, packed 16-B aligned. Rows per tile: csrc/moe_host.h
+ * (tao_moe_row_tile, tao_tune_moe). Replaces the per-expert x[indices], F.linear x 3, silu and mul
+ * of ConditionalFeedForwardAOQuantizable's many-token branch. */
+int tao_int4wo_grouped_linear_bf16(const uint16_t* x, int64_t x_rows, const int32_t* src_row,
+                                   int64_t row_div, const uint32_t* packed,
+                                   const uint16_t* scales_and_zeros, const uint32_t* packed_b,
+                                   const uint16_t* scales_and_zeros_b, const int32_t* offsets,
+                                   int64_t R, int64_t E, uint16_t* y, int64_t N, int64_t K,
+                                   int64_t group_size, void* stream);
+
+/* out[t] = the expert-weighted sum of token t's A rows of y2 bf16 [R][D], taken in ascending
+ * sorted position p = inverse[t * A + a]: acc = +0, then acc = bf16(acc + bf16(y2[p] * w[t * A + a])),
+ * the reference's mul and scatter_add as the CPU executes them, for any A. expert_weights bf16 [R]
+ * (token order), out bf16 [T][D]. D % 8 == 0, T <= 65535; y2 and out 16-B aligned. Replaces the
+ * weight gather, mul, zeros_like and scatter_add of quantizable_moe_modules.py:173-190. */
+int tao_moe_combine_bf16(const uint16_t* y2, const uint16_t* expert_weights,
+                         const int32_t* inverse, uint16_t* out, int64_t T, int64_t A, int64_t D,
+                         void* stream);
+
 /* ---- int8 KV cache (AffineQuantizedKVCache, torchao/_models/llama/model.py:198-240) -----------
  * k_cache / v_cache [B][Hkv][T][128] int8 codes, k_scale / v_scale [B][Hkv][T] bf16, one scale per
  * row: symmetric, [-127, 127], eps 1e-5, the arithmetic of _quantize_activation_per_token_absmax in

@@ -229,6 +229,14 @@ int tao_fp6_linear_route(int64_t M, int64_t N, int64_t K);
  * 0 = built-in, 1 = 24 B (a 2048-code wave slice), 2 = 48 B (a 4096-code wave slice). */
 int tao_tune_fp6(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups,
                  int chunk_groups);
+/* Rows per tile (16, 32 or 64) of tao_int4wo_grouped_linear_bf16 for R sorted rows over E experts,
+ * and whether the expert FFN runs gate and up in one launch (1) or two (0), under the calling
+ * thread's tao_tune_moe (rules: csrc/moe_host.h). */
+int tao_moe_row_tile(int64_t R, int64_t E);
+int tao_moe_dual(int64_t R, int64_t E);
+/* Launch shape of the grouped (MoE) int4 GEMM (calling thread only; tests and A/B runs): bm 0 =
+ * built-in rule, 16, 32 or 64; dual 0 = built-in rule, 1 = gate and up in two launches, 2 = one. */
+int tao_tune_moe(int bm, int dual);
 /* Per-token int8 quantisation kernel (A/B only): 0 = one wave per token, the token held in
  * registers (default, K <= 8192); 1 = one 256-thread workgroup per token. Bit-identical. */
 int tao_tune_int8_quant(int block);

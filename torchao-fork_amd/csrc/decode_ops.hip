@@ -44,6 +44,7 @@ int fp8gemv_decode_status(unsigned* bits);
 int fp8dyn_decode_status(unsigned* bits);
 int engine_decode_status(unsigned* bits);
 int kvq8_decode_status(unsigned* bits);
+int moe_decode_status(unsigned* bits);
 
 namespace {
 
@@ -944,6 +945,7 @@ extern "C" int tao_decode_status(int* bits) {
   if (rc == TAO_OK) rc = tao::sf_decode_status(&v);
   if (rc == TAO_OK) rc = tao::engine_decode_status(&v);
   if (rc == TAO_OK) rc = tao::kvq8_decode_status(&v);
+  if (rc == TAO_OK) rc = tao::moe_decode_status(&v);
   unsigned to = 0;  // split-K reducer timeouts of the single-fetch GEMMs (prefill)
   if (rc == TAO_OK) rc = tao_gemm_sf_status(&to);
   if (to != 0) v |= tao::kDecodeErrSplitK;

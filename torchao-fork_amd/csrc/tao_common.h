@@ -89,6 +89,7 @@ struct Tuning {
   int fp6_route = 0, fp6_max_m = 0;              // FP6 linear route and GEMV boundary (tao_tune_fp6)
   int fp6_rpw = 0, fp6_wk = 0, fp6_g = 0;        // FP6 GEMV launch shape (tao_tune_fp6)
   int fp6_groups = 0;                            // FP6 GEMV 32-code groups per lane chunk
+  int moe_bm = 0, moe_dual = 0;                  // grouped (MoE) int4 GEMM row tile / dual form (tao_tune_moe)
 };
 Tuning& tuning();
 
@@ -344,7 +345,8 @@ constexpr unsigned kDecodeErrKvPos = 1u;
 // tao_decode_status bits & 2: a single-fetch GEMM's split-K reducer timed out waiting for its
 // publishers (that tile was not written; never expected)
 constexpr unsigned kDecodeErrSplitK = 2u;
-// tao_decode_status bits & 4: a grouped (MoE) GEMV read an expert index outside [0, E) (clamped)
+// tao_decode_status bits & 4: a grouped (MoE) GEMV or tao_moe_route read an expert index outside
+// [0, E) (clamped)
 constexpr unsigned kDecodeErrExpert = 4u;
 #define TAO_DECODE_ERROR_WORD(reader)                                                        \
   static __device__ unsigned g_decode_err = 0;                                                \

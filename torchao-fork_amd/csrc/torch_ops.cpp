@@ -10,7 +10,8 @@
 // int8_smooth_quantize_static, int8_smooth_dyn_linear, int8_smooth_static_linear, and the W4A8 set
 // rowwise_scaled_linear_cutlass_s8s4, int8_quantize_per_token_f32, int4_quantize_rows_packed,
 // w4a8_dyn_linear, and the NF4 set nf4_quantize_blocks, nf4_dequantize, nf4_linear, and the FP6 set
-// fp6_quantize_rows, fp6_dequantize, fp6_weight_only_linear.
+// fp6_quantize_rows, fp6_dequantize, fp6_weight_only_linear, and the MoE set moe_route,
+// int4_grouped_linear, moe_combine.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -29,6 +30,7 @@
 #include "../../include/torchao_mi355x.h"
 #include "../../include/torchao_mi355x_tune.h"  // tao_nf4_linear_route, tao_fp6_linear_route
 #include "fp6_host.h"
+#include "moe_host.h"
 
 namespace {
 
@@ -1182,9 +1184,124 @@ Tensor fp6_weight_only_linear(const Tensor& x, const Tensor& codes, const Tensor
   return y.reshape(out_shape(x, N));
 }
 
+// ---- MoE expert FFN over many tokens (torchao/prototype/moe_quant; csrc/moe_gemm.hip) -----------
+std::tuple<Tensor, Tensor, Tensor> moe_route(const Tensor& expert_indices, int64_t num_experts,
+                                             int64_t top_k) {
+  TORCH_CHECK(expert_indices.is_cuda(), "moe_route: expected expert_indices on a HIP device, got ",
+              expert_indices.device());
+  TORCH_CHECK(expert_indices.scalar_type() == at::kLong, "moe_route: expert_indices must be int64, got ",
+              expert_indices.scalar_type());
+  TORCH_CHECK(num_experts >= 1 && num_experts <= tao::kMoeMaxExperts, "moe_route: num_experts (",
+              num_experts, ") is not served; served: 1 to ", tao::kMoeMaxExperts);
+  TORCH_CHECK(top_k >= 1 && top_k <= tao::kMoeMaxTopK, "moe_route: top_k (", top_k,
+              ") is not served; served: 1 to ", tao::kMoeMaxTopK);
+  const Tensor idx = expert_indices.reshape({-1}).contiguous();
+  const int64_t R = idx.numel();
+  TORCH_CHECK(R % top_k == 0, "moe_route: expert_indices has ", R,
+              " elements, not a multiple of top_k = ", top_k);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(idx.device());
+  const auto opt = idx.options().dtype(at::kInt);
+  Tensor offsets = at::empty({num_experts + 1}, opt);
+  Tensor order = at::empty({R}, opt), inverse = at::empty({R}, opt);
+  check_rc(tao_moe_route(cptr<int64_t>(idx), R, top_k, num_experts, mptr<int32_t>(offsets),
+                         mptr<int32_t>(order), mptr<int32_t>(inverse), stream_of(idx)),
+           "tao_moe_route");
+  return {offsets, order, inverse};
+}
+
+void check_int4_stack(const Tensor& x, const Tensor& packed, const Tensor& sz, int64_t group_size,
+                      const char* name) {
+  TORCH_CHECK(packed.dim() == 3 && packed.scalar_type() == at::kInt, "int4_grouped_linear: ", name,
+              " must be a 3D int32 [E, N, K/8] tensor");
+  const int64_t E = packed.size(0), N = packed.size(1), K = packed.size(2) * 8;
+  TORCH_CHECK(sz.scalar_type() == at::kBFloat16 && sz.dim() == 4 && sz.size(0) == E &&
+                  sz.size(1) == N && sz.size(2) == K / group_size && sz.size(3) == 2,
+              "int4_grouped_linear: scales_and_zeros of ", name, " must be bfloat16 [E, N, K/g, 2] = (",
+              E, ", ", N, ", ", K / group_size, ", 2), got ", sz.sizes());
+  TORCH_CHECK(packed.is_contiguous() && sz.is_contiguous(), "int4_grouped_linear: ", name,
+              " and its scales_and_zeros must be contiguous");
+  check_device(x, packed, name);
+  check_device(x, sz, "scales_and_zeros");
+}
+
+Tensor int4_grouped_linear(const Tensor& x, const std::optional<Tensor>& src_row, int64_t row_div,
+                           const Tensor& packed, const Tensor& sz,
+                           const std::optional<Tensor>& packed_b,
+                           const std::optional<Tensor>& sz_b, const Tensor& offsets,
+                           int64_t group_size) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 2,
+              "int4_grouped_linear (HIP) needs a 2D bf16 x, got ", x.scalar_type(), " ", x.dim(), "D");
+  TORCH_CHECK(group_size == 32 || group_size == 64 || group_size == 128 || group_size == 256,
+              "qGroupSize must be 32, 64, 128, or 256");
+  TORCH_CHECK(packed.dim() == 3 && packed.size(2) * 8 % group_size == 0,
+              "int4_grouped_linear: packed must be [E, N, K/8] with K divisible by qGroupSize");
+  check_int4_stack(x, packed, sz, group_size, "packed");
+  const int64_t E = packed.size(0), N = packed.size(1), K = packed.size(2) * 8;
+  TORCH_CHECK(E <= tao::kMoeMaxExperts, "int4_grouped_linear: E (", E, ") is not served; served: 1 to ",
+              tao::kMoeMaxExperts);
+  TORCH_CHECK(packed_b.has_value() == sz_b.has_value(),
+              "int4_grouped_linear: the second stack needs both packed_b and scales_and_zeros_b");
+  if (packed_b.has_value()) {
+    check_int4_stack(x, *packed_b, *sz_b, group_size, "packed_b");
+    TORCH_CHECK(packed_b->sizes() == packed.sizes(), "int4_grouped_linear: packed_b ",
+                packed_b->sizes(), " must have packed's shape ", packed.sizes());
+  }
+  TORCH_CHECK(x.size(1) == K, "x last dim ", x.size(1), " != K ", K);
+  TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 && offsets.size(0) == E + 1 &&
+                  offsets.is_contiguous(),
+              "int4_grouped_linear: offsets must be a contiguous int32 [E + 1] tensor");
+  check_device(x, offsets, "offsets");
+  TORCH_CHECK(row_div >= 1, "int4_grouped_linear: row_div must be >= 1");
+  int64_t R = x.size(0);
+  if (src_row.has_value()) {
+    TORCH_CHECK(src_row->scalar_type() == at::kInt && src_row->dim() == 1 && src_row->is_contiguous(),
+                "int4_grouped_linear: src_row must be a contiguous 1D int32 tensor");
+    check_device(x, *src_row, "src_row");
+    R = src_row->numel();
+  }
+  const Tensor x2 = rows_of(x, K);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({R, N}, x.options());
+  check_rc(tao_int4wo_grouped_linear_bf16(
+               cptr<uint16_t>(x2), x2.size(0), src_row ? cptr<int32_t>(*src_row) : nullptr, row_div,
+               cptr<uint32_t>(packed), cptr<uint16_t>(sz),
+               packed_b ? cptr<uint32_t>(*packed_b) : nullptr, sz_b ? cptr<uint16_t>(*sz_b) : nullptr,
+               cptr<int32_t>(offsets), R, E, mptr<uint16_t>(y), N, K, group_size, stream_of(x)),
+           "tao_int4wo_grouped_linear_bf16");
+  return y;
+}
+
+Tensor moe_combine(const Tensor& y2, const Tensor& expert_weights, const Tensor& inverse,
+                   int64_t top_k) {
+  TORCH_CHECK(y2.is_cuda(), "moe_combine: expected y2 on a HIP device, got ", y2.device());
+  TORCH_CHECK(y2.scalar_type() == at::kBFloat16 && y2.dim() == 2 && y2.is_contiguous(),
+              "moe_combine (HIP) needs a contiguous 2D bf16 y2");
+  TORCH_CHECK(top_k >= 1 && top_k <= tao::kMoeMaxTopK, "moe_combine: top_k (", top_k,
+              ") is not served; served: 1 to ", tao::kMoeMaxTopK);
+  const int64_t R = y2.size(0), D = y2.size(1);
+  TORCH_CHECK(R % top_k == 0, "moe_combine: y2 has ", R, " rows, not a multiple of top_k = ", top_k);
+  TORCH_CHECK(D % 8 == 0, "moe_combine: D (", D, ") must be a multiple of 8");
+  TORCH_CHECK(expert_weights.scalar_type() == at::kBFloat16 && expert_weights.numel() == R,
+              "moe_combine: expert_weights must be bf16 with R = ", R, " elements");
+  TORCH_CHECK(inverse.scalar_type() == at::kInt && inverse.numel() == R && inverse.is_contiguous(),
+              "moe_combine: inverse must be a contiguous int32 tensor of R = ", R, " elements");
+  check_device(y2, expert_weights, "expert_weights");
+  check_device(y2, inverse, "inverse");
+  const Tensor w = expert_weights.reshape({-1}).contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(y2.device());
+  Tensor out = at::empty({R / top_k, D}, y2.options());
+  check_rc(tao_moe_combine_bf16(cptr<uint16_t>(y2), cptr<uint16_t>(w), cptr<int32_t>(inverse),
+                                mptr<uint16_t>(out), R / top_k, top_k, D, stream_of(y2)),
+           "tao_moe_combine_bf16");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
+  m.impl("moe_route", &moe_route);
+  m.impl("int4_grouped_linear", &int4_grouped_linear);
+  m.impl("moe_combine", &moe_combine);
   m.impl("fp6_quantize_rows", &fp6_quantize_rows);
   m.impl("fp6_dequantize", &fp6_dequantize);
   m.impl("fp6_weight_only_linear", &fp6_weight_only_linear);
@@ -1259,6 +1376,11 @@ extern "C" const char* tao_torch_ops_served_nf4(void) {
 // The FP6 ops served here; they have no Python kernels either.
 extern "C" const char* tao_torch_ops_served_fp6(void) {
   return "fp6_quantize_rows,fp6_dequantize,fp6_weight_only_linear";
+}
+
+// The MoE ops served here; they have no Python kernels either.
+extern "C" const char* tao_torch_ops_served_moe(void) {
+  return "moe_route,int4_grouped_linear,moe_combine";
 }
 
 // The activation pre-scale ops (AWQ) served here, a set of their own as well.

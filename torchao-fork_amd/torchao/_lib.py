@@ -101,6 +101,13 @@ _SIGNATURES = {
     "tao_fp6_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p],
     "tao_fp6_linear_route": [_i64, _i64, _i64],
     "tao_tune_fp6": [_int, _int, _int, _int, _int, _int],
+    "tao_moe_route": [_p, _i64, _i64, _i64, _p, _p, _p, _p],
+    "tao_int4wo_grouped_linear_bf16": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _p,
+                                       _i64, _i64, _i64, _p],
+    "tao_moe_combine_bf16": [_p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_moe_row_tile": [_i64, _i64],
+    "tao_moe_dual": [_i64, _i64],
+    "tao_tune_moe": [_int, _int],
     "tao_tune_int8_gemv": [_int, _int, _int],
     "tao_tune_int8_quant": [_int],
     "tao_fp8wo_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],

@@ -7,6 +7,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from torchao import _lib
+# the one-token grouped GEMV and the expert FFN on it: shared with torchao/prototype/moe_quant
+from torchao.kernel.moe import int4_grouped_decode, int4_moe_ffn_one_token
 
 __all__ = ["rmsnorm", "rope_kv", "attn_decode", "rope_kv_q8", "attn_decode_q8", "silu_mul", "int4_linear_swiglu",
            "int4_linear_rope_kv", "int4_decode", "int8wo_decode", "int8dq_decode", "fp8wo_decode",
@@ -195,43 +197,13 @@ def int4_qkv_attn(x: torch.Tensor, packed: torch.Tensor, scale_and_zero: torch.T
     return out
 
 
-def int4_grouped_decode(x: torch.Tensor, packed: torch.Tensor, scale_and_zero: torch.Tensor,
-                        group_size: int, expert_idx: torch.Tensor) -> torch.Tensor:
-    """The A = expert_idx.numel() experts' int4 linears of one token in one launch
-    (tao_int4wo_grouped_gemv_bf16): packed [E, N, K/8] int32, scale_and_zero [E, N, K/g, 2] bf16
-    (a 3-D Int4WeightOnlyConfig weight's tensor_impl), x [K] / [1, K] (shared) or [A, K] (row a
-    for expert a) bf16 -> y [A, N] bf16, row a bit-identical to expert expert_idx[a]'s linear."""
-    _check(x, torch.bfloat16, "int4_grouped x")
-    _check(expert_idx, torch.int64, "int4_grouped expert_idx")
-    if packed.dim() != 3:
-        raise RuntimeError(f"int4_grouped: packed must be [E, N, K/8], got {tuple(packed.shape)}")
-    E, N, K8 = packed.shape
-    K, A = K8 * 8, expert_idx.numel()
-    rows = x.numel() // K
-    if x.shape[-1] != K or rows not in (1, A):
-        raise RuntimeError(f"int4_grouped: x {tuple(x.shape)} must be [K] or [A, K] with K = {K}")
-    y = torch.empty(A, N, dtype=x.dtype, device=x.device)
-    _lib.call("tao_int4wo_grouped_gemv_bf16", x.data_ptr(), rows, packed.data_ptr(),
-              scale_and_zero.data_ptr(), expert_idx.data_ptr(), A, E, N, K, int(group_size),
-              y.data_ptr(), _stream(x))
-    return y
-
-
 def int4_moe_ffn_decode(x: torch.Tensor, w1, w2, w3, expert_indices: torch.Tensor,
                         expert_weights: torch.Tensor) -> torch.Tensor:
     """The one-token branch of the reference's ConditionalFeedForwardAOQuantizable
     (_models/mixtral-moe/model.py:360-384) on 3-D int4 weights (AffineQuantizedTensor [E, I, D] /
     [E, D, I] / [E, I, D]): three grouped launches instead of 3 A per-expert linears, the same
     bf16 ops in between (silu(w1 x) * w3 x, then w2, then the expert-weighted sum)."""
-    def parts(w):
-        impl = w.tensor_impl
-        return impl.packed_weight, impl.scale_and_zero, w.block_size[-1]
-
-    idx = expert_indices.reshape(-1)
-    y1 = torch.nn.functional.silu(int4_grouped_decode(x, *parts(w1), idx))
-    y3 = int4_grouped_decode(x, *parts(w3), idx)
-    y2 = int4_grouped_decode((y1 * y3).contiguous(), *parts(w2), idx)  # [A, D]
-    return (y2 * expert_weights.view(-1, 1)).sum(dim=0).unsqueeze(-1)
+    return int4_moe_ffn_one_token(x, w1, w2, w3, expert_indices, expert_weights).unsqueeze(-1)
 
 
 def attn_decode_split(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,

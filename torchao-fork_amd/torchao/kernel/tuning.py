@@ -48,6 +48,9 @@ _KNOBS = {
     # (route, max_gemv_m, rows per wave, waves along K, row groups as for nf4; 32-code groups per
     # lane chunk: 0 built-in, 1 = 24 B, 2 = 48 B)
     "fp6": ("tao_tune_fp6", 6),
+    # (rows per tile of the grouped MoE GEMM: 0 built-in, 16, 32, 64; gate and up: 0 built-in,
+    # 1 = two launches, 2 = one)
+    "moe": ("tao_tune_moe", 2),
 }
 
 

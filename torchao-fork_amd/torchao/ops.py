@@ -226,6 +226,21 @@ lib_fp6.define("fp6_dequantize(Tensor codes, Tensor scale, int ebits, int mbits)
 lib_fp6.define(
     "fp6_weight_only_linear(Tensor x, Tensor codes, Tensor scale, int ebits, int mbits, "
     "Tensor? bias=None) -> Tensor")
+# The MoE ops (MoEQuantConfig, torchao/prototype/moe_quant; csrc/moe_gemm.hip), on a fragment of
+# their own; opchecked in tests/test_gpu_moe.py: the stable sort of the token activations by expert,
+# every expert's int4 linear over its own sorted rows in one launch (a second stack: gate and up
+# with SwiGLU in the epilogue), and the expert-weighted sum back to token order. bf16 HIP tensors
+# only. Their CUDA kernels exist in C++ only (csrc/torch_ops.cpp), so without libtorchao_ops.so a
+# call raises instead of falling back.
+lib_moe = torch.library.Library("torchao", "FRAGMENT")
+lib_moe.define("moe_route(Tensor expert_indices, int num_experts, int top_k) -> "
+               "(Tensor, Tensor, Tensor)")
+lib_moe.define(
+    "int4_grouped_linear(Tensor x, Tensor? src_row, int row_div, Tensor packed, "
+    "Tensor scales_and_zeros, Tensor? packed_b, Tensor? scales_and_zeros_b, Tensor offsets, "
+    "int group_size) -> Tensor")
+lib_moe.define(
+    "moe_combine(Tensor y2, Tensor expert_weights, Tensor inverse, int top_k) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -1741,6 +1756,46 @@ def _(x, codes, scale, ebits, mbits, bias=None):
     return x.new_empty((*x.shape[:-1], codes.shape[0]), dtype=torch.bfloat16)
 
 
+# ---------------------------------------------------------------------------------------------
+# MoE (csrc/moe_gemm.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
+# ---------------------------------------------------------------------------------------------
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOP_K = 8
+
+
+@torch.library.register_fake("torchao::moe_route")
+def _(expert_indices, num_experts, top_k):
+    torch._check(1 <= num_experts <= MOE_MAX_EXPERTS,
+                 lambda: f"moe_route: num_experts ({num_experts}) is not served; served: 1 to "
+                         f"{MOE_MAX_EXPERTS}")
+    torch._check(1 <= top_k <= MOE_MAX_TOP_K,
+                 lambda: f"moe_route: top_k ({top_k}) is not served; served: 1 to {MOE_MAX_TOP_K}")
+    R = expert_indices.numel()
+    return (expert_indices.new_empty((num_experts + 1,), dtype=torch.int32),
+            expert_indices.new_empty((R,), dtype=torch.int32),
+            expert_indices.new_empty((R,), dtype=torch.int32))
+
+
+@torch.library.register_fake("torchao::int4_grouped_linear")
+def _(x, src_row, row_div, packed, scales_and_zeros, packed_b, scales_and_zeros_b, offsets,
+      group_size):
+    torch._check(group_size in _GROUP_SIZES, lambda: "qGroupSize must be 32, 64, 128, or 256")
+    torch._check(packed.dim() == 3 and packed.dtype is torch.int32,
+                 lambda: "int4_grouped_linear: packed must be a 3D int32 [E, N, K/8] tensor")
+    torch._check(x.dim() == 2 and x.shape[1] == packed.shape[2] * 8,
+                 lambda: f"x last dim {x.shape[-1]} != K {packed.shape[2] * 8}")
+    R = x.shape[0] if src_row is None else src_row.numel()
+    return x.new_empty((R, packed.shape[1]), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("torchao::moe_combine")
+def _(y2, expert_weights, inverse, top_k):
+    torch._check(1 <= top_k <= MOE_MAX_TOP_K,
+                 lambda: f"moe_combine: top_k ({top_k}) is not served; served: 1 to {MOE_MAX_TOP_K}")
+    torch._check(y2.dim() == 2, lambda: "moe_combine: y2 must be 2D")
+    return y2.new_empty((y2.shape[0] // top_k, y2.shape[1]))
+
+
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
 # M = 1, profiles/r2_eager_overhead*.json). The Python impls below serve the rest, and these
@@ -1758,6 +1813,7 @@ _native_served_smoothquant: frozenset = frozenset()
 _native_served_w4a8: frozenset = frozenset()
 _native_served_nf4: frozenset = frozenset()
 _native_served_fp6: frozenset = frozenset()
+_native_served_moe: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
     _native_error = "TORCHAO_MI355X_LIB is set (variant build): Python impls"
@@ -1798,6 +1854,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_fp6
         _served.restype = ctypes.c_char_p
         _native_served_fp6 = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_moe
+        _served.restype = ctypes.c_char_p
+        _native_served_moe = frozenset(_served().decode().split(","))
     except (OSError, RuntimeError, AttributeError) as e:
         _native_error = f"{type(e).__name__}: {e}"
 
@@ -1851,6 +1910,11 @@ def native_dispatch_nf4() -> frozenset:
 def native_dispatch_fp6() -> frozenset:
     """The FP6 ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
     return _native_served_fp6
+
+
+def native_dispatch_moe() -> frozenset:
+    """The MoE ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
+    return _native_served_moe
 
 
 def native_dispatch_w4a8() -> frozenset:
