@@ -406,6 +406,31 @@ int tao_decode_status(int* bits);
 int tao_int4_quantize_bf16(const uint16_t* w, uint32_t* packed, uint16_t* scales_and_zeros,
                            int64_t rows, int64_t K, int64_t group_size, float eps, void* stream);
 
+/* Fused HQQ int4 weight quantizer (Int4WeightOnlyConfig(use_hqq=True)): replaces
+ * _choose_qparams_and_quantize_affine_hqq with optimize_weights_proximal_legacy and
+ * _convert_to_affinequantized_format (quant_primitives.py:1901-2111, called from
+ * affine_quantized_tensor.py:252-288) and the layout's pack. In fp32, the reference's CPU
+ * arithmetic (its GPU path iterates in fp16). Per group of g:
+ * scale = min((1 / (max - min)) * 15, 2e4) (torch's scalar / tensor is reciprocal * scalar),
+ * zero = rint(-min * scale), then at most 20 proximal updates of zero alone (lp 0.7, beta 10,
+ * kappa 1.01) with the reference's early stop on the mean |W - Wr| of the whole tensor, decided
+ * on the device: three launches on `stream`, no host copy or synchronisation (capturable).
+ * w [rows][K] bf16 -> packed [rows][K/8] and scales_and_zeros [rows][K/g][2] bf16 as
+ * tao_int4_quantize_bf16 writes them: q = clamp(rint(w * scale + zero), 0, 15),
+ * s = bf16(1 / scale), z = bf16((8 - zero) * (1 / scale)), so w ~= (q - 8) s + z.
+ * iters_run: one int32 on the device, the iterations run (1..20; 0 for an empty tensor).
+ * scratch: device memory owned by the caller, 8-B aligned, tao_int4_hqq_scratch_bytes(rows, K)
+ * bytes; contents are overwritten, nothing is kept between calls. g in {32,64,128,256},
+ * K % g == 0; w 16-B aligned. Results are bit-equal from run to run. */
+int tao_int4_hqq_quantize_bf16(const uint16_t* w, uint32_t* packed, uint16_t* scales_and_zeros,
+                               int32_t* iters_run, void* scratch, int64_t rows, int64_t K,
+                               int64_t group_size, void* stream);
+
+/* Scratch of tao_int4_hqq_quantize_bf16 (the per-workgroup error sums that stand in for the
+ * reference's float(torch.abs(W_f - W_r).mean()), quant_primitives.py:1957):
+ * ceil(rows * (K / 8) / 256) * 20 * 8 bytes; 0 for an empty tensor. Never fails. */
+int64_t tao_int4_hqq_scratch_bytes(int64_t rows, int64_t K);
+
 /* Fused symmetric per-row int8 weight quantizer (Int8WeightOnlyConfig /
  * Int8DynamicActivationInt8WeightConfig weights; choose_qparams_affine SYMMETRIC +
  * quantize_affine, quant_primitives.py): s[r] = bf16(max(bf16(max|w[r]| / 127.5), eps)),

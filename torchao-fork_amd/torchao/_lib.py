@@ -155,6 +155,8 @@ _SIGNATURES = {
     "tao_argmax_advance_bf16": [_p, _i64, _p, _p, _p, _i64, _p],
     "tao_int4_quantize_bf16": [_p, _p, _p, _i64, _i64, _i64, ctypes.c_float, _p],
     "tao_int8_quantize_rows_bf16": [_p, _p, _p, _i64, _i64, ctypes.c_float, _p],
+    "tao_int4_hqq_quantize_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
+    "tao_int4_hqq_scratch_bytes": [_i64, _i64],
     "tao_int4wo_grouped_gemv_bf16": [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
     "tao_int4wo_qkv_attn_supported": [_i64, _i64, _i64, _i64, _i64],
     "tao_int4wo_qkv_attn_bf16": [_p, _p, _p, _i64, _i64, _i64, _p, ctypes.c_float, _p, _p, _p,
@@ -178,7 +180,8 @@ _SIGNATURES = {
 }
 _RESTYPES = {"tao_version": ctypes.c_char_p, "tao_last_error": ctypes.c_char_p,
              "tao_last_kernel": ctypes.c_char_p,
-             "tao_int4wo_ffn_engine_workspace_bytes": ctypes.c_int64}
+             "tao_int4wo_ffn_engine_workspace_bytes": ctypes.c_int64,
+             "tao_int4_hqq_scratch_bytes": ctypes.c_int64}
 
 
 def library_path() -> str:

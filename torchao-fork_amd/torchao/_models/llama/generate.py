@@ -73,8 +73,9 @@ def build_model(name: str, device, dtype=torch.bfloat16, checkpoint_path: Option
 
 
 def apply_quantization(model: nn.Module, quantization: Optional[str]) -> nn.Module:
-    """``-q`` strings of the reference harness: int4wo-<g>, int8wo, int8dq, float8wo,
-    float8dq-row (or none). float8dq and float8dq-tensor are the reference's spellings of
+    """``-q`` strings of the reference harness: int4wo-<g>[-hqq], int8wo, int8dq, float8wo,
+    float8dq-row (or none). ``-hqq`` (reference generate.py:395-430) sets ``use_hqq=True``: other
+    zero points in the same storage, so the decode path is unchanged. float8dq and float8dq-tensor are the reference's spellings of
     per-tensor scales: the config's own NotImplementedError (it names PerRow) propagates."""
     if not quantization:
         return model
@@ -91,8 +92,11 @@ def apply_quantization(model: nn.Module, quantization: Optional[str]) -> nn.Modu
 
     if quantization.startswith("int4wo"):
         parts = quantization.split("-")
+        use_hqq = parts[-1] == "hqq"
+        if use_hqq:
+            parts = parts[:-1]
         g = int(parts[1]) if len(parts) > 1 else 128
-        quantize_(model, Int4WeightOnlyConfig(group_size=g))
+        quantize_(model, Int4WeightOnlyConfig(group_size=g, use_hqq=use_hqq))
     elif quantization == "int8wo":
         quantize_(model, Int8WeightOnlyConfig())
     elif quantization == "int8dq":

@@ -5,11 +5,13 @@ workflows on the hot path: ``from_hp_to_intx`` (pre_process -> choose_qparams ->
 post_process -> layout constructor, :231-373), ``from_hp_to_intx_static``, ``dequantize``
 (:134-196), flatten/unflatten (:198-229), ``to`` and ``_apply_fn_to_data``, and the float8
 weight-only constructor ``from_hp_to_floatx`` (:449-480; e4m3fn, ``Float8Layout``) and the FP6
-constructor ``from_hp_to_fpx`` (:526-553; ``FloatxTensorCoreLayout``). The static float8 and HQQ
-constructors belong to out-of-scope workflows and are not provided.
+constructor ``from_hp_to_fpx`` (:526-553; ``FloatxTensorCoreLayout``), and the HQQ branch of
+``from_hp_to_intx`` (:252-288). The static float8 constructor belongs to an out-of-scope workflow
+and is not provided.
 """
 
 import logging
+import math
 from typing import Optional, Tuple, Union
 
 import torch
@@ -22,6 +24,7 @@ from torchao.quantization.quant_primitives import (
     FP8_TYPES,
     _choose_qparams_affine_floatx,
     _choose_qparams_affine_tinygemm,
+    _choose_qparams_and_quantize_affine_hqq,
     _dequantize_affine_floatx,
     _quantize_affine_floatx,
     _choose_scale_float8,
@@ -323,10 +326,13 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
         use_hqq: bool = False,
     ):
         """Quantize a high-precision tensor into an integer AQT with ``_layout``."""
-        if use_hqq:
-            raise NotImplementedError("HQQ quantization is outside the MI355X hot-path scope")
         original_shape = input_float.shape
         input_float = _layout.pre_process(input_float)
+        if use_hqq:
+            return cls._from_hp_to_intx_hqq(
+                input_float, original_shape, mapping_type, block_size, target_dtype, quant_min,
+                quant_max, zero_point_dtype, zero_point_domain, _layout,
+            )
         fused = _fused_weight_quant(
             input_float, mapping_type, block_size, target_dtype, quant_min, quant_max, eps,
             scale_dtype, zero_point_dtype, preserve_zero, zero_point_domain, _layout,
@@ -372,6 +378,68 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
         tensor_impl = cls.get_tensor_impl_constructor(type(_layout))(
             data, scale, zero_point, _layout
         )
+        return cls(
+            tensor_impl,
+            block_size,
+            original_shape,
+            quant_min,
+            quant_max,
+            zero_point_domain,
+            dtype=input_float.dtype,
+        )
+
+    @classmethod
+    def _from_hp_to_intx_hqq(cls, input_float, original_shape, mapping_type, block_size,
+                             target_dtype, quant_min, quant_max, zero_point_dtype,
+                             zero_point_domain, _layout):
+        """The ``use_hqq=True`` branch of ``from_hp_to_intx`` (reference :252-288), in fp32 on
+        every device (the reference iterates in fp16 on a GPU; its CPU arithmetic is served here).
+
+        A bf16 CUDA weight with ``TensorCoreTiledLayout``, [0, 15] and g in {32, 64, 128, 256}
+        runs the fused HIP quantizer (``torchao::int4_hqq_quantize_pack``) straight into the
+        layout's storage; everything else runs the plain-torch function and the layout's pack."""
+        assert (
+            zero_point_domain == ZeroPointDomain.FLOAT
+            and mapping_type == MappingType.ASYMMETRIC
+            and quant_min == 0
+        ), "Invalid input parameters for HQQ quantization."
+        from torchao.dtypes.uintx.tensor_core_tiled_layout import (
+            TensorCoreTiledAQTTensorImpl,
+            TensorCoreTiledLayout,
+        )
+
+        if not isinstance(_layout, (TensorCoreTiledLayout, PlainLayout)):
+            raise NotImplementedError(f"HQQ (raw_output) is not served for {type(_layout).__name__}")
+        if block_size[0] != 1:
+            raise NotImplementedError("HQQ along axis 0 is not served")
+        nbits = int(math.log2(quant_max + 1))
+        group_size = max(block_size)
+        compute_dtype = zero_point_dtype if zero_point_dtype is not None else input_float.dtype
+        if (
+            input_float.is_cuda
+            and input_float.dtype == torch.bfloat16
+            and input_float.dim() in (2, 3)
+            and isinstance(_layout, TensorCoreTiledLayout)
+            and all(b == 1 for b in block_size[:-1])
+            and target_dtype == torch.int32
+            and quant_max == 15
+            and group_size in (32, 64, 128, 256)
+            and input_float.shape[-1] % group_size == 0
+            and compute_dtype == torch.bfloat16
+        ):
+            packed, sz, _ = torch.ops.torchao.int4_hqq_quantize_pack(input_float, group_size)
+            tensor_impl = TensorCoreTiledAQTTensorImpl(packed, sz, False, _layout)
+        else:
+            data, scale, zero_point, _ = _choose_qparams_and_quantize_affine_hqq(
+                input_float, nbits=nbits, group_size=group_size, axis=1,
+                compute_dtype=compute_dtype, device=input_float.device, verbose=False,
+                raw_output=False,
+            )
+            data = data.to(target_dtype)
+            data, scale, zero_point = _layout.post_process(data, scale, zero_point, block_size)
+            tensor_impl = cls.get_tensor_impl_constructor(type(_layout))(
+                data, scale, zero_point, _layout
+            )
         return cls(
             tensor_impl,
             block_size,

@@ -24,6 +24,8 @@ Operators:
   * ``int4_quantize_pack`` / ``int8_quantize_rows`` — the weight quantizers of
     ``from_hp_to_intx`` in one pass each (tinygemm qparams + quantize + row-stream pack;
     symmetric per-row int8), bit-exact to the bf16 torch-op formulation.
+  * ``int4_hqq_quantize_pack`` — ``from_hp_to_intx(use_hqq=True)`` on a bf16 GPU weight: the HQQ
+    iteration (quant_primitives.py:1901-2111) in registers, its global stop on the device.
   * ``fp8_weight_only_linear`` — e4m3fn per-row-scaled weight-only linear; replaces
     ``F.linear(x, weight.dequantize(), bias)`` (floatx/float8_layout.py:391-396).
   * ``fp8_quantize_rows`` / ``fp8_dequantize`` — the per-row e4m3fn quantizer of
@@ -241,6 +243,12 @@ lib_moe.define(
     "int group_size) -> Tensor")
 lib_moe.define(
     "moe_combine(Tensor y2, Tensor expert_weights, Tensor inverse, int top_k) -> Tensor")
+# The HQQ int4 quantizer (Int4WeightOnlyConfig(use_hqq=True); csrc/hqq.hip), on a fragment of its
+# own; opchecked in tests/test_gpu_hqq.py. bf16 HIP weight [N, K] or [E, N, K] (one stop decision
+# for the whole tensor) -> the operands of int4_weight_only_linear and the iterations run (int32
+# [1], on the device: the op never synchronises).
+lib_hqq = torch.library.Library("torchao", "FRAGMENT")
+lib_hqq.define("int4_hqq_quantize_pack(Tensor w, int group_size) -> (Tensor, Tensor, Tensor)")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -940,6 +948,43 @@ def _int4_quantize_pack_cuda(w: Tensor, group_size: int, eps: float):
                   ctypes.c_float(eps), _stream(w))
     lead = w.shape[:-1]
     return packed.reshape(*lead, K // 8), sz.reshape(*lead, K // group_size, 2)
+
+
+@torch.library.register_fake("torchao::int4_hqq_quantize_pack")
+def _(w, group_size):
+    torch._check(w.dim() in (2, 3), lambda: "int4 hqq quantize: w must be [N, K] or [E, N, K]")
+    torch._check(group_size in _GROUP_SIZES, lambda: "group_size must be 32, 64, 128, or 256")
+    K = w.size(-1)
+    torch._check(K % group_size == 0, lambda: f"K ({K}) must be divisible by group_size")
+    lead = w.shape[:-1]
+    return (w.new_empty((*lead, K // 8), dtype=torch.int32),
+            w.new_empty((*lead, K // group_size, 2), dtype=torch.bfloat16),
+            w.new_empty((1,), dtype=torch.int32))
+
+
+def _int4_hqq_quantize_pack_cuda(w: Tensor, group_size: int):
+    """bf16 W [(E,) N, K] -> (packed int32 [..., K/8], scales_and_zeros bf16 [..., K/g, 2],
+    iterations run int32 [1]). The scratch comes from the caching allocator: stream-ordered, so a
+    later call may reuse it, and a captured graph keeps its own."""
+    torch._check(w.dtype is torch.bfloat16, lambda: "int4 hqq quantize (HIP) needs a bf16 weight")
+    torch._check(w.dim() in (2, 3), lambda: "int4 hqq quantize: w must be [N, K] or [E, N, K]")
+    torch._check(group_size in _GROUP_SIZES, lambda: "group_size must be 32, 64, 128, or 256")
+    K = w.size(-1)
+    torch._check(K % group_size == 0, lambda: f"K ({K}) must be divisible by group_size")
+    w2 = w.reshape(-1, K)
+    if not w2.is_contiguous() or w2.data_ptr() % 16:
+        w2 = w2.contiguous()
+    R = w2.size(0)
+    packed = torch.empty((R, K // 8), dtype=torch.int32, device=w.device)
+    sz = torch.empty((R, K // group_size, 2), dtype=torch.bfloat16, device=w.device)
+    iters = torch.empty((1,), dtype=torch.int32, device=w.device)
+    nbytes = _lib.lib().tao_int4_hqq_scratch_bytes(R, K)
+    scratch = torch.empty((max(nbytes // 8, 1),), dtype=torch.float64, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("tao_int4_hqq_quantize_bf16", _ptr(w2), _ptr(packed), _ptr(sz), _ptr(iters),
+                  _ptr(scratch), R, K, group_size, _stream(w))
+    lead = w.shape[:-1]
+    return packed.reshape(*lead, K // 8), sz.reshape(*lead, K // group_size, 2), iters
 
 
 @torch.library.register_fake("torchao::int8_quantize_rows")
@@ -1998,6 +2043,7 @@ for _name, _fn in [
 ]:
     if _name not in _native_served_w4a8:
         lib_w4a8.impl(_name, _fn, "CUDA")
+lib_hqq.impl("int4_hqq_quantize_pack", _int4_hqq_quantize_pack_cuda, "CUDA")
 # Host packers (C++ in the same library) so quantize_ works on CPU-resident models.
 lib.impl("int4_pack", _int4_pack_cpu, "CPU")
 lib.impl("int4_unpack", _int4_unpack_cpu, "CPU")

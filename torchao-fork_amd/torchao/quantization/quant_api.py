@@ -210,7 +210,9 @@ class Int4WeightOnlyConfig(AOBaseConfig):
 
     Args mirror the reference (quant_api.py:997-1040): ``group_size`` in {32, 64, 128, 256}
     (default 128), ``layout`` (default ``TensorCoreTiledLayout(inner_k_tiles=8)``),
-    ``use_hqq`` (unsupported here), ``zero_point_domain`` (NONE = layout default, FLOAT),
+    ``use_hqq`` (half-quadratic quantization: the same scales, zero points moved by a proximal
+    iteration, in fp32 on every device; a fused HIP quantizer on bf16 GPU weights),
+    ``zero_point_domain`` (NONE = layout default, FLOAT),
     ``set_inductor_config``, ``preserve_zero`` (None = layout default, False), ``version``
     (1 = AffineQuantizedTensor; 2 = fbgemm tensors, unsupported).
     """
@@ -242,8 +244,6 @@ def _int4_weight_only_quantize_tensor(weight: torch.Tensor, config: Int4WeightOn
         return weight
     if config.version != 1:
         raise NotImplementedError("Int4WeightOnlyConfig(version=2) (fbgemm tensors) is out of scope")
-    if config.use_hqq:
-        raise NotImplementedError("Int4WeightOnlyConfig(use_hqq=True) is out of scope")
     assert type(layout) in LAYOUT_TO_ZERO_POINT_DOMAIN, (
         f"Only support layout: {list(LAYOUT_TO_ZERO_POINT_DOMAIN)}"
     )

@@ -16,14 +16,18 @@ bit-for-bit against fixtures generated from the reference, tests/golden/):
   * ``_choose_qparams_affine_floatx`` / ``_quantize_affine_floatx`` /
     ``_dequantize_affine_floatx``        (:2114-2171; FP6 e3m2 / e2m3, one bf16 scale per row;
     written here from the formats' definition, pinned against the reference by fixtures)
+  * ``_choose_qparams_and_quantize_affine_hqq`` / ``optimize_weights_proximal_legacy`` /
+    ``_shrink_lp_op`` / ``_convert_to_affinequantized_format``  (:1901-2111; HQQ, in fp32 on
+    every device: the reference's CPU arithmetic)
 
 These run with torch ops on whatever device the weight lives on: they execute once at
 quantization time, outside the per-token hot loop (which is the HIP kernels behind torchao.ops).
 """
 
 import functools
+import math
 from enum import Enum, auto
-from typing import List, Optional, Tuple, Union
+from typing import Callable, List, Optional, Tuple, Union
 
 import torch
 
@@ -52,6 +56,11 @@ __all__ = [
     "_choose_qparams_affine_floatx",
     "_quantize_affine_floatx",
     "_dequantize_affine_floatx",
+    "_shrink_lp_op",
+    "optimize_weights_proximal_legacy",
+    "_convert_to_affinequantized_format",
+    "_choose_qparams_and_quantize_affine_hqq",
+    "HQQ_OPT_PARAMS",
 ]
 
 
@@ -619,6 +628,156 @@ def _dequantize_affine_floatx(tensor: torch.Tensor, scale: torch.Tensor, ebits: 
     _floatx_check(ebits, mbits)
     values = _floatx_code_values(ebits, mbits, tensor.device)[tensor.long()]
     return (values * scale.to(torch.float32).view(-1, 1)).to(output_dtype)
+
+
+# ---------------------------------------------------------------------------------------------
+# HQQ (half-quadratic quantization; reference :1901-2111)
+# ---------------------------------------------------------------------------------------------
+HQQ_OPT_PARAMS = {"lp_norm": 0.7, "beta": 1e1, "kappa": 1.01, "iters": 20, "early_stop": True}
+
+
+def _shrink_lp_op(x: torch.Tensor, beta: float, lp_norm: float) -> torch.Tensor:
+    """Proximal operator of the lp norm: sign(x) * relu(|x| - |x|^(p-1) / beta)."""
+    if lp_norm == 1:
+        return torch.sign(x) * torch.nn.functional.relu(torch.abs(x) - 1.0 / beta)
+    return torch.sign(x) * torch.nn.functional.relu(
+        torch.abs(x) - (1.0 / beta) * torch.pow(torch.abs(x), lp_norm - 1)
+    )
+
+
+def _hqq_proximal_loop(W_f, scale, zero, min_max, axis, opt_params):
+    """The proximal iteration on zero alone (scale is fixed). Returns the final zero and the
+    error e_i of every iteration run (mean |W - W_r| over the whole tensor, measured with the
+    zero from before that iteration's update). The update of an iteration is applied before its
+    stop test, so a loop that stops at iteration i has updated zero i + 1 times."""
+    lp_norm, beta, kappa = opt_params["lp_norm"], opt_params["beta"], opt_params["kappa"]
+    best_error, errors = 1e4, []
+    for _ in range(opt_params["iters"]):
+        W_q = torch.round(W_f * scale + zero).clamp(min_max[0], min_max[1])
+        W_r = (W_q - zero) / scale
+        W_e = _shrink_lp_op(W_f - W_r, beta, lp_norm)
+        zero = torch.mean(W_q - (W_f - W_e) * scale, axis=axis, keepdim=True)
+        beta *= kappa
+        current_error = float(torch.abs(W_f - W_r).mean())
+        errors.append(current_error)
+        if opt_params["early_stop"]:
+            if current_error < best_error:
+                best_error = current_error
+            else:
+                break
+    return zero, errors
+
+
+@torch.inference_mode()
+def optimize_weights_proximal_legacy(
+    tensor: torch.Tensor,
+    scale: torch.Tensor,
+    zero: torch.Tensor,
+    min_max: list,
+    axis: int = 0,
+    dtype: Union[torch.dtype, None] = None,
+    device: Union[str, None] = None,
+    verbose: bool = False,
+    opt_params: dict = HQQ_OPT_PARAMS,
+) -> tuple:
+    """Proximal solver of || W - dequantize(quantize(W)) ||_p^p over the zero point (reference
+    :1913-1972). ``dtype=None`` is float32 on every device: the reference picks float16 on a GPU,
+    this package serves its CPU arithmetic everywhere."""
+    device = tensor.device if (device is None) else torch.device(device)
+    if dtype is None:
+        dtype = torch.float32
+    W_f = tensor.to(dtype=dtype, device=device)
+    scale = scale.to(dtype=dtype, device=device)
+    zero = zero.to(dtype=dtype, device=device)
+    zero, errors = _hqq_proximal_loop(W_f, scale, zero, min_max, axis, opt_params)
+    if verbose:
+        for i, e in enumerate(errors):
+            print("Iter " + str(i + 1), " | Error: " + str(e))
+    scale = scale.to(tensor.device)
+    zero = zero.to(tensor.device)
+    W_q = torch.round(tensor * scale + zero).clamp(min_max[0], min_max[1])
+    return W_q, scale, zero
+
+
+def _is_divisible(val1: int, val2: int) -> bool:
+    return int(val2 * math.ceil(val1 / val2)) == val1
+
+
+def _convert_to_affinequantized_format(
+    W_q: torch.Tensor,
+    scale: torch.Tensor,
+    zero: torch.Tensor,
+    nbits: int,
+    shape: Union[List, Tuple, torch.Size],
+) -> Tuple:
+    """HQQ's W = (W_q - zero) * scale -> the affine form (W_q - mid_point) * scale_ao + zero_ao
+    (reference :1980-1994)."""
+    quant_min = 0
+    quant_max = 2**nbits - 1
+    mid_point = (quant_max + quant_min + 1) / 2
+    zero_ao = ((mid_point - zero.float()) * scale.float()).to(zero.dtype)
+    scale_ao = scale
+    W_q_ao = W_q.view(shape)
+    return W_q_ao, scale_ao, zero_ao
+
+
+def _choose_qparams_and_quantize_affine_hqq(
+    tensor: torch.Tensor,
+    nbits: float = 4,
+    group_size: int = 64,
+    optimize: bool = True,
+    axis: int = 1,
+    compute_dtype: torch.dtype = torch.float16,
+    device: str = "cuda",
+    verbose: bool = False,
+    raw_output: bool = False,
+    optimize_weights: Callable = optimize_weights_proximal_legacy,
+) -> tuple:
+    """HQQ quantizer (reference :1998-2111): the min/max scale of every group, clamped at 2e4 and
+    never changed afterwards, and a zero point moved by the proximal solver. Returns
+    (W_q uint8 of the input's shape, scale, zero, shape) with scale / zero [numel / g, 1] in
+    ``compute_dtype`` and in the affine form (W_q - 8) * scale + zero. Plain torch ops in fp32;
+    bf16 GPU weights of the int4 layout take ``torchao::int4_hqq_quantize_pack`` instead
+    (AffineQuantizedTensor.from_hp_to_intx). ``axis=1``, ``raw_output=False`` are served."""
+    assert axis in [0, 1], "axis should be either 0 or 1"
+    if axis != 1 or raw_output:
+        raise NotImplementedError("HQQ: only axis=1 with raw_output=False is served")
+    if group_size is not None:
+        assert _is_divisible(tensor.numel(), group_size), (
+            "group_size should be divisble by the total tensor dimensions. shape: "
+            + str(tensor.shape)
+            + ", group_size: "
+            + str(group_size)
+        )
+    W = tensor.to(device=device, dtype=torch.float32)
+    shape = W.shape
+    if group_size is not None:
+        W = W.reshape([-1, group_size])
+    _min = W.min(axis=axis, keepdim=True)[0]
+    _max = W.max(axis=axis, keepdim=True)[0]
+    max_v = round(2**nbits - 1)
+    min_max = [0, max_v]
+    # scalar / tensor is reciprocal(tensor) * scalar in torch: two roundings, which csrc/hqq.hip
+    # reproduces (an ulp in the scale moves rint(-min * scale) on a tie, and with it the group)
+    scale = (max_v / (_max - _min)).clamp(max=2e4)
+    zero = -_min * scale
+    if nbits in [4]:
+        zero = _Round.apply(zero)
+    if optimize:
+        W_q, scale, zero = optimize_weights(
+            tensor=W, scale=scale, zero=zero, min_max=min_max, axis=axis, device=device,
+            verbose=verbose,
+        )
+    else:
+        zero = zero.to(compute_dtype)
+        scale = scale.to(compute_dtype)
+        W_q = _Round.apply(W * scale + zero).clamp(min_max[0], min_max[1])
+    scale = 1.0 / scale
+    W_q, scale, zero = _convert_to_affinequantized_format(W_q, scale, zero, nbits, shape)
+    W_q = W_q.to(dtype=torch.uint8, device=device)
+    scale = scale.to(dtype=compute_dtype, device=device)
+    zero = zero.to(dtype=compute_dtype, device=device)
+    return W_q, scale, zero, shape
 
 
 # enums appear in flattened AQT metadata: allow weights_only=True checkpoint loads
