@@ -605,6 +605,34 @@ int tao_moe_combine_bf16(const uint16_t* y2, const uint16_t* expert_weights,
                          const int32_t* inverse, uint16_t* out, int64_t T, int64_t A, int64_t D,
                          void* stream);
 
+/* ---- uintx weight-only, 1 to 7 bits (csrc/uintx.hip; UIntXWeightOnlyConfig,
+ * torchao/dtypes/uintx/uintx_layout.py) --------------------------------------------------------
+ * A weight [N][K] of `bits`-bit codes is the reference's UintxLayout shards (pack_dim = -1), read
+ * in place: a code is cut into its 4-, 2- and 1-bit parts (the set bits of `bits`, low part
+ * first), each part a uint8 stream per row: s4 [N][K/2], s2 [N][K/4], s1 [N][K/8]; a width passes
+ * exactly its shards and null for the others. Inside a shard of width w (S = 8 / w fields per
+ * byte), field f of byte b of a row holds element f * (K / S) + b. scale bf16 [N][K / group],
+ * zero_point int32 [N][K / group], zero points in [0, 2^bits - 1]. K % 128 == 0, group_size % 16
+ * == 0, K % group_size == 0; shards 16-B aligned. */
+
+/* w[n][k] = bf16( bf16(q - zp) * scale ), the reference's dequantize_affine on the unpacked codes
+ * to bf16 bit for bit (replaces bitpacking.unpack + dequantize_affine). w 16-B aligned. */
+int tao_uintx_dequant_bf16(const uint8_t* s4, const uint8_t* s2, const uint8_t* s1,
+                           const uint16_t* scale, const int32_t* zero_point, uint16_t* w,
+                           int64_t N, int64_t K, int bits, int group_size, void* stream);
+
+/* y[m][n] = bf16( sum_k x[m][k] * (q[n][k] - zp) * scale ), products unrounded and the sum in
+ * fp32; with a bias a second rounding, bf16(y + bias[n]). x bf16 [M][K], y bf16 [M][N]. The
+ * decode GEMV (uintx_gemv_kernel): one launch up to 8 tokens, a sequence of 8-token launches
+ * beyond. The op torchao::uintx_weight_only_linear calls it up to the boundary of
+ * tao_uintx_linear_route (torchao_mi355x_tune.h) and dequantizes + matmuls above. Any N >= 0;
+ * M >= 0 (M == 0 is a no-op); x 16-B aligned. Replaces the unpack + dequantize + F.linear of the
+ * reference, which has no kernel for this layout on any device. */
+int tao_uintx_linear_bf16(const uint16_t* x, const uint8_t* s4, const uint8_t* s2,
+                          const uint8_t* s1, const uint16_t* scale, const int32_t* zero_point,
+                          const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                          int bits, int group_size, void* stream);
+
 /* ---- int8 KV cache (AffineQuantizedKVCache, torchao/_models/llama/model.py:198-240) -----------
  * k_cache / v_cache [B][Hkv][T][128] int8 codes, k_scale / v_scale [B][Hkv][T] bf16, one scale per
  * row: symmetric, [-127, 127], eps 1e-5, the arithmetic of _quantize_activation_per_token_absmax in

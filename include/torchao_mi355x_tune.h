@@ -237,6 +237,24 @@ int tao_moe_dual(int64_t R, int64_t E);
 /* Launch shape of the grouped (MoE) int4 GEMM (calling thread only; tests and A/B runs): bm 0 =
  * built-in rule, 16, 32 or 64; dual 0 = built-in rule, 1 = gate and up in two launches, 2 = one. */
 int tao_tune_moe(int bm, int dual);
+/* The route torchao::uintx_weight_only_linear takes for this call under the calling thread's
+ * tao_tune_uintx: 1 = the GEMV, tao_uintx_linear_bf16 (up to the built-in boundary M of
+ * csrc/uintx_host.h for this bit width); 2 = tao_uintx_dequant_bf16 into a temporary and the bf16
+ * matmul, which needs an allocator and lives in the op (csrc/torch_ops.cpp). */
+int tao_uintx_linear_route(int64_t M, int64_t N, int64_t K, int bits);
+/* Bytes of each shard piece per lane unit (4, 8 or 16) of the GEMV launch that serves M tokens
+ * (its first 8-token piece) under the calling thread's tao_tune_uintx: the built-in rule of
+ * csrc/uintx_host.h on (K, bits, M), or the forced unit, capped at 8 for 8 rows per wave. */
+int tao_uintx_gemv_unit(int64_t M, int64_t K, int bits);
+/* Route and launch shape of the uintx linear (calling thread only; tests and A/B runs): the first
+ * five arguments as tao_tune_nf4's; unit = bytes of each shard piece per lane unit of the GEMV:
+ * 0 = built-in (from K, bits and M), 4, 8 or 16 (32, 64 or 128 codes per lane); x_lds = where the
+ * 4- and 8-token tiles take x from: 0 = built-in, 1 = through L1, 2 = staged in LDS where it fits. */
+int tao_tune_uintx(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups,
+                   int unit, int x_lds);
+/* 1 where the GEMV launch that serves M tokens stages x in LDS, 0 where it reads x through L1,
+ * under the calling thread's tao_tune_uintx (csrc/uintx_host.h uintx_x_lds). */
+int tao_uintx_gemv_x_lds(int64_t M, int64_t K, int bits);
 /* Per-token int8 quantisation kernel (A/B only): 0 = one wave per token, the token held in
  * registers (default, K <= 8192); 1 = one 256-thread workgroup per token. Bit-identical. */
 int tao_tune_int8_quant(int block);

@@ -11,7 +11,7 @@
 // rowwise_scaled_linear_cutlass_s8s4, int8_quantize_per_token_f32, int4_quantize_rows_packed,
 // w4a8_dyn_linear, and the NF4 set nf4_quantize_blocks, nf4_dequantize, nf4_linear, and the FP6 set
 // fp6_quantize_rows, fp6_dequantize, fp6_weight_only_linear, and the MoE set moe_route,
-// int4_grouped_linear, moe_combine.
+// int4_grouped_linear, moe_combine, and the uintx set uintx_dequantize, uintx_weight_only_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -31,6 +31,7 @@
 #include "../../include/torchao_mi355x_tune.h"  // tao_nf4_linear_route, tao_fp6_linear_route
 #include "fp6_host.h"
 #include "moe_host.h"
+#include "uintx_host.h"
 
 namespace {
 
@@ -1296,9 +1297,122 @@ Tensor moe_combine(const Tensor& y2, const Tensor& expert_weights, const Tensor&
   return out;
 }
 
+// ---- uintx weight-only, 1 to 7 bits (torchao/dtypes/uintx/uintx_layout.py; csrc/uintx.hip) ------
+// int4_shard / int2_shard / int1_shard uint8 [N, K/2] / [N, K/4] / [N, K/8] (exactly the shards of
+// the width's set bits), scale bf16 and zero_point int32 of N * K / group_size elements
+struct UintxWeight {
+  Tensor s4, s2, s1, scale, zp;  // absent shards undefined
+  int64_t N, K;
+  const uint8_t* p4() const { return s4.defined() ? cptr<uint8_t>(s4) : nullptr; }
+  const uint8_t* p2() const { return s2.defined() ? cptr<uint8_t>(s2) : nullptr; }
+  const uint8_t* p1() const { return s1.defined() ? cptr<uint8_t>(s1) : nullptr; }
+};
+UintxWeight check_uintx_weight(const std::optional<Tensor>& s4, const std::optional<Tensor>& s2,
+                               const std::optional<Tensor>& s1, const Tensor& scale,
+                               const Tensor& zero_point, int64_t bits, int64_t group,
+                               const char* op) {
+  TORCH_CHECK(tao::uintx_bits_ok(bits), op, ": bit_width ", bits, " is not served; served: 1 to 7");
+  const std::optional<Tensor>* shards[3] = {&s4, &s2, &s1};
+  const int width[3] = {4, 2, 1};
+  const char* names[3] = {"int4_shard", "int2_shard", "int1_shard"};
+  UintxWeight p;
+  p.N = p.K = -1;
+  Tensor* out[3] = {&p.s4, &p.s2, &p.s1};
+  for (int i = 0; i < 3; ++i) {
+    const bool want = (bits & width[i]) != 0;
+    TORCH_CHECK(shards[i]->has_value() == want, op, ": uint", bits, (want ? " needs " : " has no "),
+                names[i]);
+    if (!want) continue;
+    const Tensor& t = **shards[i];
+    TORCH_CHECK(t.is_cuda(), op, ": expected ", names[i], " on a HIP device, got ", t.device());
+    TORCH_CHECK(t.dim() == 2 && t.scalar_type() == at::kByte, op, ": ", names[i],
+                " must be a 2D uint8 tensor, got ", t.scalar_type(), " ", t.sizes());
+    const int64_t N = t.size(0), K = t.size(1) * 8 / width[i];
+    TORCH_CHECK(p.N < 0 || (p.N == N && p.K == K), op, ": ", names[i], " ", t.sizes(),
+                " does not match the other shards' N = ", p.N, ", K = ", p.K);
+    p.N = N, p.K = K;
+    if (out[0]->defined()) check_device(*out[0], t, names[i]);
+    else if (out[1]->defined()) check_device(*out[1], t, names[i]);
+    Tensor c = t;
+    if (!c.is_contiguous() || reinterpret_cast<uintptr_t>(c.data_ptr()) % 16) c = c.clone();
+    *out[i] = c;
+  }
+  TORCH_CHECK(tao::uintx_shape_ok(p.K, group), op, ": K (", p.K,
+              ") must be a positive multiple of 128 and group_size (", group,
+              ") a multiple of 16 that divides K");
+  const Tensor& any = p.s4.defined() ? p.s4 : p.s2.defined() ? p.s2 : p.s1;
+  const int64_t nq = p.N * (p.K / group);
+  TORCH_CHECK(scale.scalar_type() == at::kBFloat16, op, " (HIP) needs a bf16 scale, got ",
+              scale.scalar_type());
+  TORCH_CHECK(zero_point.scalar_type() == at::kInt, op, " needs an int32 zero_point, got ",
+              zero_point.scalar_type());
+  TORCH_CHECK(scale.numel() == nq && zero_point.numel() == nq, op,
+              ": scale and zero_point must have N * K / group_size = ", nq, " elements, got ",
+              scale.numel(), " and ", zero_point.numel());
+  check_device(any, scale, "scale");
+  check_device(any, zero_point, "zero_point");
+  p.scale = scale.reshape({-1}).contiguous();
+  p.zp = zero_point.reshape({-1}).contiguous();
+  return p;
+}
+
+Tensor uintx_dequantize_checked(const UintxWeight& p, int64_t bits, int64_t group) {
+  Tensor w = at::empty({p.N, p.K}, p.scale.options());
+  check_rc(tao_uintx_dequant_bf16(p.p4(), p.p2(), p.p1(), cptr<uint16_t>(p.scale),
+                                  cptr<int32_t>(p.zp), mptr<uint16_t>(w), p.N, p.K, (int)bits,
+                                  (int)group, stream_of(p.scale)),
+           "tao_uintx_dequant_bf16");
+  return w;
+}
+
+Tensor uintx_dequantize(const std::optional<Tensor>& s4, const std::optional<Tensor>& s2,
+                        const std::optional<Tensor>& s1, const Tensor& scale,
+                        const Tensor& zero_point, int64_t bits, int64_t group) {
+  const UintxWeight p =
+      check_uintx_weight(s4, s2, s1, scale, zero_point, bits, group, "uintx_dequantize");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(scale.device());
+  return uintx_dequantize_checked(p, bits, group);
+}
+
+Tensor uintx_weight_only_linear(const Tensor& x, const std::optional<Tensor>& s4,
+                                const std::optional<Tensor>& s2, const std::optional<Tensor>& s1,
+                                const Tensor& scale, const Tensor& zero_point, int64_t bits,
+                                int64_t group, const std::optional<Tensor>& bias) {
+  const char* op = "uintx_weight_only_linear";
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, op, " (HIP) needs bf16 x, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1, op, ": x must have at least one dimension");
+  const UintxWeight p = check_uintx_weight(s4, s2, s1, scale, zero_point, bits, group, op);
+  check_device(x, p.scale, "the weight");
+  const int64_t N = p.N, K = p.K;
+  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
+  TORCH_CHECK(!bias.has_value() || bias->numel() == N, op, ": bias must have N = ", N, " elements");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  if (M > 0 && N > 0 && tao_uintx_linear_route(M, N, K, (int)bits) == 2) {
+    // W^ into a temporary of the caching allocator, then the bf16 matmul; the bias is a second
+    // rounding, as on the other route
+    const Tensor w = uintx_dequantize_checked(p, bits, group);
+    Tensor y = at::linear(x2, w);
+    if (b) y = y + *b;
+    return y.reshape(out_shape(x, N));
+  }
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  check_rc(tao_uintx_linear_bf16(cptr<uint16_t>(x2), p.p4(), p.p2(), p.p1(),
+                                 cptr<uint16_t>(p.scale), cptr<int32_t>(p.zp),
+                                 b ? cptr<uint16_t>(*b) : nullptr, mptr<uint16_t>(y), M, N, K,
+                                 (int)bits, (int)group, stream_of(x)),
+           "tao_uintx_linear_bf16");
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
+  m.impl("uintx_dequantize", &uintx_dequantize);
+  m.impl("uintx_weight_only_linear", &uintx_weight_only_linear);
   m.impl("moe_route", &moe_route);
   m.impl("int4_grouped_linear", &int4_grouped_linear);
   m.impl("moe_combine", &moe_combine);
@@ -1376,6 +1490,11 @@ extern "C" const char* tao_torch_ops_served_nf4(void) {
 // The FP6 ops served here; they have no Python kernels either.
 extern "C" const char* tao_torch_ops_served_fp6(void) {
   return "fp6_quantize_rows,fp6_dequantize,fp6_weight_only_linear";
+}
+
+// The uintx ops served here; they have no Python kernels either.
+extern "C" const char* tao_torch_ops_served_uintx(void) {
+  return "uintx_dequantize,uintx_weight_only_linear";
 }
 
 // The MoE ops served here; they have no Python kernels either.

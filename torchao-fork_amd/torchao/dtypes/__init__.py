@@ -28,6 +28,10 @@ from .uintx import (
     PlainAQTTensorImpl,
     TensorCoreTiledAQTTensorImpl,
     TensorCoreTiledLayout,
+    UintxAQTTensorImpl,
+    UintxLayout,
+    UintxTensor,
+    to_uintx,
 )
 from .utils import AQTTensorImpl, Layout, PlainLayout
 
@@ -41,6 +45,10 @@ __all__ = [
     "TensorCoreTiledAQTTensorImpl",
     "CutlassInt4PackedLayout",
     "Int4PackedTensorImpl",
+    "UintxLayout",
+    "UintxAQTTensorImpl",
+    "UintxTensor",
+    "to_uintx",
     "Float8Layout",
     "Float8AQTTensorImpl",
     "Float8MMConfig",

@@ -221,6 +221,14 @@ class AffineQuantizedTensor(TorchAOBaseTensor):
         output_dtype = self.dtype if output_dtype is None else output_dtype
         if hasattr(self.tensor_impl, "packed_floatx_data"):
             return self._dequantize_floatx(output_dtype)
+        from torchao.dtypes.uintx.uintx_layout import UintxAQTTensorImpl
+
+        if isinstance(self.tensor_impl, UintxAQTTensorImpl):
+            # the shards dequantized in place where the HIP kernel serves, else the formula below
+            dq = self.tensor_impl._dequantize_hip(self.block_size, self.zero_point_domain,
+                                                  output_dtype)
+            if dq is not None:
+                return dq
         data, scale, zero_point = self.tensor_impl.get_plain()
         if data.dtype in FP8_TYPES:
             return self._dequantize_float8(data, scale, output_dtype)

@@ -10,7 +10,8 @@ subclass usable inside ``nn.Linear``, ``DTensor.from_local`` and state-dict load
 The pairs registered here are the MI355X ones, in the reference's order of precedence:
 int8 dynamic-activation x int8 weight, int8 weight-only, int4 weight-only (gfx950 layout),
 float8 (e4m3fn) weight-only, float8 dynamic-activation, int8 dynamic-activation x packed int4
-weight (CutlassInt4PackedLayout), FP6 weight-only (FloatxTensorCoreLayout, bf16 activations).
+weight (CutlassInt4PackedLayout), FP6 weight-only (FloatxTensorCoreLayout, bf16 activations),
+uintx (1- to 7-bit) weight-only (UintxLayout, bf16 activations).
 """
 
 import logging
@@ -42,6 +43,10 @@ from torchao.dtypes.uintx.plain_layout import (
 from torchao.dtypes.uintx.tensor_core_tiled_layout import (
     _linear_bf16_act_uint4_weight_check,
     _linear_bf16_act_uint4_weight_impl,
+)
+from torchao.dtypes.uintx.uintx_layout import (
+    _linear_bf16_act_uintx_weight_check,
+    _linear_bf16_act_uintx_weight_impl,
 )
 from torchao.utils import fill_defaults
 
@@ -89,6 +94,7 @@ for _cond, _impl in [
     (_linear_fp8_act_fp8_weight_check, _linear_fp8_act_fp8_weight_impl),
     (_linear_int8_act_int4_weight_cutlass_check, _linear_int8_act_int4_weight_cutlass_impl),
     (_linear_bf16_act_floatx_weight_check, _linear_bf16_act_floatx_weight_impl),
+    (_linear_bf16_act_uintx_weight_check, _linear_bf16_act_uintx_weight_impl),
 ]:
     register_aqt_quantized_linear_dispatch(_cond, _impl)
 

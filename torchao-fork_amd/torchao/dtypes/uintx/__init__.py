@@ -1,6 +1,8 @@
 from .cutlass_int4_packed_layout import CutlassInt4PackedLayout, Int4PackedTensorImpl
 from .plain_layout import PlainAQTTensorImpl
 from .tensor_core_tiled_layout import TensorCoreTiledAQTTensorImpl, TensorCoreTiledLayout
+from .uintx_layout import UintxAQTTensorImpl, UintxLayout, UintxTensor, to_uintx
 
 __all__ = ["CutlassInt4PackedLayout", "Int4PackedTensorImpl", "PlainAQTTensorImpl",
-           "TensorCoreTiledAQTTensorImpl", "TensorCoreTiledLayout"]
+           "TensorCoreTiledAQTTensorImpl", "TensorCoreTiledLayout", "UintxAQTTensorImpl",
+           "UintxLayout", "UintxTensor", "to_uintx"]

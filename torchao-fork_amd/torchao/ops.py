@@ -249,6 +249,21 @@ lib_moe.define(
 # [1], on the device: the op never synchronises).
 lib_hqq = torch.library.Library("torchao", "FRAGMENT")
 lib_hqq.define("int4_hqq_quantize_pack(Tensor w, int group_size) -> (Tensor, Tensor, Tensor)")
+# The uintx ops (UIntXWeightOnlyConfig, torchao/dtypes/uintx/uintx_layout.py; csrc/uintx.hip), on
+# a fragment of their own; opchecked in tests/test_gpu_uintx.py. The weight is the UintxLayout
+# shards as they are stored: int4_shard uint8 [N, K/2], int2_shard [N, K/4], int1_shard [N, K/8],
+# exactly those of the set bits of bit_width (1..7) and None for the others; scale bf16 and
+# zero_point int32 of N * K / group_size elements. K % 128 == 0, group_size % 16 == 0. bf16 HIP
+# tensors only. Their CUDA kernels exist in C++ only (csrc/torch_ops.cpp), so without
+# libtorchao_ops.so a call raises instead of falling back.
+lib_uintx = torch.library.Library("torchao", "FRAGMENT")
+lib_uintx.define(
+    "uintx_dequantize(Tensor? int4_shard, Tensor? int2_shard, Tensor? int1_shard, Tensor scale, "
+    "Tensor zero_point, int bit_width, int group_size) -> Tensor")
+lib_uintx.define(
+    "uintx_weight_only_linear(Tensor x, Tensor? int4_shard, Tensor? int2_shard, "
+    "Tensor? int1_shard, Tensor scale, Tensor zero_point, int bit_width, int group_size, "
+    "Tensor? bias=None) -> Tensor")
 
 _GROUP_SIZES = (32, 64, 128, 256)
 
@@ -1841,6 +1856,48 @@ def _(y2, expert_weights, inverse, top_k):
     return y2.new_empty((y2.shape[0] // top_k, y2.shape[1]))
 
 
+# ---------------------------------------------------------------------------------------------
+# uintx (csrc/uintx.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
+# ---------------------------------------------------------------------------------------------
+def _check_uintx_weight(s4, s2, s1, scale, zero_point, bits, group, op):
+    """(N, K) of the weight the shards describe."""
+    torch._check(1 <= bits <= 7, lambda: f"{op}: bit_width {bits} is not served; served: 1 to 7")
+    N = K = None
+    for w, t in ((4, s4), (2, s2), (1, s1)):
+        torch._check((t is not None) == bool(bits & w),
+                     lambda: f"{op}: uint{bits} takes exactly the shards of its set bits")
+        if t is None:
+            continue
+        torch._check(t.dtype is torch.uint8 and t.dim() == 2,
+                     lambda: f"{op}: int{w}_shard must be a 2D uint8 tensor")
+        n, k = t.shape[0], t.shape[1] * 8 // w
+        torch._check(N is None or (N, K) == (n, k),
+                     lambda: f"{op}: the shards do not describe one [N, K] weight")
+        N, K = n, k
+    torch._check(K > 0 and K % 128 == 0 and group > 0 and group % 16 == 0 and K % group == 0,
+                 lambda: f"{op}: K ({K}) must be a positive multiple of 128 and group_size "
+                         f"({group}) a multiple of 16 that divides K")
+    nq = N * (K // group)
+    torch._check(scale.numel() == nq and zero_point.numel() == nq,
+                 lambda: f"{op}: scale and zero_point must have N * K / group_size = {nq} elements")
+    return N, K
+
+
+@torch.library.register_fake("torchao::uintx_dequantize")
+def _(int4_shard, int2_shard, int1_shard, scale, zero_point, bit_width, group_size):
+    N, K = _check_uintx_weight(int4_shard, int2_shard, int1_shard, scale, zero_point, bit_width,
+                               group_size, "uintx_dequantize")
+    return scale.new_empty((N, K), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("torchao::uintx_weight_only_linear")
+def _(x, int4_shard, int2_shard, int1_shard, scale, zero_point, bit_width, group_size, bias=None):
+    N, K = _check_uintx_weight(int4_shard, int2_shard, int1_shard, scale, zero_point, bit_width,
+                               group_size, "uintx_weight_only_linear")
+    torch._check(x.shape[-1] == K, lambda: f"x last dim {x.shape[-1]} != K {K}")
+    return x.new_empty((*x.shape[:-1], N), dtype=torch.bfloat16)
+
+
 # The per-linear ops take their CUDA kernels from libtorchao_ops.so (csrc/torch_ops.cpp: the
 # same checks, then the C-ABI, with no Python frame: ~19 -> ~7 µs of host time per call at
 # M = 1, profiles/r2_eager_overhead*.json). The Python impls below serve the rest, and these
@@ -1858,6 +1915,7 @@ _native_served_smoothquant: frozenset = frozenset()
 _native_served_w4a8: frozenset = frozenset()
 _native_served_nf4: frozenset = frozenset()
 _native_served_fp6: frozenset = frozenset()
+_native_served_uintx: frozenset = frozenset()
 _native_served_moe: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
@@ -1899,6 +1957,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_fp6
         _served.restype = ctypes.c_char_p
         _native_served_fp6 = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_uintx
+        _served.restype = ctypes.c_char_p
+        _native_served_uintx = frozenset(_served().decode().split(","))
         _served = _ops_dll.tao_torch_ops_served_moe
         _served.restype = ctypes.c_char_p
         _native_served_moe = frozenset(_served().decode().split(","))
@@ -1960,6 +2021,11 @@ def native_dispatch_fp6() -> frozenset:
 def native_dispatch_moe() -> frozenset:
     """The MoE ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
     return _native_served_moe
+
+
+def native_dispatch_uintx() -> frozenset:
+    """The uintx ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
+    return _native_served_uintx
 
 
 def native_dispatch_w4a8() -> frozenset:

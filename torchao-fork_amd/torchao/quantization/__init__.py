@@ -18,6 +18,7 @@ from torchao.quantization.quant_api import (
     Int8DynamicActivationInt4WeightConfig,
     Int8DynamicActivationInt8WeightConfig,
     Int8WeightOnlyConfig,
+    UIntXWeightOnlyConfig,
     ModuleFqnToConfig,
     float8_dynamic_activation_float8_weight,
     float8_weight_only,
@@ -27,6 +28,7 @@ from torchao.quantization.quant_api import (
     int8_dynamic_activation_int8_weight,
     int8_weight_only,
     quantize_,
+    uintx_weight_only,
 )
 from torchao.quantization.quant_primitives import (
     MappingType,
@@ -49,6 +51,8 @@ __all__ = [
     "Float8DynamicActivationFloat8WeightConfig",
     "FPXWeightOnlyConfig",
     "fpx_weight_only",
+    "UIntXWeightOnlyConfig",
+    "uintx_weight_only",
     "PerAxis",
     "PerRow",
     "PerTensor",

@@ -70,6 +70,8 @@ __all__ = [
     "float8_weight_only",
     "FPXWeightOnlyConfig",
     "fpx_weight_only",
+    "UIntXWeightOnlyConfig",
+    "uintx_weight_only",
     "Float8DynamicActivationFloat8WeightConfig",
     "float8_dynamic_activation_float8_weight",
     "ModuleFqnToConfig",
@@ -656,6 +658,93 @@ def _fpx_weight_only_transform(module: nn.Module, config: FPXWeightOnlyConfig) -
 
 # quantize_ runs this over every selected module before the first swap
 _fpx_weight_only_transform.precheck = _fpx_precheck
+
+
+# ---------------------------------------------------------------------------------------------
+# uintx (1- to 7-bit) weight-only
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class UIntXWeightOnlyConfig(AOBaseConfig):
+    """Asymmetric per-group weight-only quantization to ``torch.uint1`` .. ``torch.uint7``,
+    bit-packed into ``UintxLayout`` shards (reference quant_api.py:1865-1971, same fields and
+    defaults): integer zero points (int32), scales in the weight's dtype, ``group_size`` along
+    the input dimension (default 64), ``pack_dim`` -1.
+
+    Served here: the seven sub-byte widths with ``pack_dim=-1`` and ``use_hqq=False`` on 2-D
+    weights. ``use_hqq=True``, ``torch.uint8``, another ``pack_dim`` and 3-D weights raise
+    ``NotImplementedError``, and ``in_features % group_size != 0`` raises the reference's
+    ``AssertionError``, all before ``quantize_`` touches a module (the reference raises the last
+    one in the middle of the walk, with earlier modules already swapped)."""
+
+    dtype: torch.dtype
+    group_size: int = 64
+    pack_dim: int = -1
+    use_hqq: bool = False
+    set_inductor_config: bool = True
+
+    def __post_init__(self):
+        torch._C._log_api_usage_once("torchao.quantization.UIntXWeightOnlyConfig")
+
+
+uintx_weight_only = UIntXWeightOnlyConfig
+
+_UINTX_SERVED = ("served: torch.uint1 .. torch.uint7 with pack_dim=-1 and use_hqq=False on 2-D "
+                 "weights")
+
+
+def _uintx_precheck(module: nn.Module, config: UIntXWeightOnlyConfig) -> None:
+    """What this config refuses, raised before ``quantize_`` swaps any weight."""
+    from torchao.dtypes.uintx.uintx_layout import _DTYPE_TO_BIT_WIDTH
+
+    if config.use_hqq:
+        raise NotImplementedError(
+            f"UIntXWeightOnlyConfig(use_hqq=True) is not implemented on MI355X; {_UINTX_SERVED}")
+    if config.dtype not in _DTYPE_TO_BIT_WIDTH:
+        raise NotImplementedError(
+            f"UIntXWeightOnlyConfig(dtype={config.dtype}) is not implemented on MI355X "
+            f"(torch.uint8 is Int8WeightOnlyConfig's ground); {_UINTX_SERVED}")
+    if config.pack_dim != -1:
+        raise NotImplementedError(
+            f"UIntXWeightOnlyConfig(pack_dim={config.pack_dim}) is not implemented on MI355X; "
+            f"{_UINTX_SERVED}")
+    weight = module.weight
+    if weight.dim() != 2:
+        raise NotImplementedError(
+            f"UIntXWeightOnlyConfig on a {weight.dim()}-D weight is not implemented on MI355X; "
+            f"{_UINTX_SERVED}")
+    in_dim = weight.shape[1]
+    if in_dim % config.group_size != 0:  # the reference's error; raised, so that -O keeps it
+        raise AssertionError(
+            f"Expecting input size at 1 dimension: {in_dim} to be divisible by block_size at 1 "
+            f"dimension: {config.group_size}")
+    if in_dim % 8 != 0:
+        raise AssertionError(f"pack dimension size ({in_dim}) is not divisible by 8")
+
+
+@register_quantize_module_handler(UIntXWeightOnlyConfig)
+def _uintx_weight_only_transform(module: nn.Module, config: UIntXWeightOnlyConfig) -> nn.Module:
+    _uintx_precheck(module, config)
+    if config.set_inductor_config:
+        torchao.quantization.utils.recommended_inductor_config_setter()
+    from torchao.dtypes.uintx.uintx_layout import UintxLayout
+
+    # the existing plain-torch primitives + pack, on the weight's device, once per weight
+    new_weight = to_affine_quantized_intx(
+        module.weight,
+        MappingType.ASYMMETRIC,
+        (1, config.group_size),
+        config.dtype,
+        eps=torch.finfo(torch.float32).eps,
+        zero_point_dtype=torch.int32,
+        zero_point_domain=ZeroPointDomain.INT,
+        preserve_zero=True,
+        _layout=UintxLayout(dtype=config.dtype, pack_dim=config.pack_dim),
+    )
+    return _swap_weight(module, new_weight)
+
+
+# quantize_ runs this over every selected module before the first swap
+_uintx_weight_only_transform.precheck = _uintx_precheck
 
 
 # ---------------------------------------------------------------------------------------------
