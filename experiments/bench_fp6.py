@@ -6,6 +6,8 @@ and against the other weight-only GEMVs, in one process on one GPU:
                      (8-token launches; timed up to M = 32)
   {fmt}_gemv48       the GEMV with the 48-B lane chunk (the A/B behind fp6_host.h's default)
   {fmt}_dequant_mm   the same, forced onto the HIP dequantizer + F.linear (a bf16 temporary)
+  {fmt}_mfma         the same on the Fp6WO policy of gemm_mfma_kernel (tuning(fp6_mfma=1), the GEMV
+                     boundary moved down to one token; timed from M = 2)
   torch_dequant      the plain-torch dequantize (unpack the bit stream, table lookup, multiply) +
                      F.linear on the same device: what a user has without the kernels
   fp8wo, int8wo      torch.ops.torchao.fp8_weight_only_linear / int8_weight_only_linear
@@ -24,8 +26,12 @@ over rounds and the spread (max - min) / median are reported. Nothing here is a 
 One JSON line per (shape, M) to --out (default profiles/fp6_bench.jsonl).
 python experiments/bench_fp6.py [--out FILE] [--rounds N] [--shapes I,J] [--ms 1,16]
 
---boundary (default --ms 2,4,8,16,32): only fp6 on both forced routes and as routed: the
+--boundary (default --ms 2,4,8,16,32): only fp6 on the three forced routes and as routed: the
 measurement behind the route's boundary (profiles/fp6_bench_boundary.jsonl).
+--mfma (default --ms 2,4,8,16,32,128,512, no quantizer): the MFMA route of both formats against
+the forced GEMV and the forced dequantize + matmul of e3m2 and the float8 / int8 / int4 g32
+linears as routed (profiles/fp6_mfma_bench.jsonl; with --boundary,
+profiles/fp6_mfma_bench_boundary.jsonl).
 """
 
 import argparse
@@ -58,6 +64,8 @@ T = torch.ops.torchao
 FORMATS = {"e3m2": (3, 2), "e2m3": (2, 3)}
 MS = [1, 2, 4, 8, 16, 128]
 BOUNDARY_MS = [2, 4, 8, 16, 32]
+MFMA_MS = [2, 4, 8, 16, 32, 128, 512]
+MFMA_KNOBS = {"fp6": (0, 1, 0, 0, 0, 0), "fp6_mfma": 1}  # GEMV at one token only, MFMA above
 GEMV_MAX_M = 32
 ROTATE_BYTES = 1 << 29  # fp6 code bytes per rotation: twice the 256 MiB Infinity Cache
 
@@ -92,7 +100,7 @@ def time_quantizer(emit, rounds):
               "codes_equal": True, "device": torch.cuda.get_device_name(0)})
 
 
-def bench_shape(N, K, ms, rounds, emit, boundary=False):
+def bench_shape(N, K, ms, rounds, emit, boundary=False, mfma=False):
     dev = "cuda"
     gen = torch.Generator(device=dev).manual_seed(N * 7 + K)
     copies = max(3, -(-ROTATE_BYTES // (N * K * 3 // 4)))
@@ -116,11 +124,17 @@ def bench_shape(N, K, ms, rounds, emit, boundary=False):
             def lin(i, fmt=fmt, e=e, m=m):
                 return T.fp6_weight_only_linear(x, *f6[fmt][i], e, m, None)
 
-            paths[fmt], knobs[fmt] = lin, {}
+            if M >= 2:
+                paths[fmt + "_mfma"], knobs[fmt + "_mfma"] = lin, MFMA_KNOBS
+            if mfma and not boundary and fmt != "e3m2":
+                continue  # the other format differs by one instruction: its MFMA column only
+            if not mfma or boundary:
+                paths[fmt], knobs[fmt] = lin, {}
             paths[fmt + "_dequant_mm"], knobs[fmt + "_dequant_mm"] = lin, {"fp6": (2, 0, 0, 0, 0, 0)}
             if M <= GEMV_MAX_M:
                 paths[fmt + "_gemv"], knobs[fmt + "_gemv"] = lin, {"fp6": (1, 0, 0, 0, 0, 1)}
-                paths[fmt + "_gemv48"], knobs[fmt + "_gemv48"] = lin, {"fp6": (1, 0, 0, 0, 0, 2)}
+                if not mfma:
+                    paths[fmt + "_gemv48"], knobs[fmt + "_gemv48"] = lin, {"fp6": (1, 0, 0, 0, 0, 2)}
         if not boundary:
             def torch_dequant(i):
                 c, s = f6["e3m2"][i]
@@ -128,12 +142,12 @@ def bench_shape(N, K, ms, rounds, emit, boundary=False):
                                                              torch.bfloat16))
 
             paths.update({
-                "torch_dequant": torch_dequant,
+                **({} if mfma else {"torch_dequant": torch_dequant}),
                 "fp8wo": lambda i: T.fp8_weight_only_linear(x, *f8[i], None),
                 "int8wo": lambda i: T.int8_weight_only_linear(x, *i8[i], None),
                 "int4_g32": lambda i: T.int4_weight_only_linear(x, *i4[i], 32, None),
             })
-            knobs.update({"torch_dequant": {}, "fp8wo": {}, "int8wo": {}, "int4_g32": {}})
+            knobs.update({n: {} for n in paths if n not in knobs})
         kernel = {}  # the last project kernel of each path that launches one
         for name, fn in paths.items():
             with tuning(**knobs[name]):
@@ -162,19 +176,27 @@ def bench_shape(N, K, ms, rounds, emit, boundary=False):
             "device": torch.cuda.get_device_name(0),
         }
         for fmt in FORMATS:
+            if fmt + "_mfma" in med:
+                for other in (fmt + "_dequant_mm", fmt + "_gemv", "fp8wo"):
+                    if other in med:
+                        rec[f"{fmt}_mfma_over_{other.replace(fmt + '_', '')}"] = round(
+                            med[fmt + "_mfma"] / med[other], 4)
             if fmt + "_gemv" in med:
                 rec[fmt + "_gemv_over_dequant_mm"] = round(
                     med[fmt + "_gemv"] / med[fmt + "_dequant_mm"], 4)
-                rec[fmt + "_gemv48_over_gemv"] = round(med[fmt + "_gemv48"] / med[fmt + "_gemv"], 4)
+                if fmt + "_gemv48" in med:
+                    rec[fmt + "_gemv48_over_gemv"] = round(
+                        med[fmt + "_gemv48"] / med[fmt + "_gemv"], 4)
                 # bytes the GEMV must move: codes, one bf16 scale per row; x and y once
                 gb = (N * K * 0.75 + 2 * N + 2 * M * (N + K)) / 1e9
                 rec[fmt + "_gemv_gbytes_per_s"] = round(gb / (med[fmt + "_gemv"] * 1e-6), 1)
-            if not boundary:
+            if not boundary and not mfma:
                 rec[fmt + "_over_fp8wo"] = round(med[fmt] / med["fp8wo"], 4)
                 rec[fmt + "_over_int8wo"] = round(med[fmt] / med["int8wo"], 4)
                 rec[fmt + "_over_int4_g32"] = round(med[fmt] / med["int4_g32"], 4)
         if not boundary:
-            rec["torch_dequant_over_e3m2"] = round(med["torch_dequant"] / med["e3m2"], 3)
+            if not mfma:
+                rec["torch_dequant_over_e3m2"] = round(med["torch_dequant"] / med["e3m2"], 3)
             rec["fp8wo_gbytes_per_s"] = round(
                 (N * K + 4 * N + 2 * M * (N + K)) / 1e9 / (med["fp8wo"] * 1e-6), 1)
         emit(rec)
@@ -190,14 +212,18 @@ def main():
     ap.add_argument("--ms", default=None)
     ap.add_argument("--boundary", action="store_true",
                     help="time fp6_weight_only_linear on both forced routes at each M")
+    ap.add_argument("--mfma", action="store_true",
+                    help="the MFMA route against the forced routes and the other formats")
     ap.add_argument("--no-quantizer", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_fp6.py measures on the GPU; no device found")
     out = args.out or os.path.join(
-        ROOT, "profiles", "fp6_bench_boundary.jsonl" if args.boundary else "fp6_bench.jsonl")
+        ROOT, "profiles", ("fp6_mfma_bench" if args.mfma else "fp6_bench")
+        + ("_boundary.jsonl" if args.boundary else ".jsonl"))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    ms = [int(m) for m in args.ms.split(",")] if args.ms else (BOUNDARY_MS if args.boundary else MS)
+    ms = [int(m) for m in args.ms.split(",")] if args.ms else (
+        BOUNDARY_MS if args.boundary else MFMA_MS if args.mfma else MS)
     with open(out, "w") as f:
         def emit(rec):
             line = json.dumps(rec)
@@ -205,10 +231,10 @@ def main():
             f.write(line + "\n")
             f.flush()
 
-        if not args.boundary and not args.no_quantizer:
+        if not args.boundary and not args.mfma and not args.no_quantizer:
             time_quantizer(emit, args.rounds)
         for i in (int(v) for v in args.shapes.split(",") if v != ""):
-            bench_shape(*SHAPES[i], ms, args.rounds, emit, args.boundary)
+            bench_shape(*SHAPES[i], ms, args.rounds, emit, args.boundary, args.mfma)
 
 
 if __name__ == "__main__":

@@ -222,13 +222,20 @@ int tao_tune_nf4(int route, int max_gemv_m, int rows_per_wave, int waves_k, int 
 /* The route torchao::fp6_weight_only_linear takes for this call under the calling thread's
  * tao_tune_fp6: 1 = the GEMV, tao_fp6_linear_bf16 (up to the built-in boundary M of
  * csrc/fp6_host.h); 2 = tao_fp6_dequant_bf16 into a temporary and the bf16 matmul, which needs an
- * allocator and lives in the op (csrc/torch_ops.cpp). */
+ * allocator and lives in the op (csrc/torch_ops.cpp); 3 = the MFMA GEMM, tao_fp6_linear_bf16 too
+ * (only under tao_tune_fp6_mfma). */
 int tao_fp6_linear_route(int64_t M, int64_t N, int64_t K);
 /* Route and launch shape of the FP6 linear (calling thread only; tests and A/B runs): the first
  * five arguments as tao_tune_nf4's; chunk_groups = 32-code groups per lane chunk of the GEMV:
  * 0 = built-in, 1 = 24 B (a 2048-code wave slice), 2 = 48 B (a 4096-code wave slice). */
 int tao_tune_fp6(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups,
                  int chunk_groups);
+/* The MFMA route of the FP6 linear (the Fp6WO policy of gemm_mfma_kernel, reading the 6-bit
+ * storage in place): 0 = built-in route, 1 = every call the rule would send to dequantize + matmul
+ * runs on the MFMA GEMM inside tao_fp6_linear_bf16 instead, and tao_fp6_linear_route returns 3
+ * where it returned 2. A route forced through tao_tune_fp6 (1 or 2) still wins, and its max_gemv_m
+ * still moves the GEMV boundary. Calling thread only. */
+int tao_tune_fp6_mfma(int on);
 /* Rows per tile (16, 32 or 64) of tao_int4wo_grouped_linear_bf16 for R sorted rows over E experts,
  * and whether the expert FFN runs gate and up in one launch (1) or two (0), under the calling
  * thread's tao_tune_moe (rules: csrc/moe_host.h). */

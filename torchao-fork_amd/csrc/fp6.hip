@@ -15,8 +15,11 @@
 // is the measured default, fp6_host.h): one
 // v_cvt_scalef32_pk32_bf16_{bf6,fp6} per group with scale 1.0 (exact: every fp6 value is a bf16
 // number), then 16 v_dot2_f32_bf16 against x as loaded; the row scale meets the fp32 total once.
+// MFMA GEMM: the Fp6WO policy of gemm_mfma_kernel (gemm_mfma_policy.h) on the same storage and the
+// same epilogue, reached through tao_tune_fp6_mfma until the route rule names it.
 #include "fp6_codec.h"
 #include "fp6_host.h"
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 namespace tao {
@@ -310,7 +313,8 @@ extern "C" int tao_fp6_dequant_bf16(const uint32_t* codes, const uint16_t* scale
 }
 
 extern "C" int tao_fp6_linear_route(int64_t M, int64_t N, int64_t K) {
-  return tao::fp6_route(M, N, K, tao::tuning().fp6_route, tao::tuning().fp6_max_m);
+  return tao::fp6_route(M, N, K, tao::tuning().fp6_route, tao::tuning().fp6_max_m,
+                        tao::tuning().fp6_mfma);
 }
 
 extern "C" int tao_fp6_linear_bf16(const uint16_t* x, const uint32_t* codes, const uint16_t* scale,
@@ -332,6 +336,9 @@ extern "C" int tao_fp6_linear_bf16(const uint16_t* x, const uint32_t* codes, con
   const Tuning& tu = tuning();
   const int fmt = fp6_format_of(ebits, mbits);
   const int grp = fp6_chunk_groups(tu.fp6_groups);
+  // the Fp6WO policy of gemm_mfma_kernel where the rule names it (tao_tune_fp6_mfma)
+  if (fp6_route(M, N, K, tu.fp6_route, tu.fp6_max_m, tu.fp6_mfma) == kFp6RouteMfma)
+    return fp6_mm_launch(x, codes, scale, bias, y, (int)M, (int)N, (int)K, fmt, st);
   // 8-token pieces: one launch wherever the route rule chose the GEMV, a sequence of them where
   // a caller forces it beyond (or calls this entry on a shape the op would dequantize)
   for (int64_t m0 = 0; m0 < M; m0 += kFp6GemvMaxM) {
@@ -371,5 +378,11 @@ extern "C" int tao_tune_fp6(int route, int max_gemv_m, int rows_per_wave, int wa
   tu.fp6_wk = waves_k;
   tu.fp6_g = row_groups;
   tu.fp6_groups = chunk_groups;
+  return TAO_OK;
+}
+
+extern "C" int tao_tune_fp6_mfma(int on) {
+  TAO_CHECK_ARG(on == 0 || on == 1, "tune: fp6 mfma must be 0 (built-in route) or 1");
+  tao::tuning().fp6_mfma = on;
   return TAO_OK;
 }

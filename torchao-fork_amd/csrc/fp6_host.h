@@ -18,13 +18,13 @@ static inline int fp6_format_of(int64_t ebits, int64_t mbits) {
 // dwords of native storage per row of K codes (K % 32 == 0): K * 6 / 32
 static inline int64_t fp6_row_dwords(int64_t K) { return K / 32 * 6; }
 
-enum { kFp6RouteAuto = 0, kFp6RouteGemv = 1, kFp6RouteDequantMm = 2 };
+enum { kFp6RouteAuto = 0, kFp6RouteGemv = 1, kFp6RouteDequantMm = 2, kFp6RouteMfma = 3 };
 
 // The most tokens one GEMV launch serves (fp6wo_gemv_kernel<*, 8, 1, *>); a forced GEMV beyond it
 // is a sequence of launches over 8-token pieces.
 constexpr int kFp6GemvMaxM = 8;
 
-// Two routes: the decode GEMV, and the dequantizer into a temporary + the bf16 matmul. force:
+// Two built-in routes: the decode GEMV, and the dequantizer into a temporary + the bf16 matmul. force:
 // tao_tune_fp6's route (kFp6Route*); max_gemv_m > 0 moves the boundary (tao_tune_fp6 too).
 // The built-in boundary is measured (experiments/bench_fp6.py --boundary,
 // profiles/fp6_bench_boundary.jsonl, both routes forced, e3m2; e2m3 is within 1 %; us GEMV vs
@@ -32,13 +32,19 @@ constexpr int kFp6GemvMaxM = 8;
 // 8-token instance wins at all four shapes (22.9 vs 42.9, 33.3 vs 53.5, 74.0 vs 120.4, 87.8 vs
 // 113.6); at M = 16, two 8-token launches, it loses at all four (45.8 vs 42.9, 66.6 vs 52.6,
 // 148.2 vs 119.7, 175.7 vs 114.5). N and K do not enter: the rule is M <= 8, one launch.
+// A third route, the Fp6WO policy of gemm_mfma_kernel (gemm_mfma.hip), is behind a hook of its
+// own (mfma: tao_tune_fp6_mfma): with it on, every call this rule would send to dequantize +
+// matmul goes to the MFMA GEMM instead. A forced route still wins, and max_gemv_m still moves the
+// GEMV boundary. The built-in rule does not name it yet (measurements: DESIGN §4.20).
 constexpr int kFp6GemvDefaultM = 8;
-static inline int fp6_route(int64_t M, int64_t N, int64_t K, int force, int max_gemv_m) {
+static inline int fp6_route(int64_t M, int64_t N, int64_t K, int force, int max_gemv_m,
+                            int mfma = 0) {
   (void)N;
   (void)K;
   if (force == kFp6RouteGemv || force == kFp6RouteDequantMm) return force;
   const int64_t lim = max_gemv_m > 0 ? max_gemv_m : kFp6GemvDefaultM;
-  return M <= lim ? kFp6RouteGemv : kFp6RouteDequantMm;
+  if (M <= lim) return kFp6RouteGemv;
+  return mfma ? kFp6RouteMfma : kFp6RouteDequantMm;
 }
 
 // Tokens per lane set (MT) and rows per wave (RPW) of the GEMV launch that serves m <= 8 tokens:

@@ -1,9 +1,11 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// nine weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
+// ten weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
 //   Int4WO  : bf16 x, int4 group-quant W (gfx950 row-stream layout), v_mfma_f32_16x16x32_bf16
 //   Int8WO  : bf16 x, int8 per-channel W,                            v_mfma_f32_16x16x32_bf16
 //   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
+//   Fp6WO   : bf16 x, OCP FP6 (e3m2 / e2m3) per-channel W read from its 6-bit stream, decoded by
+//             v_cvt_scalef32_pk32_bf16_{bf6,fp6},                    v_mfma_f32_16x16x32_bf16
 //   Int8Dyn : int8 x (per-token scale), int8 W (per-channel scale),   v_mfma_i32_16x16x64_i8
 //   Int8DynW4: int8 x (per-token fp32 scale), int4 W two per byte (per-channel fp32 scale),
 //             expanded to int8 x 16 in registers,                    v_mfma_i32_16x16x64_i8
@@ -583,7 +585,7 @@ template <int BM, int KG, int NW, class P>
 void launch_one(dim3 grid, hipStream_t stream, const uint8_t* xb, const P& pol,
                 const uint16_t* bias, uint16_t* y, int M, int N, int K, int sps,
                 typename P::Acc* slab, unsigned* cnt) {
-  if constexpr (BM <= P::kMaxBM && KG <= P::kMaxKG) {
+  if constexpr (BM <= P::kMaxBM && KG <= P::kMaxKG && P::fits(BM, KG, NW)) {
     // ring depth: 4 steps, 3 where the per-stage registers grow (int8-dyn's 64-B pieces,
     // int4's 512-B x rows), 2 at BM >= 64
     constexpr bool big = sizeof(typename P::Chunk) > 32 || P::kABytes * P::kKStep > 256;
@@ -679,6 +681,35 @@ int gshift_of(int64_t g) {
 
 }  // namespace
 
+// The Fp6WO instances are built from this file a second time, as an object of their own
+// (TAO_GEMM_FP6_TU, Makefile) compiled without the packed fp32 instructions; that object holds
+// fp6_mm_launch and nothing else, this one everything else. The existing instances keep the
+// flags, and so the instructions, they were measured with.
+#ifdef TAO_GEMM_FP6_TU
+// FP6 weight-only (fp6.hip): the calls its route rule gives to the MFMA route (fp6_host.h)
+int fp6_mm_launch(const uint16_t* x, const uint32_t* codes, const uint16_t* scale,
+                  const uint16_t* bias, uint16_t* y, int M, int N, int K, int fmt,
+                  hipStream_t stream) {
+  // one buffer descriptor per operand, 32-bit byte counts and offsets (a lane's offset runs up
+  // to one step past the end of the codes before the range check drops it)
+  constexpr int64_t kMaxBytes = (1LL << 32) - 4096;
+  TAO_CHECK_ARG((int64_t)N * (K / 32 * 24) <= kMaxBytes && (int64_t)M * K * 2 <= kMaxBytes,
+                "fp6 linear (MFMA route): codes (N x K = %d x %d) and x (M = %d) must each be "
+                "below 4 GiB", N, K, M);
+  if (fmt == 0) {
+    Fp6WO<0> pol;
+    pol.w = codes;
+    pol.scale = scale;
+    return launch_gemm(x, pol, bias, y, M, N, K, stream);
+  }
+  Fp6WO<1> pol;
+  pol.w = codes;
+  pol.scale = scale;
+  return launch_gemm(x, pol, bias, y, M, N, K, stream);
+}
+
+}  // namespace tao
+#else
 // the skinny-M crossover, for the single-fetch partials entry (gemm_sf.hip), which serves only
 // shapes the plain linear runs on the single-fetch kernel
 bool int4_linear_takes_gemv(int64_t M, int64_t N, int64_t K) { return use_gemv(M, N, K); }
@@ -924,3 +955,4 @@ extern "C" int tao_tune_gemm(int m_tile, int k_groups, int splits) {
   tao::tuning().splits = splits;
   return TAO_OK;
 }
+#endif  // TAO_GEMM_FP6_TU

@@ -19,6 +19,7 @@
 // "equivalent" spelling is not a substitute for the one that is there.
 #pragma once
 
+#include "fp6_codec.h"
 #include "tao_mfma.h"
 
 namespace tao {
@@ -45,6 +46,8 @@ struct PolicyDefaults {
   static __device__ __forceinline__ Acc mfma(const uint4& a, const bf16x8_t& b, Acc c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), b, c, 0, 0, 0);
   }
+  // whether the instance (BM, KG, NW) is built: its one LDS array must fit (Fp6WO overrides)
+  static constexpr bool fits(int, int, int) { return true; }
   static constexpr bool kRowF = false, kColF = false;  // no per-row / per-column factor
   __device__ __forceinline__ const uint16_t* row_factor() const { return nullptr; }
   __device__ __forceinline__ const uint16_t* col_factor() const { return nullptr; }
@@ -305,6 +308,130 @@ struct Fp8WO : ByteWeights<128> {
   // the fp32 sum times the fp32 scale, rounded once (include/torchao_mi355x.h)
   static constexpr bool kColF = true;
   __device__ __forceinline__ const float* col_factor() const { return scale; }
+  __device__ __forceinline__ float epi(float acc, float, float sc) const {
+    return round_bf16(acc * sc);
+  }
+};
+
+// Fp6WO<FMT>: bf16 x, OCP FP6 W (FMT 0 = e3m2, 1 = e2m3; fp6_codec.h) read in place from native
+// storage, int32 [N][K * 6 / 32]: code k at bits 6 k .. 6 k + 5 of the row's bit stream, a 32-code
+// group = 24 B = one operand of v_cvt_scalef32_pk32_bf16_{bf6,fp6}. One bf16 scale per row, met
+// once in the epilogue. Int4WO's step, x image and k order: 256 k per step = 192 B = 8 groups per
+// row; lane (n, kq) owns groups kq and 4 + kq; the conversion puts stream position p in result
+// element p, so the 16 result dwords of a group are four B fragments of 8 consecutive k, dwords
+// 4 t .. 4 t + 3 for MFMA s = 4 h + t of group 4 h + kq: x slot 4 (4 h + kq) + t.
+//  * Intake: a wave's 16 rows x 192 B are 192 16-B pieces, three loads per lane; load i of lane l
+//    takes piece p = 64 i + l, i.e. piece p % 12 of row p / 12, so consecutive lanes read
+//    consecutive 16 B and each load instruction covers 5 1/3 whole row segments (1 KiB in at most
+//    six runs). K % 64 == 0 makes a row a multiple of 48 B: every piece is 16-B aligned. Rows past N
+//    are clamped per piece. The step's byte offset rides in the VGPR offset, not in the scalar one:
+//    the descriptor's range check covers the vector offset only, and a K tail of the last row must
+//    read 0 rather than the bytes behind the buffer. (Three v_add_u32 per step and column block.)
+//  * Regroup: per-wave LDS stage of 16 rows at a pitch of 208 B (3328 B, 208 uint4), row-major.
+//    Write: piece (r, c) at byte 208 r + 16 c, one ds_write_b128 per load; its 16-B granule index
+//    mod 16 is 13 r + c = p + p / 12 (mod 16), so any 16 lanes of consecutive p collide only where
+//    their window crosses a row end: one or two granules hit twice, 2-way at worst. Read: a group
+//    starts at byte 24 kq + 96 h of the row, 8-B but not 16-B aligned, so lane (n, kq) reads its
+//    two groups as 3 + 3 ds_read_b64 at 8-B granule 26 n + 12 h + 3 kq + q. Mod 32 (64 banks x 4 B
+//    = 32 granules) 26 n runs over the 16 even residues, so for the lanes of one half-wave (kq 0, 1
+//    or 2, 3) the 16 rows of the even kq take the residues of one parity and those of the odd kq
+//    (3 more) the other: 32 distinct granules, conflict-free. Over all 64 lanes every residue is hit
+//    exactly twice, so any other split of the wave into passes is 2-way at worst.
+//  * Decode: one conversion with scale 1.0 per group, exact (every fp6 value is a bf16 number). The
+//    six raw dwords of both groups are kept (12 VGPRs per column block) and frag() converts a
+//    group where its four MFMAs come up (one conversion: the four calls are one expression).
+//    Converting both groups in prep() instead gives the same VGPR count in every instance and no
+//    scratch either (the scheduler moves the conversions to their MFMAs in both spellings), so the
+//    smaller Prep stands.
+//  * The instances are compiled in a translation unit of their own, without the packed fp32
+//    instructions (Makefile, gemm_mfma.hip TAO_GEMM_FP6_TU).
+//  * Tails: no code is NaN or inf, so past K the next row's codes (or 0 past the buffer) meet x that
+//    the LDS store zeroes and add exactly 0: no mask_tail.
+//  * LDS: x tiles KG x 2 x BM x 512 B, stages KG x 4 x NW x 3328 B; fits() drops the one instance
+//    past 160 KiB, (BM, KG, NW) = (64, 2, 2), which no launch shape names (KG x BM <= 64). Four
+//    k-groups (1024 threads, 128 VGPRs) spill, so kMaxKG = 2.
+template <int FMT>
+struct Fp6WO : PolicyDefaults {
+  static constexpr int kPathId = 9;  // no measured table entries: the heuristic shapes
+  static constexpr int kABytes = 2;  // bf16 x
+  static constexpr int kKStep = 256;
+  static constexpr int kMfma = 8;
+  static constexpr int kMaxBM = 64;  // 512-B x rows, as Int4WO
+  static constexpr int kPrefKG = 2;
+  static constexpr int kMaxKG = 2;  // four k-groups (128 VGPRs per lane) spill 24 B to scratch
+  static constexpr int kMinSlice = 4;
+  static constexpr int kRowB = 192;                 // code bytes per row and step
+  static constexpr int kPitch = 208;                // stage row pitch, bytes
+  static constexpr int kStage = 16 * kPitch / 16;   // uint4 per wave
+  static constexpr bool fits(int bm, int kg, int nw) {
+    return (kg * 2 * bm * 32 + kg * 4 * nw * kStage) * 16 <= 160 * 1024;
+  }
+  const uint32_t* w;      // [N][K * 6 / 32]
+  const uint16_t* scale;  // [N] bf16
+  typedef uint32_t StageRead __attribute__((ext_vector_type(2), may_alias));
+  struct Lane {
+    Rsrc w;
+    uint32_t wv[3];
+  };
+  struct Chunk {
+    uint4 v[3];  // pieces 64 i + lane of the wave's 192
+  };
+  struct Prep {
+    u32x6_t g[2];  // groups kq and 4 + kq of row n, as stored
+  };
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    const uint32_t rb = (uint32_t)(K >> 5) * 24u;  // bytes per row
+    const int base = bn - (lane & 15);             // the wave's first row
+    Lane L;
+    L.w = make_rsrc(w, (uint32_t)N * rb);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int p = 64 * i + lane, r = base + p / 12;
+      L.wv[i] = (uint32_t)(r < N ? r : N - 1) * rb + 16 * (p % 12);
+    }
+    return L;
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    Chunk ch;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ch.v[i] = bload16<kNT>(L.w, L.wv[i] + st * kRowB, 0);
+    return ch;
+  }
+  static __device__ __forceinline__ u32x16_t decode(const u32x6_t& g) {
+    if constexpr (FMT == 0)
+      return __builtin_bit_cast(u32x16_t, __builtin_amdgcn_cvt_scalef32_pk32_bf16_bf6(g, 1.0f));
+    else
+      return __builtin_bit_cast(u32x16_t, __builtin_amdgcn_cvt_scalef32_pk32_bf16_fp6(g, 1.0f));
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int p = 64 * i + lane;
+      stage[(p / 12) * (kPitch / 16) + p % 12] = ch.v[i];
+    }
+    const int n = lane & 15, kq = lane >> 4;
+    const StageRead* rd = reinterpret_cast<const StageRead*>(stage) + n * (kPitch / 8) + 3 * kq;
+    Prep p;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const StageRead a = rd[12 * h], b = rd[12 * h + 1], c = rd[12 * h + 2];
+      p.g[h] = u32x6_t{a[0], a[1], b[0], b[1], c[0], c[1]};
+    }
+    return p;
+  }
+  // B fragment of MFMA s = 4 h + t: result dwords 4 t .. 4 t + 3 of group 4 h + kq (the four calls
+  // of one h share one conversion)
+  __device__ __forceinline__ bf16x8_t frag(const Prep& p, int s) const {
+    const int t = s & 3;
+    const u32x16_t d = decode(p.g[s >> 2]);
+    return as_bf16x8(d[4 * t], d[4 * t + 1], d[4 * t + 2], d[4 * t + 3]);
+  }
+  static __device__ __forceinline__ int slot(int s, int kq) { return Int4WO::slot(s, kq); }
+  static __device__ __forceinline__ int xswz(int row) { return Int4WO::xswz(row); }
+  // the GEMV's formula (fp6.hip): bf16(fp32(acc * s)); the bias add and its rounding follow in
+  // the kernel
+  static constexpr bool kColF = true;
+  __device__ __forceinline__ const uint16_t* col_factor() const { return scale; }
   __device__ __forceinline__ float epi(float acc, float, float sc) const {
     return round_bf16(acc * sc);
   }

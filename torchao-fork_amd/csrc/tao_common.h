@@ -89,6 +89,7 @@ struct Tuning {
   int fp6_route = 0, fp6_max_m = 0;              // FP6 linear route and GEMV boundary (tao_tune_fp6)
   int fp6_rpw = 0, fp6_wk = 0, fp6_g = 0;        // FP6 GEMV launch shape (tao_tune_fp6)
   int fp6_groups = 0;                            // FP6 GEMV 32-code groups per lane chunk
+  int fp6_mfma = 0;                              // FP6 linear: 1 = MFMA GEMM where the rule says dequant + mm
   int uintx_route = 0, uintx_max_m = 0;          // uintx linear route and GEMV boundary (tao_tune_uintx)
   int uintx_rpw = 0, uintx_wk = 0, uintx_g = 0;  // uintx GEMV launch shape (tao_tune_uintx)
   int uintx_xlds = 0;                            // uintx GEMV x: 0 built-in, 1 through L1, 2 staged in LDS

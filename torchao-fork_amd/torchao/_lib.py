@@ -101,6 +101,7 @@ _SIGNATURES = {
     "tao_fp6_linear_bf16": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p],
     "tao_fp6_linear_route": [_i64, _i64, _i64],
     "tao_tune_fp6": [_int, _int, _int, _int, _int, _int],
+    "tao_tune_fp6_mfma": [_int],
     "tao_uintx_dequant_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _int, _int, _p],
     "tao_uintx_linear_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p],
     "tao_uintx_linear_route": [_i64, _i64, _i64, _int],

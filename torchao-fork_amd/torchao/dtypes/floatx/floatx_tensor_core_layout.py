@@ -21,7 +21,8 @@ unflattened (the int4 precedent: uintx/tensor_core_tiled_layout.py);
 functions, on any device.
 
 Linear. bf16 activations on the GPU run ``torch.ops.torchao.fp6_weight_only_linear`` (csrc/fp6.hip:
-the decode GEMV up to the boundary of csrc/fp6_host.h, the HIP dequantizer + bf16 matmul above);
+the decode GEMV up to the boundary of csrc/fp6_host.h, the HIP dequantizer + bf16 matmul above, or,
+under ``torchao.kernel.tuning.tuning(fp6_mfma=1)``, the MFMA GEMM on the same storage above);
 on the CPU the linear is ``F.linear(x, W.dequantize(), bias)`` (the reference raises there: its
 kernel is CUDA only). Other activation dtypes take the dispatch table's dequantize fallback.
 Only the two FP6 formats are served; the reference's fp5 forms (e2m2, e3m1) raise.

@@ -48,6 +48,8 @@ _KNOBS = {
     # (route, max_gemv_m, rows per wave, waves along K, row groups as for nf4; 32-code groups per
     # lane chunk: 0 built-in, 1 = 24 B, 2 = 48 B)
     "fp6": ("tao_tune_fp6", 6),
+    # 1: the MFMA GEMM wherever the fp6 route rule says dequantize + matmul
+    "fp6_mfma": ("tao_tune_fp6_mfma", 1),
     # (route, max_gemv_m, rows per wave, waves along K, row groups as for nf4; bytes of each shard
     # piece per lane unit: 0 built-in, 4, 8, 16; x of the 4- / 8-token tiles: 0 built-in, 1 through
     # L1, 2 staged in LDS)
