@@ -25,6 +25,11 @@ python experiments/bench_uintx.py [--out FILE] [--rounds N] [--shapes I,J] [--ms
 
 --boundary (default --ms 4,8,12,16): only the routed linear and both forced routes: the
 measurement behind the route's boundary (profiles/uintx_bench_boundary.jsonl).
+
+--mfma (default --ms 2,4,8,16,32,64,128,256,512; profiles/uintx_mfma_bench.jsonl): the MFMA route
+(tuning(uintx_mfma=1), with the GEMV boundary moved to one token so that it runs at every M > 1)
+against the forced GEMV (M <= 32), the forced dequantize + matmul, int4 g64 and int8 weight-only
+(these two once per shape and M, with the first width).
 """
 
 import argparse
@@ -62,7 +67,7 @@ def uintx_weights(bits, N, K, gen):
     return (*shards, scale, zp, bits, G)
 
 
-def bench_shape(bits, N, K, ms, rounds, emit, boundary, torch_bits, others):
+def bench_shape(bits, N, K, ms, rounds, emit, boundary, torch_bits, others, mfma=False):
     gen = torch.Generator(device="cuda").manual_seed(N * 7 + K + bits)
     wbytes = N * K * bits // 8 + N * (K // G) * 6
     ux = [uintx_weights(bits, N, K, gen) for _ in range(ncopies(wbytes))]
@@ -77,7 +82,14 @@ def bench_shape(bits, N, K, ms, rounds, emit, boundary, torch_bits, others):
                  "dequant_mm": (lin, len(ux), {"uintx": (2, 0, 0, 0, 0, 0, 0)})}
         if M <= 32:
             paths["gemv"] = (lin, len(ux), {"uintx": (1, 0, 0, 0, 0, 0, 0)})
-        if not boundary:
+        if mfma:
+            del paths["uintx"]
+            paths["mfma"] = (lin, len(ux), {"uintx": (0, 1, 0, 0, 0, 0, 0), "uintx_mfma": 1})
+        if mfma and others is not None:
+            i4, i8 = others
+            paths["int4_g64"] = (lambda i: T.int4_weight_only_linear(x, *i4[i], G, None), len(i4), {})
+            paths["int8wo"] = (lambda i: T.int8_weight_only_linear(x, *i8[i], None), len(i8), {})
+        if not boundary and not mfma:
             if M <= 8:
                 for u in (4, 8, 16):
                     paths[f"gemv_u{u}"] = (lin, len(ux), {"uintx": (1, 0, 0, 0, 0, u, 0)})
@@ -119,6 +131,10 @@ def bench_shape(bits, N, K, ms, rounds, emit, boundary, torch_bits, others):
                 rec[n + "_gbytes_per_s"] = round(gb / (med[n] * 1e-6), 1)
         if "gemv" in med:
             rec["gemv_over_dequant_mm"] = round(med["gemv"] / med["dequant_mm"], 4)
+        if "mfma" in med:
+            rec["dequant_mm_over_mfma"] = round(med["dequant_mm"] / med["mfma"], 3)
+            if "gemv" in med:
+                rec["gemv_over_mfma"] = round(med["gemv"] / med["mfma"], 3)
         emit(rec)
         del graphs
         torch.cuda.empty_cache()
@@ -146,14 +162,18 @@ def main():
     ap.add_argument("--torch-bits", default="3")
     ap.add_argument("--boundary", action="store_true",
                     help="time the linear on both forced routes at each M")
+    ap.add_argument("--mfma", action="store_true",
+                    help="time the MFMA route against both forced routes, int4 g64 and int8")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_uintx.py measures on the GPU; no device found")
     out = args.out or os.path.join(
-        ROOT, "profiles", "uintx_bench_boundary.jsonl" if args.boundary else "uintx_bench.jsonl")
+        ROOT, "profiles", "uintx_mfma_bench.jsonl" if args.mfma else
+        "uintx_bench_boundary.jsonl" if args.boundary else "uintx_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    ms = [int(m) for m in args.ms.split(",")] if args.ms else ([4, 8, 12, 16] if args.boundary
-                                                              else [1, 2, 4, 8])
+    ms = [int(m) for m in args.ms.split(",")] if args.ms else (
+        [2, 4, 8, 16, 32, 64, 128, 256, 512] if args.mfma else [4, 8, 12, 16] if args.boundary
+        else [1, 2, 4, 8])
     torch_bits = {int(b) for b in args.torch_bits.split(",") if b}
     with open(out, "w") as f:
         def emit(rec):
@@ -166,7 +186,10 @@ def main():
             N, K = SHAPES[i]
             others = None if args.boundary else other_weights(N, K)
             for bits in (int(b) for b in args.bits.split(",")):
-                bench_shape(bits, N, K, ms, args.rounds, emit, args.boundary, torch_bits, others)
+                bench_shape(bits, N, K, ms, args.rounds, emit, args.boundary, torch_bits, others,
+                            args.mfma)
+                if args.mfma:
+                    others = None  # int4 / int8 do not depend on the width: once per shape
 
 
 if __name__ == "__main__":

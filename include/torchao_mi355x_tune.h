@@ -247,8 +247,18 @@ int tao_tune_moe(int bm, int dual);
 /* The route torchao::uintx_weight_only_linear takes for this call under the calling thread's
  * tao_tune_uintx: 1 = the GEMV, tao_uintx_linear_bf16 (up to the built-in boundary M of
  * csrc/uintx_host.h for this bit width); 2 = tao_uintx_dequant_bf16 into a temporary and the bf16
- * matmul, which needs an allocator and lives in the op (csrc/torch_ops.cpp). */
+ * matmul, which needs an allocator and lives in the op (csrc/torch_ops.cpp); 3 = the MFMA GEMM,
+ * tao_uintx_linear_bf16 too (only under tao_tune_uintx_mfma, and only where the kernel serves K and
+ * group_size: csrc/uintx_host.h uintx_mfma_ok). The _g form is the op's rule; the form without a
+ * group size answers for a group size the MFMA GEMM serves (a multiple of 32). */
 int tao_uintx_linear_route(int64_t M, int64_t N, int64_t K, int bits);
+int tao_uintx_linear_route_g(int64_t M, int64_t N, int64_t K, int bits, int group_size);
+/* The MFMA route of the uintx linear (the UintxWO policy of gemm_mfma_kernel, reading the shards
+ * in place): 0 = built-in route, 1 = every call the rule would send to dequantize + matmul, and
+ * that the kernel serves, runs on the MFMA GEMM inside tao_uintx_linear_bf16 instead, and
+ * tao_uintx_linear_route(_g) returns 3 where it returned 2. A route forced through tao_tune_uintx
+ * (1 or 2) still wins, and its max_gemv_m still moves the GEMV boundary. Calling thread only. */
+int tao_tune_uintx_mfma(int on);
 /* Bytes of each shard piece per lane unit (4, 8 or 16) of the GEMV launch that serves M tokens
  * (its first 8-token piece) under the calling thread's tao_tune_uintx: the built-in rule of
  * csrc/uintx_host.h on (K, bits, M), or the forced unit, capped at 8 for 8 rows per wave. */

@@ -1,6 +1,9 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// ten weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
+// eleven weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
+//   UintxWO : bf16 x, 1- to 7-bit group-quant W read from its bit-sliced shards, x gathered in the
+//             shards' segment order, per-group scale and zero point applied to each MFMA's fp32
+//             product,                                               v_mfma_f32_16x16x32_bf16
 //   Int4WO  : bf16 x, int4 group-quant W (gfx950 row-stream layout), v_mfma_f32_16x16x32_bf16
 //   Int8WO  : bf16 x, int8 per-channel W,                            v_mfma_f32_16x16x32_bf16
 //   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
@@ -39,6 +42,7 @@
 #include "fp8_dyn_host.h"
 #include "gemm_mfma_policy.h"
 #include "tao_gemm.h"
+#include "uintx_host.h"
 
 // Experiment switch: ring depth override (experiments/gemm_depth.sh; 0 = launch_one's rule).
 #ifndef TAO_GEMM_DEPTH
@@ -94,7 +98,8 @@ __device__ __forceinline__ int x_slot(int row, int slot) {
 // registers per lane (256 threads) hipcc puts MFMA results into AGPRs and copies each one out with
 // a v_accvgpr_read; asked to leave room for two waves per SIMD (256 registers, which these
 // instances fit without scratch) it writes them to VGPRs. 0: no attribute (every other policy).
-#define TAO_GEMM_WPE_ATTR __attribute__((amdgpu_waves_per_eu(P::kBlockF32 ? 2 : 0)))
+#define TAO_GEMM_WPE_ATTR \
+  __attribute__((amdgpu_waves_per_eu((P::kBlockF32 || P::kGroupF32) ? 2 : 0)))
 #endif
 template <int BM, int D, int KG, int NW, class P>
 __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
@@ -158,6 +163,9 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
   for (int i = 0; i < XLOADS; ++i) {
     const int gm = m_blk + row0 + RPP * i;
     xv[i] = (uint32_t)(gm < M ? gm : M - 1) * (uint32_t)row_bytes + xslot_b;
+    // (kXGather) the slot's piece of the row instead: eight strided pieces per step
+    if constexpr (P::kXGather)
+      xv[i] = (uint32_t)(gm < M ? gm : M - 1) * (uint32_t)row_bytes + P::xoff(xslot, K);
     xlds[i] = x_slot<SLOTS, P>(row0 + RPP * i, xslot);
   }
   const bool ragged = (row_bytes % XSB) != 0;
@@ -203,7 +211,12 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
     const int st0 = abs_step(j);
     const int st = st0 < s1 ? st0 : s1 - 1;
 #pragma unroll
-    for (int i = 0; i < XLOADS; ++i) xdst[i] = bload16(xrs, xv[i], st * XSB);
+    for (int i = 0; i < XLOADS; ++i) {
+      if constexpr (P::kXGather)
+        xdst[i] = bload16(xrs, xv[i], st * P::kXStepB);
+      else
+        xdst[i] = bload16(xrs, xv[i], st * XSB);
+    }
     if constexpr (kBSA) {
       const uint2 v = *reinterpret_cast<const uint2*>(xsrow[0] + st * 8);
       sdst[0] = v.x;
@@ -223,7 +236,12 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
   auto store_x = [&](const uint4 (&src)[XLOADS], int j) __attribute__((always_inline)) {
     const int st = abs_step(j);
     uint4* dst = xs + (j & 1) * TILE;
-    if constexpr (P::kXPerm) {
+    if constexpr (P::kXGather) {
+      // a piece outside its segment (P::xin) or of an inactive step -> 0
+      const uint32_t keep = st < s1 && P::xin(xslot, st, K) ? ~0u : 0u;
+#pragma unroll
+      for (int i = 0; i < XLOADS; ++i) dst[xlds[i]] = and16(src[i], keep);
+    } else if constexpr (P::kXPerm) {
       // (Int8DynW4) each piece's bytes in the B fragment's k order; the tail mask as below
       const uint32_t keep = st < s1 && st * XSB + xslot_b < row_bytes ? ~0u : 0u;
 #pragma unroll
@@ -328,8 +346,18 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
             const int row = t * 16 + (lane & 15);
             // one A fragment read from LDS feeds the wave's NW column blocks
             const uint4 a = xb[x_slot<SLOTS, P>(row, slot)];
+            if constexpr (P::kGroupF32) {
+              // the MFMA's k lie in one group: its product and the rows' sums of the same x (an
+              // MFMA against ones) meet the group's scale and zero point in fp32
+              const Acc sx = P::mfma(a, P::ones(), Acc{0, 0, 0, 0});
 #pragma unroll
-            for (int c = 0; c < NW; ++c) acc[t * NW + c] = P::mfma(a, bfrag[c], acc[t * NW + c]);
+              for (int c = 0; c < NW; ++c)
+                acc[t * NW + c] = P::group_acc(P::mfma(a, bfrag[c], Acc{0, 0, 0, 0}), sx, pw[c], s,
+                                               acc[t * NW + c]);
+            } else {
+#pragma unroll
+              for (int c = 0; c < NW; ++c) acc[t * NW + c] = P::mfma(a, bfrag[c], acc[t * NW + c]);
+            }
           }
         }
       }
@@ -589,8 +617,10 @@ void launch_one(dim3 grid, hipStream_t stream, const uint8_t* xb, const P& pol,
     // ring depth: 4 steps, 3 where the per-stage registers grow (int8-dyn's 64-B pieces,
     // int4's 512-B x rows), 2 at BM >= 64
     constexpr bool big = sizeof(typename P::Chunk) > 32 || P::kABytes * P::kKStep > 256;
-    constexpr int D = TAO_GEMM_DEPTH > 0 ? TAO_GEMM_DEPTH
-                                         : (BM <= 16 ? 4 : (BM <= 32 ? (big ? 3 : 4) : 2));
+    // (never deeper than the policy allows: UintxWO's third stage costs 84 VGPRs)
+    constexpr int D0 = TAO_GEMM_DEPTH > 0 ? TAO_GEMM_DEPTH
+                                          : (BM <= 16 ? 4 : (BM <= 32 ? (big ? 3 : 4) : 2));
+    constexpr int D = D0 < P::kMaxDepth ? D0 : P::kMaxDepth;
     launch((gemm_mfma_kernel<BM, D, KG, NW, P>), grid, dim3(256 * KG), 0, stream, xb, pol, bias, y,
            M, N, K, sps, slab, cnt, tuning().splitk_fenced, tuning().gemm_order,
            tuning().cnt_stride);
@@ -685,7 +715,7 @@ int gshift_of(int64_t g) {
 // (TAO_GEMM_FP6_TU, Makefile) compiled without the packed fp32 instructions; that object holds
 // fp6_mm_launch and nothing else, this one everything else. The existing instances keep the
 // flags, and so the instructions, they were measured with.
-#ifdef TAO_GEMM_FP6_TU
+#if defined(TAO_GEMM_FP6_TU)
 // FP6 weight-only (fp6.hip): the calls its route rule gives to the MFMA route (fp6_host.h)
 int fp6_mm_launch(const uint16_t* x, const uint32_t* codes, const uint16_t* scale,
                   const uint16_t* bias, uint16_t* y, int M, int N, int K, int fmt,
@@ -705,6 +735,36 @@ int fp6_mm_launch(const uint16_t* x, const uint32_t* codes, const uint16_t* scal
   Fp6WO<1> pol;
   pol.w = codes;
   pol.scale = scale;
+  return launch_gemm(x, pol, bias, y, M, N, K, stream);
+}
+
+}  // namespace tao
+#elif defined(TAO_GEMM_UINTX_TU)
+// The UintxWO<BITS> instances: one more object of this file per width (TAO_GEMM_UINTX_TU = BITS,
+// Makefile), each holding uintx_mm_launch<BITS> and nothing else, so the seven build side by side.
+// uintx weight-only (uintx.hip): the calls its route rule gives to the MFMA route (uintx_host.h)
+template <>
+int uintx_mm_launch<TAO_GEMM_UINTX_TU>(const uint16_t* x, const uint8_t* s4, const uint8_t* s2,
+                                       const uint8_t* s1, const uint16_t* scale, const int32_t* zp,
+                                       const uint16_t* bias, uint16_t* y, int M, int N, int K,
+                                       int group, hipStream_t stream) {
+  // one buffer descriptor per operand, 32-bit byte counts and offsets; a lane's offset runs up to
+  // one window past either end of a shard before the range check drops it
+  constexpr int64_t kMaxBytes = (1LL << 32) - 4096;
+  TAO_CHECK_ARG((int64_t)N * (K / 2) <= kMaxBytes && (int64_t)N * (K / group) * 4 <= kMaxBytes &&
+                    (int64_t)M * K * 2 <= kMaxBytes,
+                "uintx linear (MFMA route): a shard (N x K = %d x %d), the zero points (group %d) "
+                "and x (M = %d) must each be below 4 GiB", N, K, group, M);
+  TAO_CHECK_ARG(tuning().gemm_nw != 2,
+                "uintx linear (MFMA route): built for 16 columns per wave only (tao_tune_gemm_nw 2)");
+  UintxWO<TAO_GEMM_UINTX_TU> pol;
+  pol.s4 = s4;
+  pol.s2 = s2;
+  pol.s1 = s1;
+  pol.scale = scale;
+  pol.zp = zp;
+  pol.gmul = uintx_group_mul(group);
+  pol.ngrp = K / group;
   return launch_gemm(x, pol, bias, y, M, N, K, stream);
 }
 
@@ -955,4 +1015,4 @@ extern "C" int tao_tune_gemm(int m_tile, int k_groups, int splits) {
   tao::tuning().splits = splits;
   return TAO_OK;
 }
-#endif  // TAO_GEMM_FP6_TU
+#endif  // TAO_GEMM_FP6_TU / TAO_GEMM_UINTX_TU

@@ -36,10 +36,13 @@ struct PolicyDefaults {
   static constexpr bool kMaskTail = false;     // weights past a K tail need no zeroing
   static constexpr int kASlots = 1;            // 16-B x slots one MFMA reads per lane
   static constexpr int kMaxKG = 4;             // k-groups per workgroup the policy is built for
+  static constexpr int kMaxDepth = 4;          // deepest load ring the policy is built with
   static constexpr bool kBlockScaled = false;  // the MFMAs take per-block scale bytes
   static constexpr bool kScaleAligned = false;  // ... a row's 8 per step are one aligned 8-B word
   static constexpr bool kBlockF32 = false;     // fp32 scales per 128-k block, applied per MFMA
   static constexpr bool kXPerm = false;        // x pieces pass through xperm() on their way to LDS
+  static constexpr bool kXGather = false;      // an x row's step is strided pieces: xoff() / xin()
+  static constexpr bool kGroupF32 = false;     // per-group scale and zero point, applied per MFMA
   typedef f32x4_t Acc;
   // x image mask (x_slot, gemm_mfma.hip)
   static __device__ __forceinline__ int xswz(int row) { return row & 15; }
@@ -435,6 +438,188 @@ struct Fp6WO : PolicyDefaults {
   __device__ __forceinline__ float epi(float acc, float, float sc) const {
     return round_bf16(acc * sc);
   }
+};
+
+// UintxWO<BITS>: bf16 x, uintx W (1 to 7 bits, uintx.hip) read in place from the UintxLayout
+// shards s4 [N][K/2], s2 [N][K/4], s1 [N][K/8]; bf16 scale and int32 zero point per (row, group).
+// With K8 = K / 8, element k = j K8 + i lies in segment j at position i; the byte at position i of
+// s4 piece j & 3, s2 piece j & 1 and the one s1 piece holds its 4-, 2- and 1-bit parts.
+//  * k order: a step is the position window [32 st, 32 st + 32) of all eight segments, 256 codes per
+//    row. MFMA s of the step is segment s, and lane (n, kq) supplies its positions 8 kq .. 8 kq + 7:
+//    the MFMA's 32 k are consecutive. x is gathered to match (kXGather): the 16-B slot 4 j + q of
+//    the x image is x[m][j K8 + 32 st + 8 q .. + 8], so slot(s, kq) = 4 s + kq, Int8Dyn's map,
+//    conflict-free under the plain row mask.
+//  * K8 % 32 == 16 (K % 256 == 128): an odd segment starts at k = 16 (mod 32), so its windows are
+//    [32 st - 16, 32 st + 16) instead: every MFMA still covers one aligned 32-k block, which a group
+//    of a multiple of 32 never splits (uintx_mfma_ok). The half window before an odd segment's
+//    start (st = 0) and the one past an even segment's end (the last step) are zeroed in the x image
+//    (xin()); the codes loaded there are another piece's, the next row's or, past the array, the 0 of
+//    the range check, and meet that 0.
+//  * Intake: the lane that feeds the MFMA loads its own bytes, one 8-B load per piece (4 + 2 + 1,
+//    and the s1 piece a second time at the odd segments' offset): a wave's load is 16 rows x 32 B.
+//    No LDS stage for the codes. Every offset that can leave the array rides in the vector offset,
+//    which the descriptor checks (the scalar one is not checked).
+//  * Decode: frag() cuts segment s out of the lane's dwords by whole-dword shifts and masks (the
+//    GEMV's codes4) and puts each code byte under 0x43: the bf16 number 128 + q, exactly. Per lane
+//    and MFMA (8 codes): 2 x (and, 2 x shift-and-or) at 7 bits, then 4 v_perm_b32: 10 VALU at most,
+//    4 at uint4 / uint2 / uint1 segment 0.
+//  * Scales: the MFMA runs into a zero accumulator, a second one against a B of ones gives the
+//    sum of the same 32 x per row, and acc += s (P - (zp + 128) X) in fp32 (kGroupF32): 8 FMAs per
+//    lane, MFMA and M tile. The products are unrounded and the correction is applied per group, so
+//    integer inputs stay exact (tests/test_gpu_exact_uintx_mfma.py); the result is the GEMV's.
+//    Lane (n, kq) loads the (scale, zp) of segments kq and 4 + kq (four loads riding in the weight
+//    ring) and the wave's lanes exchange them as (s, zp + 128) floats through an 80-B-pitch stage
+//    (16 rows x 8 pairs; pitch 5 granules, coprime to 16: the b128 reads are conflict-free).
+//  * Instances: 16 columns per wave only, k-groups x BM <= 64 (what choose_shape names).
+template <int BITS>
+struct UintxWO : PolicyDefaults {
+  static_assert(BITS >= 1 && BITS <= 7, "1 to 7 bits");
+  static constexpr int kPathId = 10;  // no measured table entries: the heuristic shapes
+  static constexpr int kABytes = 2;   // bf16 x
+  static constexpr int kKStep = 256;
+  static constexpr int kMfma = 8;
+  static constexpr int kMaxBM = 64;  // 512-B x rows, as Int4WO
+  static constexpr int kPrefKG = 2;
+  static constexpr int kMaxKG = 2;
+  // Ring depth 2 at every BM. At 7 bits and BM = 16 depth 2 / 3 / 4 take 116 / 200 / 256 VGPRs (the
+  // last with 24 B of scratch); 116 keeps four waves per SIMD in flight, 200 two.
+  static constexpr int kMaxDepth = 2;
+  static constexpr int kMinSlice = 4;
+  static constexpr bool kXGather = true;
+  static constexpr bool kGroupF32 = true;
+  static constexpr int kXStepB = 64;  // x bytes per segment and step
+  static constexpr bool kS4 = (BITS & 4) != 0, kS2 = (BITS & 2) != 0, kS1 = (BITS & 1) != 0;
+  static constexpr int kPos2 = kS4 ? 4 : 0, kPos1 = kPos2 + (kS2 ? 2 : 0);
+  static constexpr int kI2 = kS4 ? 4 : 0, kI1 = kI2 + (kS2 ? 2 : 0);  // first piece of s2, s1
+  static constexpr int kPieces = kI1 + (kS1 ? 2 : 0);
+  static constexpr int kPitch = 80;                // qparam stage row pitch, bytes
+  static constexpr int kStage = 16 * kPitch / 16;  // uint4 per wave
+  static constexpr bool fits(int bm, int kg, int nw) { return nw == 1 && kg * bm <= 64; }
+  const uint8_t *s4, *s2, *s1;
+  const uint16_t* scale;  // [N][K / group] bf16
+  const int32_t* zp;      // [N][K / group]
+  uint32_t gmul;          // ceil(2^32 / group) (uintx_group_mul)
+  int ngrp;               // K / group
+  typedef uint32_t StageW __attribute__((ext_vector_type(2), may_alias));
+  typedef uint32_t StageR __attribute__((ext_vector_type(4), may_alias));
+  struct Lane {
+    Rsrc r4, r2, r1, rs, rz;
+    uint32_t v4, v2, v1;  // byte 8 kq of piece 0 of row n of each shard
+    uint32_t q;           // n * ngrp
+    uint32_t ka;          // kq * K8: segment kq's first k
+    int K8, odd;          // odd: positions an odd segment's window starts early, 16 or 0
+  };
+  struct Chunk {
+    uint2 w[kPieces];  // s4 pieces 0..3, s2 pieces 0..1, s1 at the even and at the odd offset
+    uint32_t sc[2], zp[2];  // of segments kq and 4 + kq
+  };
+  struct Prep {
+    uint2 w[kPieces];
+    float s[8], zc[8];  // per segment: scale, zp + 128
+  };
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    const uint32_t n = bn < N ? bn : N - 1, kq = lane >> 4;
+    Lane L;
+    L.K8 = K >> 3;
+    L.odd = L.K8 & 16;
+    if constexpr (kS4) L.r4 = make_rsrc(s4, (uint32_t)N * (uint32_t)(K >> 1));
+    if constexpr (kS2) L.r2 = make_rsrc(s2, (uint32_t)N * (uint32_t)(K >> 2));
+    if constexpr (kS1) L.r1 = make_rsrc(s1, (uint32_t)N * (uint32_t)L.K8);
+    L.rs = make_rsrc(scale, (uint32_t)N * (uint32_t)ngrp * 2u);
+    L.rz = make_rsrc(zp, (uint32_t)N * (uint32_t)ngrp * 4u);
+    L.v4 = n * 4u * L.K8 + 8u * kq;
+    L.v2 = n * 2u * L.K8 + 8u * kq;
+    L.v1 = n * (uint32_t)L.K8 + 8u * kq;
+    L.q = n * (uint32_t)ngrp;
+    L.ka = kq * (uint32_t)L.K8;
+    return L;
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    Chunk ch;
+    const int o = st * 32;
+    if constexpr (kS4) {
+#pragma unroll
+      for (int h = 0; h < 4; ++h)
+        ch.w[h] = bload8<kNT>(L.r4, L.v4 + (uint32_t)(o + h * L.K8 - (h & 1) * L.odd), 0);
+    }
+    if constexpr (kS2) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        ch.w[kI2 + h] = bload8<kNT>(L.r2, L.v2 + (uint32_t)(o + h * L.K8 - h * L.odd), 0);
+    }
+    if constexpr (kS1) {
+      ch.w[kI1] = bload8<kNT>(L.r1, L.v1 + (uint32_t)o, 0);
+      ch.w[kI1 + 1] = bload8<kNT>(L.r1, L.v1 + (uint32_t)(o - L.odd), 0);
+    }
+    // k = j K8 + 32 st lies in the block MFMA j covers at either window offset
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const uint32_t gi = L.q + __umulhi(L.ka + (uint32_t)(4 * u * L.K8 + o), gmul);
+      ch.sc[u] = bload2(L.rs, gi * 2u, 0);
+      ch.zp[u] = bload4(L.rz, gi * 4u, 0);
+    }
+    return ch;
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    const int n = lane & 15, kq = lane >> 4;
+    StageW* wr = reinterpret_cast<StageW*>(stage) + n * (kPitch / 8) + kq;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      wr[4 * u] = StageW{ch.sc[u] << 16, __float_as_uint((float)(int)ch.zp[u] + 128.f)};
+    const StageR* rd = reinterpret_cast<const StageR*>(stage) + n * (kPitch / 16);
+    Prep p;
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i) p.w[i] = ch.w[i];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const StageR v = rd[r];
+      p.s[2 * r] = __uint_as_float(v[0]);
+      p.zc[2 * r] = __uint_as_float(v[1]);
+      p.s[2 * r + 1] = __uint_as_float(v[2]);
+      p.zc[2 * r + 1] = __uint_as_float(v[3]);
+    }
+    return p;
+  }
+  // B fragment of MFMA s: the codes of segment s at the lane's 8 positions, as bf16 128 + q
+  __device__ __forceinline__ bf16x8_t frag(const Prep& p, int s) const {
+    uint32_t c[2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      auto dw = [&](int i) { return d == 0 ? p.w[i].x : p.w[i].y; };
+      c[d] = 0;
+      if constexpr (kS4) c[d] = (dw(s & 3) >> (4 * (s >> 2))) & 0x0F0F0F0Fu;
+      if constexpr (kS2) c[d] |= ((dw(kI2 + (s & 1)) >> (2 * (s >> 1))) & 0x03030303u) << kPos2;
+      if constexpr (kS1) c[d] |= ((dw(kI1 + (s & 1)) >> s) & 0x01010101u) << kPos1;
+    }
+    return as_bf16x8(__builtin_amdgcn_perm(0x43434343u, c[0], 0x04010400u),
+                     __builtin_amdgcn_perm(0x43434343u, c[0], 0x04030402u),
+                     __builtin_amdgcn_perm(0x43434343u, c[1], 0x04010400u),
+                     __builtin_amdgcn_perm(0x43434343u, c[1], 0x04030402u));
+  }
+  static __device__ __forceinline__ bf16x8_t ones() {
+    return as_bf16x8(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);
+  }
+  // acc += s (P - (zp + 128) X): pr the MFMA's product against 128 + q, sx the one against ones
+  static __device__ __forceinline__ Acc group_acc(const Acc& pr, const Acc& sx, const Prep& p,
+                                                  int s, Acc c) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      c[i] = __builtin_fmaf(p.s[s], __builtin_fmaf(-p.zc[s], sx[i], pr[i]), c[i]);
+    return c;
+  }
+  static __device__ __forceinline__ int slot(int s, int kq) { return 4 * s + kq; }
+  // (kXGather) byte offset in an x row of image slot 4 j + q at step 0; the step adds kXStepB
+  static __device__ __forceinline__ uint32_t xoff(int slot, int K) {
+    const int j = slot >> 2, K8 = K >> 3;
+    return 2u * (uint32_t)(j * K8 - (j & 1) * (K8 & 16)) + 16u * (slot & 3);
+  }
+  // whether the slot's 8 positions at step st lie inside their segment
+  static __device__ __forceinline__ bool xin(int slot, int st, int K) {
+    const int K8 = K >> 3;
+    return (uint32_t)(32 * st + 8 * (slot & 3) - ((slot >> 2) & 1) * (K8 & 16)) < (uint32_t)K8;
+  }
+  // the GEMV's output (uintx.hip): bf16(sum); the bias add and its rounding follow in the kernel
+  __device__ __forceinline__ float epi(float acc, float, float) const { return round_bf16(acc); }
 };
 
 struct Int8Dyn : ByteWeights<256> {

@@ -94,6 +94,7 @@ struct Tuning {
   int uintx_rpw = 0, uintx_wk = 0, uintx_g = 0;  // uintx GEMV launch shape (tao_tune_uintx)
   int uintx_xlds = 0;                            // uintx GEMV x: 0 built-in, 1 through L1, 2 staged in LDS
   int uintx_unit = 0;                            // uintx GEMV bytes of a shard piece per lane unit
+  int uintx_mfma = 0;                            // uintx linear: 1 = MFMA GEMM where the rule says dequant + mm
   int moe_bm = 0, moe_dual = 0;                  // grouped (MoE) int4 GEMM row tile / dual form (tao_tune_moe)
 };
 Tuning& tuning();
@@ -246,6 +247,18 @@ __device__ __forceinline__ void bstore16(Rsrc r, uint32_t voff, uint32_t soff, u
 template <int AUX = 0>
 __device__ __forceinline__ uint32_t bload4(Rsrc r, uint32_t voff, uint32_t soff) {
   return __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, AUX);
+}
+
+template <int AUX = 0>
+__device__ __forceinline__ uint2 bload8(Rsrc r, uint32_t voff, uint32_t soff) {
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  const u32x2 v =
+      __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, AUX));
+  return make_uint2(v[0], v[1]);
+}
+template <int AUX = 0>
+__device__ __forceinline__ uint32_t bload2(Rsrc r, uint32_t voff, uint32_t soff) {
+  return __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, AUX);
 }
 
 constexpr int kWave = 64;

@@ -75,6 +75,11 @@ int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq
 int fp6_mm_launch(const uint16_t* x, const uint32_t* codes, const uint16_t* scale,
                   const uint16_t* bias, uint16_t* y, int M, int N, int K, int fmt,
                   hipStream_t stream);
+// one specialisation per width 1..7, each in an object of its own (gemm_mfma.hip TAO_GEMM_UINTX_TU)
+template <int BITS>
+int uintx_mm_launch(const uint16_t* x, const uint8_t* s4, const uint8_t* s2, const uint8_t* s1,
+                    const uint16_t* scale, const int32_t* zp, const uint16_t* bias, uint16_t* y,
+                    int M, int N, int K, int group, hipStream_t stream);
 int w4a8_scaled_mm_launch(const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
                           const uint16_t* bias, uint16_t* y, int M, int N, int K,
                           hipStream_t stream);

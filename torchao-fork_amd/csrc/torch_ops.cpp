@@ -1391,7 +1391,7 @@ Tensor uintx_weight_only_linear(const Tensor& x, const std::optional<Tensor>& s4
   const int64_t M = x2.size(0);
   const std::optional<Tensor> b = bf16_bias(bias);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  if (M > 0 && N > 0 && tao_uintx_linear_route(M, N, K, (int)bits) == 2) {
+  if (M > 0 && N > 0 && tao_uintx_linear_route_g(M, N, K, (int)bits, (int)group) == 2) {
     // W^ into a temporary of the caching allocator, then the bf16 matmul; the bias is a second
     // rounding, as on the other route
     const Tensor w = uintx_dequantize_checked(p, bits, group);

@@ -1,7 +1,9 @@
 // uintx (torch.uint1 .. torch.uint7) weight-only linear (UIntXWeightOnlyConfig): the decode GEMV
 // and the dequantizer behind tao_uintx_linear_bf16 and tao_uintx_dequant_bf16
 // (torchao/dtypes/uintx/uintx_layout.py). The route rule, the GEMV's tile and its lane unit are in
-// uintx_host.h.
+// uintx_host.h. A third route, the UintxWO policy of gemm_mfma_kernel (gemm_mfma_policy.h), reads the
+// same shards; tao_uintx_linear_bf16 reaches it through tao_tune_uintx_mfma until the route rule
+// names it.
 //
 // Storage, read in place (the reference's UintxLayout shards, pack_dim = -1): a code of BITS bits
 // is cut into its 4-, 2- and 1-bit parts (the set bits of BITS), each part a uint8 stream per row:
@@ -18,6 +20,7 @@
 //   linear:      y[m][n]  = bf16( sum_k x[m][k] (q - zp) s )  fp32 sums (+ bias -> bf16)
 #include <type_traits>
 
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 #include "uintx_host.h"
 
@@ -372,8 +375,14 @@ extern "C" int tao_uintx_dequant_bf16(const uint8_t* s4, const uint8_t* s2, cons
   });
 }
 
+extern "C" int tao_uintx_linear_route_g(int64_t M, int64_t N, int64_t K, int bits,
+                                        int group_size) {
+  const tao::Tuning& tu = tao::tuning();
+  return tao::uintx_route(M, N, K, bits, tu.uintx_route, tu.uintx_max_m, tu.uintx_mfma, group_size);
+}
+
 extern "C" int tao_uintx_linear_route(int64_t M, int64_t N, int64_t K, int bits) {
-  return tao::uintx_route(M, N, K, bits, tao::tuning().uintx_route, tao::tuning().uintx_max_m);
+  return tao_uintx_linear_route_g(M, N, K, bits, 0);
 }
 
 extern "C" int tao_uintx_gemv_unit(int64_t M, int64_t K, int bits) {
@@ -403,6 +412,13 @@ extern "C" int tao_uintx_linear_bf16(const uint16_t* x, const uint8_t* s4, const
   TAO_CHECK_ALIGN(y, 2, "y");
   if (bias != nullptr) TAO_CHECK_ALIGN(bias, 2, "bias");
   const Tuning& tu = tuning();
+  // the UintxWO policy of gemm_mfma_kernel where the rule names it (tao_tune_uintx_mfma)
+  if (uintx_route(M, N, K, bits, tu.uintx_route, tu.uintx_max_m, tu.uintx_mfma, group_size) ==
+      kUintxRouteMfma)
+    return dispatch_uintx_bits(bits, [&](auto b) {
+      return uintx_mm_launch<decltype(b)::value>(x, s4, s2, s1, scale, zero_point, bias, y, (int)M,
+                                                 (int)N, (int)K, group_size, as_stream(stream));
+    });
   // 8-token pieces: one launch wherever the route rule chose the GEMV, a sequence of them where
   // a caller forces it beyond (or calls this entry on a shape the op would dequantize)
   for (int64_t m0 = 0; m0 < M; m0 += kUintxGemvMaxM) {
@@ -418,6 +434,12 @@ extern "C" int tao_uintx_linear_bf16(const uint16_t* x, const uint8_t* s4, const
     });
     if (rc != TAO_OK) return rc;
   }
+  return TAO_OK;
+}
+
+extern "C" int tao_tune_uintx_mfma(int on) {
+  TAO_CHECK_ARG(on == 0 || on == 1, "tune: uintx mfma must be 0 (built-in route) or 1");
+  tao::tuning().uintx_mfma = on;
   return TAO_OK;
 }
 

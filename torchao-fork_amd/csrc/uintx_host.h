@@ -28,13 +28,13 @@ static inline uint32_t uintx_group_mul(int64_t group) {
   return (uint32_t)(((1LL << 32) + group - 1) / group);
 }
 
-enum { kUintxRouteAuto = 0, kUintxRouteGemv = 1, kUintxRouteDequantMm = 2 };
+enum { kUintxRouteAuto = 0, kUintxRouteGemv = 1, kUintxRouteDequantMm = 2, kUintxRouteMfma = 3 };
 
 // The most tokens one GEMV launch serves (uintx_gemv_kernel<*, 8, 1, *>); a forced GEMV beyond it
 // is a sequence of launches over 8-token pieces.
 constexpr int kUintxGemvMaxM = 8;
 
-// Two routes: the decode GEMV, and the dequantizer into a temporary + the bf16 matmul. force:
+// Two built-in routes: the decode GEMV, and the dequantizer into a temporary + the bf16 matmul. force:
 // tao_tune_uintx's route (kUintxRoute*); max_gemv_m > 0 moves the boundary (tao_tune_uintx too).
 // The built-in boundary is measured per width (experiments/bench_uintx.py --boundary,
 // profiles/uintx_bench_boundary.jsonl, both routes forced at M = 4, 8, 12, 16; us GEMV vs
@@ -49,13 +49,29 @@ static inline int uintx_default_max_m(int bits) {
   (void)bits;
   return 8;
 }
+// What the UintxWO policy of gemm_mfma_kernel serves (gemm_mfma_policy.h): each of its MFMAs takes
+// the 32 consecutive k of one aligned 32-k block and meets one (scale, zero point) pair, so a
+// group must be a whole number of such blocks. K needs nothing beyond uintx_shape_ok: where
+// K / 8 is an odd multiple of 16 the odd segments' step windows start 16 positions early, which
+// keeps every MFMA on an aligned block. group_size <= 0: not known to the caller
+// (tao_uintx_linear_route), taken as served.
+static inline bool uintx_mfma_ok(int64_t K, int64_t group) {
+  if (group <= 0) return K > 0 && K < (1LL << 31) && K % 128 == 0;
+  return uintx_shape_ok(K, group) && group % 32 == 0;
+}
+
+// A third route, the UintxWO policy of gemm_mfma_kernel, is behind a hook of its own (mfma:
+// tao_tune_uintx_mfma): with it on, every call this rule would send to dequantize + matmul, and
+// that uintx_mfma_ok serves, goes to the MFMA GEMM instead. A forced route still wins, and
+// max_gemv_m still moves the GEMV boundary. The built-in rule does not name it yet (measurements
+// and the boundary they suggest: DESIGN 4.23.1).
 static inline int uintx_route(int64_t M, int64_t N, int64_t K, int bits, int force,
-                              int max_gemv_m) {
+                              int max_gemv_m, int mfma = 0, int64_t group = 0) {
   (void)N;
-  (void)K;
   if (force == kUintxRouteGemv || force == kUintxRouteDequantMm) return force;
   const int64_t lim = max_gemv_m > 0 ? max_gemv_m : uintx_default_max_m(bits);
-  return M <= lim ? kUintxRouteGemv : kUintxRouteDequantMm;
+  if (M <= lim) return kUintxRouteGemv;
+  return mfma && uintx_mfma_ok(K, group) ? kUintxRouteMfma : kUintxRouteDequantMm;
 }
 
 // Tokens per lane set (MT) and rows per wave (RPW) of the GEMV launch that serves m <= 8 tokens:

@@ -105,6 +105,8 @@ _SIGNATURES = {
     "tao_uintx_dequant_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _int, _int, _p],
     "tao_uintx_linear_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p],
     "tao_uintx_linear_route": [_i64, _i64, _i64, _int],
+    "tao_uintx_linear_route_g": [_i64, _i64, _i64, _int, _int],
+    "tao_tune_uintx_mfma": [_int],
     "tao_uintx_gemv_unit": [_i64, _i64, _int],
     "tao_tune_uintx": [_int, _int, _int, _int, _int, _int, _int],
     "tao_uintx_gemv_x_lds": [_i64, _i64, _int],

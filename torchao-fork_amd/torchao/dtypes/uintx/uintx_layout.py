@@ -9,7 +9,9 @@ is such a tensor.
 The reference has no kernel for this layout on any device: its linear unpacks the shards,
 dequantizes the whole weight and calls ``F.linear``. Here bf16 activations on the GPU with
 ``K % 128 == 0`` and ``group_size % 16 == 0`` run ``torch.ops.torchao.uintx_weight_only_linear``
-(csrc/uintx.hip), which reads the shards in place; every other input takes the table's generic
+(csrc/uintx.hip), which reads the shards in place (above 8 tokens it dequantizes into a temporary
+and calls the bf16 matmul; under ``torchao.kernel.tuning.tuning(uintx_mfma=1)`` an MFMA GEMM on
+the same shards serves those calls where ``group_size % 32 == 0``); every other input takes the table's generic
 dequantize -> ``F.linear`` route, the reference's arithmetic. One addition to the reference's
 surface: ``UintxTensor`` is registered as a safe global, so a ``state_dict`` saved here loads with
 ``weights_only=True``.

@@ -54,6 +54,9 @@ _KNOBS = {
     # piece per lane unit: 0 built-in, 4, 8, 16; x of the 4- / 8-token tiles: 0 built-in, 1 through
     # L1, 2 staged in LDS)
     "uintx": ("tao_tune_uintx", 7),
+    # 1: the MFMA GEMM wherever the uintx route rule says dequantize + matmul and the kernel serves
+    # the shape (group_size a multiple of 32)
+    "uintx_mfma": ("tao_tune_uintx_mfma", 1),
     # (rows per tile of the grouped MoE GEMM: 0 built-in, 16, 32, 64; gate and up: 0 built-in,
     # 1 = two launches, 2 = one)
     "moe": ("tao_tune_moe", 2),
