@@ -1,6 +1,6 @@
 // Stand-alone host program for the sanitizers: runs the host-side arithmetic of the NF4 linear
-// (csrc/nf4_host.h: the route rule, the GEMV's tile choice, the factor count) over a sweep of
-// arguments and checks the invariants nf4.hip and torch_ops.cpp rely on. No GPU call.
+// (csrc/nf4_host.h over csrc/wo_host.h: the route rule, the GEMV's tile choice, the factor count)
+// over a sweep of arguments and checks the invariants nf4.hip and torch_ops.cpp rely on. No GPU call.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //     -I torchao-fork_amd/csrc experiments/sanitize_nf4_host.cpp -o sanitize_nf4_host \
 //     && ./sanitize_nf4_host
@@ -28,10 +28,10 @@ int main() {
       for (int64_t M = 0; M <= 4200; M = M < 40 ? M + 1 : M * 2 + 1) {
         for (int force = 0; force <= 2; ++force)
           for (int lim : {0, 1, 2, 8, 64}) {
-            const int r = nf4_route(M, N, K, force, lim);
-            CHECK(r == kNf4RouteGemv || r == kNf4RouteDequantMm);
-            if (force != kNf4RouteAuto) CHECK(r == force);
-            else CHECK((r == kNf4RouteGemv) == (M <= (lim > 0 ? lim : kNf4GemvDefaultM)));
+            const int r = nf4_route(M, force, lim);
+            CHECK(r == kWoRouteGemv || r == kWoRouteDequantMm);
+            if (force != kWoRouteAuto) CHECK(r == force);
+            else CHECK((r == kWoRouteGemv) == (M <= (lim > 0 ? lim : kNf4GemvDefaultM)));
             ++cases;
           }
       }
@@ -40,8 +40,8 @@ int main() {
       if (blocks > 0) CHECK(((blocks - 1) >> 8) < nf4_num_factors(N, K));
       CHECK(nf4_num_factors(N, K) * 16384 >= N * K && (nf4_num_factors(N, K) - 1) * 16384 < N * K);
     }
-  for (int m = 1; m <= kNf4GemvMaxM; ++m) {
-    const Nf4GemvTile t = nf4_gemv_tile(m);
+  for (int m = 1; m <= kWoGemvMaxM; ++m) {
+    const WoGemvTile t = wo_gemv_tile(m);
     CHECK(t.mt >= m && t.mt * t.rpw == (m == 1 ? 4 : 8));
     CHECK(t.mt == 1 || t.mt == 2 || t.mt == 4 || t.mt == 8);
     ++cases;

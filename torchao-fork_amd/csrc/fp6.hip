@@ -1,7 +1,8 @@
 // FP6 (e3m2 / e2m3) weight-only linear (FPXWeightOnlyConfig): row quantizer, dequantizer and the
 // decode GEMV behind tao_fp6_quantize_rows_bf16, tao_fp6_dequant_bf16 and tao_fp6_linear_bf16
 // (torchao/dtypes/floatx/floatx_tensor_core_layout.py). The formats' arithmetic and the storage
-// are in fp6_codec.h; the route rule and the GEMV's tile choice are in fp6_host.h.
+// are in fp6_codec.h, the measured boundary of its route rule and the lane chunk in fp6_host.h; the
+// rule, the GEMV's tile, launch and tail are the weight-only front end's (wo_host.h, tao_gemv.h).
 //
 //   quantize, per row:   s = bf16(max(amax|w|, 1e-12) / max_normal)     the IEEE fp32 quotient
 //                        code = fp6_rne_sat(float(w) / float(s))         again a true division
@@ -203,6 +204,7 @@ __global__ __launch_bounds__(512) void fp6wo_gemv_kernel(
     }
   }
 
+  // the tail, written out in each GEMV kernel (tao_gemv.h, "the plain weight-only GEMVs' tail")
   float v[V];
 #pragma unroll
   for (int r = 0; r < RPW; ++r)
@@ -223,37 +225,24 @@ __global__ __launch_bounds__(512) void fp6wo_gemv_kernel(
   }
 }
 
-// wk, g: 0 = the default shape, Wk = min(S, 8) waves along K and as many row groups as fit 8 waves
-// (M > 1), one row group at M == 1: the byte-weight GEMVs' choice (tao_gemv.h wo8_gemv).
+// wk, g: tao_tune_fp6's, 0 = the default shape (tao_gemv.h wo_gemv_launch)
 template <int FMT, int MT, int RPW, int GRP>
 int fp6_gemv_launch(const uint16_t* x, const uint32_t* w, const uint16_t* scale,
                     const uint16_t* bias, uint16_t* y, int M, int N, int K, hipStream_t stream,
                     int wk, int g) {
-  const GemvLaunchShape sh =
-      gemv_launch_shape(K / (kFp6Group * GRP), wk > 0 ? wk : 8, g > 0 ? g : (MT == 1 ? 1 : 8));
-  const int rows_per_wg = sh.G * RPW;
-  const int grid = (N + rows_per_wg - 1) / rows_per_wg;
-  const size_t lds = (size_t)sh.G * sh.Wk * RPW * MT * sizeof(float);
-  launch(fp6wo_gemv_kernel<FMT, MT, RPW, GRP>, dim3(grid), dim3(64 * sh.Wk * sh.G), lds, stream, x,
-         w, scale, bias, y, M, N, K, sh.Wk, sh.G, sh.S);
+  const WoGemvLaunch L = wo_gemv_launch(K / (kFp6Group * GRP), N, MT, RPW, wk, g);
+  launch(fp6wo_gemv_kernel<FMT, MT, RPW, GRP>, dim3(L.grid), dim3(L.threads), L.lds, stream, x, w,
+         scale, bias, y, M, N, K, L.Wk, L.G, L.S);
   return check_launch("fp6wo_gemv_kernel");
 }
 
 template <int FMT, int GRP>
 int fp6_gemv(const uint16_t* x, const uint32_t* w, const uint16_t* scale, const uint16_t* bias,
-             uint16_t* y, int m, int N, int K, hipStream_t st, const Tuning& tu) {
-  const Fp6GemvTile tile = fp6_gemv_tile(m);
-#define TAO_FP6(MT, RPW) \
-  return fp6_gemv_launch<FMT, MT, RPW, GRP>(x, w, scale, bias, y, m, N, K, st, tu.fp6_wk, tu.fp6_g)
-  if (tile.mt == 1) {
-    if (tu.fp6_rpw == 2) TAO_FP6(1, 2);
-    if (tu.fp6_rpw == 8) TAO_FP6(1, 8);
-    TAO_FP6(1, 4);
-  }
-  if (tile.mt == 2) TAO_FP6(2, 4);
-  if (tile.mt == 4) TAO_FP6(4, 2);
-  TAO_FP6(8, 1);
-#undef TAO_FP6
+             uint16_t* y, int m, int N, int K, hipStream_t st, const WoTune& tu) {
+  return dispatch_gemv_tile(m, tu.rpw, [&](auto mt, auto rpw) {
+    return fp6_gemv_launch<FMT, decltype(mt)::value, decltype(rpw)::value, GRP>(
+        x, w, scale, bias, y, m, N, K, st, tu.wk, tu.g);
+  });
 }
 
 int check_fp6_format(const char* what, int ebits, int mbits) {
@@ -313,7 +302,9 @@ extern "C" int tao_fp6_dequant_bf16(const uint32_t* codes, const uint16_t* scale
 }
 
 extern "C" int tao_fp6_linear_route(int64_t M, int64_t N, int64_t K) {
-  return tao::fp6_route(M, N, K, tao::tuning().fp6_route, tao::tuning().fp6_max_m,
+  (void)N;
+  (void)K;
+  return tao::fp6_route(M, tao::tuning().fp6.route, tao::tuning().fp6.max_m,
                         tao::tuning().fp6_mfma);
 }
 
@@ -333,51 +324,29 @@ extern "C" int tao_fp6_linear_bf16(const uint16_t* x, const uint32_t* codes, con
   TAO_CHECK_ALIGN(y, 2, "y");
   if (bias != nullptr) TAO_CHECK_ALIGN(bias, 2, "bias");
   const hipStream_t st = as_stream(stream);
-  const Tuning& tu = tuning();
+  const WoTune& tu = tuning().fp6;
   const int fmt = fp6_format_of(ebits, mbits);
-  const int grp = fp6_chunk_groups(tu.fp6_groups);
+  const int grp = fp6_chunk_groups(tuning().fp6_groups);
   // the Fp6WO policy of gemm_mfma_kernel where the rule names it (tao_tune_fp6_mfma)
-  if (fp6_route(M, N, K, tu.fp6_route, tu.fp6_max_m, tu.fp6_mfma) == kFp6RouteMfma)
+  if (fp6_route(M, tu.route, tu.max_m, tuning().fp6_mfma) == kWoRouteMfma)
     return fp6_mm_launch(x, codes, scale, bias, y, (int)M, (int)N, (int)K, fmt, st);
-  // 8-token pieces: one launch wherever the route rule chose the GEMV, a sequence of them where
-  // a caller forces it beyond (or calls this entry on a shape the op would dequantize)
-  for (int64_t m0 = 0; m0 < M; m0 += kFp6GemvMaxM) {
-    const int m = (int)(M - m0 < kFp6GemvMaxM ? M - m0 : kFp6GemvMaxM);
-    const uint16_t* xm = x + m0 * K;
-    uint16_t* ym = y + m0 * N;
-    int rc;
+  return for_gemv_pieces(x, y, M, N, K, [&](const uint16_t* xm, uint16_t* ym, int m) {
     if (fmt == 0)
-      rc = grp == 1 ? fp6_gemv<0, 1>(xm, codes, scale, bias, ym, m, (int)N, (int)K, st, tu)
-                    : fp6_gemv<0, 2>(xm, codes, scale, bias, ym, m, (int)N, (int)K, st, tu);
-    else
-      rc = grp == 1 ? fp6_gemv<1, 1>(xm, codes, scale, bias, ym, m, (int)N, (int)K, st, tu)
+      return grp == 1 ? fp6_gemv<0, 1>(xm, codes, scale, bias, ym, m, (int)N, (int)K, st, tu)
+                      : fp6_gemv<0, 2>(xm, codes, scale, bias, ym, m, (int)N, (int)K, st, tu);
+    return grp == 1 ? fp6_gemv<1, 1>(xm, codes, scale, bias, ym, m, (int)N, (int)K, st, tu)
                     : fp6_gemv<1, 2>(xm, codes, scale, bias, ym, m, (int)N, (int)K, st, tu);
-    if (rc != TAO_OK) return rc;
-  }
-  return TAO_OK;
+  });
 }
 
 extern "C" int tao_tune_fp6(int route, int max_gemv_m, int rows_per_wave, int waves_k,
                             int row_groups, int chunk_groups) {
   using namespace tao;
-  TAO_CHECK_ARG(route >= kFp6RouteAuto && route <= kFp6RouteDequantMm,
-                "tune: fp6 route must be 0 (auto), 1 (gemv) or 2 (dequant + mm)");
-  TAO_CHECK_ARG(max_gemv_m >= 0, "tune: fp6 max_gemv_m must be >= 0");
-  TAO_CHECK_ARG(rows_per_wave == 0 || rows_per_wave == 2 || rows_per_wave == 4 ||
-                    rows_per_wave == 8,
-                "tune: fp6 rows_per_wave must be 0, 2, 4 or 8");
-  TAO_CHECK_ARG(waves_k >= 0 && waves_k <= 8, "tune: fp6 waves_k must be in [0, 8]");
-  TAO_CHECK_ARG(row_groups >= 0 && row_groups <= 8, "tune: fp6 row_groups must be in [0, 8]");
-  TAO_CHECK_ARG(waves_k * row_groups <= 8, "tune: fp6 waves_k * row_groups must be <= 8");
+  if (int rc = check_wo_tune("fp6", route, max_gemv_m, rows_per_wave, waves_k, row_groups)) return rc;
   TAO_CHECK_ARG(chunk_groups >= 0 && chunk_groups <= 2,
                 "tune: fp6 chunk_groups must be 0 (built-in), 1 (24 B) or 2 (48 B)");
-  Tuning& tu = tuning();
-  tu.fp6_route = route;
-  tu.fp6_max_m = max_gemv_m;
-  tu.fp6_rpw = rows_per_wave;
-  tu.fp6_wk = waves_k;
-  tu.fp6_g = row_groups;
-  tu.fp6_groups = chunk_groups;
+  tuning().fp6 = {route, max_gemv_m, rows_per_wave, waves_k, row_groups};
+  tuning().fp6_groups = chunk_groups;
   return TAO_OK;
 }
 

@@ -1,10 +1,13 @@
-// Host-side arithmetic of the FP6 weight-only linear (fp6.hip, torch_ops.cpp): which formats are
-// served, which route serves a call, and the decode GEMV's instantiation for a token count. Plain
+// Host-side arithmetic of the FP6 weight-only linear (fp6.hip, torch_ops.cpp) that is the format's
+// own: which formats are served, the measured boundary of its route rule and the lane chunk. The
+// rule itself and the decode GEMV's instantiation for a token count are in wo_host.h. Plain
 // functions of their arguments, so that a stand-alone host program can run them on the CPU.
 // Internal header.
 #pragma once
 
 #include <stdint.h>
+
+#include "wo_host.h"
 
 namespace tao {
 
@@ -18,14 +21,8 @@ static inline int fp6_format_of(int64_t ebits, int64_t mbits) {
 // dwords of native storage per row of K codes (K % 32 == 0): K * 6 / 32
 static inline int64_t fp6_row_dwords(int64_t K) { return K / 32 * 6; }
 
-enum { kFp6RouteAuto = 0, kFp6RouteGemv = 1, kFp6RouteDequantMm = 2, kFp6RouteMfma = 3 };
-
-// The most tokens one GEMV launch serves (fp6wo_gemv_kernel<*, 8, 1, *>); a forced GEMV beyond it
-// is a sequence of launches over 8-token pieces.
-constexpr int kFp6GemvMaxM = 8;
-
-// Two built-in routes: the decode GEMV, and the dequantizer into a temporary + the bf16 matmul. force:
-// tao_tune_fp6's route (kFp6Route*); max_gemv_m > 0 moves the boundary (tao_tune_fp6 too).
+// Two built-in routes (wo_route): the decode GEMV, and the dequantizer into a temporary + the bf16
+// matmul. force: tao_tune_fp6's route (kWoRoute*); max_gemv_m > 0 moves the boundary (tao_tune_fp6 too).
 // The built-in boundary is measured (experiments/bench_fp6.py --boundary,
 // profiles/fp6_bench_boundary.jsonl, both routes forced, e3m2; e2m3 is within 1 %; us GEMV vs
 // dequantize + matmul at 4096^2, 6144 x 4096, 14336 x 4096, 4096 x 14336): at M = 8 the GEMV's
@@ -37,27 +34,8 @@ constexpr int kFp6GemvMaxM = 8;
 // matmul goes to the MFMA GEMM instead. A forced route still wins, and max_gemv_m still moves the
 // GEMV boundary. The built-in rule does not name it yet (measurements: DESIGN §4.20).
 constexpr int kFp6GemvDefaultM = 8;
-static inline int fp6_route(int64_t M, int64_t N, int64_t K, int force, int max_gemv_m,
-                            int mfma = 0) {
-  (void)N;
-  (void)K;
-  if (force == kFp6RouteGemv || force == kFp6RouteDequantMm) return force;
-  const int64_t lim = max_gemv_m > 0 ? max_gemv_m : kFp6GemvDefaultM;
-  if (M <= lim) return kFp6RouteGemv;
-  return mfma ? kFp6RouteMfma : kFp6RouteDequantMm;
-}
-
-// Tokens per lane set (MT) and rows per wave (RPW) of the GEMV launch that serves m <= 8 tokens:
-// V = MT * RPW partials per lane, 4 at one token and 8 beyond, as nf4_host.h and the byte-weight
-// GEMVs keep it.
-struct Fp6GemvTile {
-  int mt, rpw;
-};
-static inline Fp6GemvTile fp6_gemv_tile(int m) {
-  if (m <= 1) return {1, 4};
-  if (m <= 2) return {2, 4};
-  if (m <= 4) return {4, 2};
-  return {8, 1};
+static inline int fp6_route(int64_t M, int force, int max_gemv_m, int mfma) {
+  return wo_route(M, force, max_gemv_m, kFp6GemvDefaultM, mfma != 0);
 }
 
 // 32-code groups per lane chunk: 1 (24 B, three 8-B loads, a 2048-code wave slice) unless the

@@ -90,6 +90,7 @@ __global__ __launch_bounds__(512) void fp8wo_gemv_kernel(
     }
   }
 
+  // the tail, written out in each GEMV kernel (tao_gemv.h, "the plain weight-only GEMVs' tail")
   float v[V];
 #pragma unroll
   for (int r = 0; r < RPW; ++r)

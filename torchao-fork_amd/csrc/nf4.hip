@@ -1,7 +1,8 @@
 // NF4 (QLoRA) weight-only linear: block quantizer, flat dequantizer and the decode GEMV behind
 // tao_nf4_quantize_blocks_bf16, tao_nf4_dequant_bf16 and tao_nf4_linear_bf16
-// (torchao/dtypes/nf4tensor.py). The format's arithmetic is in nf4_block.h; the route rule and
-// the GEMV's tile choice are in nf4_host.h.
+// (torchao/dtypes/nf4tensor.py). The format's arithmetic is in nf4_block.h, the measured boundary
+// of its route rule in nf4_host.h; the rule, the GEMV's tile, launch and tail are the weight-only
+// front end's (wo_host.h, tao_gemv.h).
 //
 // Replaces F.linear(x, weight.to(x.dtype)) of the reference's LinearNF4 (torchao/dtypes/
 // nf4tensor.py:1037-1048), which rebuilds a bf16 copy of W with about ten eager torch ops on every
@@ -216,6 +217,7 @@ __global__ __launch_bounds__(512) void nf4_gemv_kernel(
     }
   }
 
+  // the tail, written out in each GEMV kernel (tao_gemv.h, "the plain weight-only GEMVs' tail")
   float v[V];
 #pragma unroll
   for (int r = 0; r < RPW; ++r)
@@ -236,20 +238,14 @@ __global__ __launch_bounds__(512) void nf4_gemv_kernel(
   }
 }
 
-// wk, g: 0 = the default shape, Wk = min(S, 8) waves along K and as many row groups as fit 8 waves
-// (M > 1), one row group at M == 1: the byte-weight GEMVs' choice (tao_gemv.h wo8_gemv).
+// wk, g: tao_tune_nf4's, 0 = the default shape (tao_gemv.h wo_gemv_launch)
 template <int MT, int RPW>
 int nf4_gemv_launch(const uint16_t* x, const uint8_t* w, const int8_t* qs, const uint16_t* qf,
                     const uint16_t* mean, const uint16_t* levels, const uint16_t* bias,
                     uint16_t* y, int M, int N, int K, hipStream_t stream, int wk, int g) {
-  const GemvLaunchShape sh =
-      gemv_launch_shape(K / 32, wk > 0 ? wk : 8, g > 0 ? g : (MT == 1 ? 1 : 8));
-  const int rows_per_wg = sh.G * RPW;
-  const int grid = (N + rows_per_wg - 1) / rows_per_wg;
-  const size_t lds = (size_t)sh.G * sh.Wk * RPW * MT * sizeof(float);
-  launch(nf4_gemv_kernel<MT, RPW>, dim3(grid), dim3(64 * sh.Wk * sh.G), lds, stream, x,
-         reinterpret_cast<const uint4*>(w), qs, qf, mean, levels, bias, y, M, N, K, sh.Wk, sh.G,
-         sh.S);
+  const WoGemvLaunch L = wo_gemv_launch(K / 32, N, MT, RPW, wk, g);
+  launch(nf4_gemv_kernel<MT, RPW>, dim3(L.grid), dim3(L.threads), L.lds, stream, x,
+         reinterpret_cast<const uint4*>(w), qs, qf, mean, levels, bias, y, M, N, K, L.Wk, L.G, L.S);
   return check_launch("nf4_gemv_kernel");
 }
 
@@ -302,7 +298,9 @@ extern "C" int tao_nf4_dequant_bf16(const uint8_t* codes, const int8_t* qscalers
 }
 
 extern "C" int tao_nf4_linear_route(int64_t M, int64_t N, int64_t K) {
-  return tao::nf4_route(M, N, K, tao::tuning().nf4_route, tao::tuning().nf4_max_m);
+  (void)N;
+  (void)K;
+  return tao::nf4_route(M, tao::tuning().nf4.route, tao::tuning().nf4.max_m);
 }
 
 extern "C" int tao_nf4_linear_bf16(const uint16_t* x, const uint8_t* codes,
@@ -325,48 +323,19 @@ extern "C" int tao_nf4_linear_bf16(const uint16_t* x, const uint8_t* codes,
   TAO_CHECK_ALIGN(y, 2, "y");
   if (bias != nullptr) TAO_CHECK_ALIGN(bias, 2, "bias");
   const hipStream_t st = as_stream(stream);
-  const Tuning& tu = tuning();
-  // 8-token pieces: one launch wherever the route rule chose the GEMV, a sequence of them where
-  // a caller forces it beyond (or calls this entry on a shape the op would dequantize)
-  for (int64_t m0 = 0; m0 < M; m0 += kNf4GemvMaxM) {
-    const int m = (int)(M - m0 < kNf4GemvMaxM ? M - m0 : kNf4GemvMaxM);
-    const uint16_t* xm = x + m0 * K;
-    uint16_t* ym = y + m0 * N;
-    const Nf4GemvTile tile = nf4_gemv_tile(m);
-    int rc;
-#define TAO_NF4(MT, RPW)                                                                         \
-  rc = nf4_gemv_launch<MT, RPW>(xm, codes, qscalers, qfactor, mean, levels, bias, ym, m, (int)N, \
-                                (int)K, st, tu.nf4_wk, tu.nf4_g)
-    if (tile.mt == 1) {
-      if (tu.nf4_rpw == 2) TAO_NF4(1, 2);
-      else if (tu.nf4_rpw == 8) TAO_NF4(1, 8);
-      else TAO_NF4(1, 4);
-    } else if (tile.mt == 2) TAO_NF4(2, 4);
-    else if (tile.mt == 4) TAO_NF4(4, 2);
-    else TAO_NF4(8, 1);
-#undef TAO_NF4
-    if (rc != TAO_OK) return rc;
-  }
-  return TAO_OK;
+  const WoTune& tu = tuning().nf4;
+  return for_gemv_pieces(x, y, M, N, K, [&](const uint16_t* xm, uint16_t* ym, int m) {
+    return dispatch_gemv_tile(m, tu.rpw, [&](auto mt, auto rpw) {
+      return nf4_gemv_launch<decltype(mt)::value, decltype(rpw)::value>(
+          xm, codes, qscalers, qfactor, mean, levels, bias, ym, m, (int)N, (int)K, st, tu.wk, tu.g);
+    });
+  });
 }
 
 extern "C" int tao_tune_nf4(int route, int max_gemv_m, int rows_per_wave, int waves_k,
                             int row_groups) {
   using namespace tao;
-  TAO_CHECK_ARG(route >= kNf4RouteAuto && route <= kNf4RouteDequantMm,
-                "tune: nf4 route must be 0 (auto), 1 (gemv) or 2 (dequant + mm)");
-  TAO_CHECK_ARG(max_gemv_m >= 0, "tune: nf4 max_gemv_m must be >= 0");
-  TAO_CHECK_ARG(rows_per_wave == 0 || rows_per_wave == 2 || rows_per_wave == 4 ||
-                    rows_per_wave == 8,
-                "tune: nf4 rows_per_wave must be 0, 2, 4 or 8");
-  TAO_CHECK_ARG(waves_k >= 0 && waves_k <= 8, "tune: nf4 waves_k must be in [0, 8]");
-  TAO_CHECK_ARG(row_groups >= 0 && row_groups <= 8, "tune: nf4 row_groups must be in [0, 8]");
-  TAO_CHECK_ARG(waves_k * row_groups <= 8, "tune: nf4 waves_k * row_groups must be <= 8");
-  Tuning& tu = tuning();
-  tu.nf4_route = route;
-  tu.nf4_max_m = max_gemv_m;
-  tu.nf4_rpw = rows_per_wave;
-  tu.nf4_wk = waves_k;
-  tu.nf4_g = row_groups;
+  if (int rc = check_wo_tune("nf4", route, max_gemv_m, rows_per_wave, waves_k, row_groups)) return rc;
+  tuning().nf4 = {route, max_gemv_m, rows_per_wave, waves_k, row_groups};
   return TAO_OK;
 }

@@ -9,6 +9,7 @@
 #include "../../include/torchao_mi355x.h"
 #include "../../include/torchao_mi355x_llama.h"
 #include "../../include/torchao_mi355x_tune.h"
+#include "wo_host.h"
 
 namespace tao {
 
@@ -55,6 +56,29 @@ int graph_workspace_count();
 // default instead.
 bool fence_free_validated();
 
+// What tao_tune_nf4, tao_tune_fp6 and tao_tune_uintx share: the linear's route (kWoRoute*,
+// wo_host.h) and GEMV boundary, and the GEMV's launch shape (rows per wave at one token, waves
+// along K, row groups).
+struct WoTune {
+  int route = 0, max_m = 0, rpw = 0, wk = 0, g = 0;
+};
+// The checks of those five arguments, in the order the hooks report them; fmt names the format in
+// the messages ("nf4", ...). The hooks check their own arguments after it and assign last, so a
+// refused call changes nothing.
+static inline int check_wo_tune(const char* fmt, int route, int max_gemv_m, int rows_per_wave,
+                                int waves_k, int row_groups) {
+  TAO_CHECK_ARG(route >= kWoRouteAuto && route <= kWoRouteDequantMm,
+                "tune: %s route must be 0 (auto), 1 (gemv) or 2 (dequant + mm)", fmt);
+  TAO_CHECK_ARG(max_gemv_m >= 0, "tune: %s max_gemv_m must be >= 0", fmt);
+  TAO_CHECK_ARG(rows_per_wave == 0 || rows_per_wave == 2 || rows_per_wave == 4 ||
+                    rows_per_wave == 8,
+                "tune: %s rows_per_wave must be 0, 2, 4 or 8", fmt);
+  TAO_CHECK_ARG(waves_k >= 0 && waves_k <= 8, "tune: %s waves_k must be in [0, 8]", fmt);
+  TAO_CHECK_ARG(row_groups >= 0 && row_groups <= 8, "tune: %s row_groups must be in [0, 8]", fmt);
+  TAO_CHECK_ARG(waves_k * row_groups <= 8, "tune: %s waves_k * row_groups must be <= 8", fmt);
+  return TAO_OK;
+}
+
 struct Tuning {
   int rpw = 0, wk = 0, g = 0, occ = 0;           // int4 GEMV (tao_tune_int4_gemv)
   int xlds = 0, norm = 0;                        // int4 GEMV x staging / deferred norm
@@ -84,14 +108,9 @@ struct Tuning {
   int sf_loaders = 0;  // single-fetch GEMMs: loader waves (0 built-in, 1 off, 2 on, 3 eight)
   int attn_prefill_nw = 0;  // prefill attention: waves per query block (0 built-in, 1, 2, 4)
   int gemv_lds = 0;  // int4 GEMV: minimum dynamic LDS per workgroup (caps residency; tao_tune_int4_lds)
-  int nf4_route = 0, nf4_max_m = 0;              // NF4 linear route and GEMV boundary (tao_tune_nf4)
-  int nf4_rpw = 0, nf4_wk = 0, nf4_g = 0;        // NF4 GEMV launch shape (tao_tune_nf4)
-  int fp6_route = 0, fp6_max_m = 0;              // FP6 linear route and GEMV boundary (tao_tune_fp6)
-  int fp6_rpw = 0, fp6_wk = 0, fp6_g = 0;        // FP6 GEMV launch shape (tao_tune_fp6)
+  WoTune nf4, fp6, uintx;                        // tao_tune_nf4 / tao_tune_fp6 / tao_tune_uintx
   int fp6_groups = 0;                            // FP6 GEMV 32-code groups per lane chunk
   int fp6_mfma = 0;                              // FP6 linear: 1 = MFMA GEMM where the rule says dequant + mm
-  int uintx_route = 0, uintx_max_m = 0;          // uintx linear route and GEMV boundary (tao_tune_uintx)
-  int uintx_rpw = 0, uintx_wk = 0, uintx_g = 0;  // uintx GEMV launch shape (tao_tune_uintx)
   int uintx_xlds = 0;                            // uintx GEMV x: 0 built-in, 1 through L1, 2 staged in LDS
   int uintx_unit = 0;                            // uintx GEMV bytes of a shard piece per lane unit
   int uintx_mfma = 0;                            // uintx linear: 1 = MFMA GEMM where the rule says dequant + mm

@@ -1,5 +1,6 @@
 // The GEMV skeleton shared by the decode kernels (int4_gemv.hip, int8_gemv.hip, int8_dyn.hip,
-// fp8_gemv.hip, scaled_gemv.h). Internal header.
+// fp8_gemv.hip, scaled_gemv.h) and the weight-only GEMVs of the sub-byte formats (nf4.hip, fp6.hip,
+// uintx.hip). Internal header.
 //
 // Work decomposition, common to all of them:
 //   * a "slice" is one 1-KiB wave load of one weight row: 64 lanes x 16 B (1024 k of int8 / fp8
@@ -14,9 +15,18 @@
 //     row-pair epilogue (DecodeFuse, pair_epilogue); all five entries pick the
 //     epilogue's instantiation through dispatch_epilogue.
 // Each file keeps what is its own: the per-slice arithmetic, the prologue's LDS layout and its
-// entries' argument checks. The byte-weight (int8 / fp8) weight-only kernels share
-//   * at M >= 1 the launcher and M dispatcher of the plain GEMVs (wo8_gemv; one __global__
-//     function per format, see there);
+// entries' argument checks. The plain weight-only GEMVs (int8, fp8, NF4, FP6, uintx: x [M][K] bf16,
+// M <= 8 per launch, optional bias) are one __global__ function per format, since their main
+// loops do not survive a shared body (see wo8_launch), around one front end:
+//   * the route rule and the (MT, RPW) tile of a token count (wo_host.h), picked as compile-time
+//     constants by dispatch_gemv_tile;
+//   * the launch of a tile: wo_gemv_launch (slices, waves, row groups, grid, reduction LDS);
+//   * the loop over 8-token pieces of a longer forced GEMV: for_gemv_pieces.
+// The kernels' tail (reduce, combine, the format's output, bias, store) is alike too, but written
+// out in each (see "the plain weight-only GEMVs' tail"). A further weight-only format supplies its
+// kernel (chunk arithmetic and that tail), its measured default boundary and its weight checks ("The weight-only GEMV front end").
+// The byte-weight (int8 / fp8) weight-only kernels share beyond that
+//   * at M >= 1 the launcher of the plain GEMVs (wo8_gemv; see there);
 //   * at M == 1 with the decode fusions one kernel and one host path: wo8_decode_kernel over a
 //     format policy (Int8Decode in int8_gemv.hip, Fp8Decode in fp8_gemv.hip: the chunk arithmetic,
 //     whether tail lanes skip it, the scale type and the final rounding), wo8_decode_shape (the
@@ -123,6 +133,57 @@ static inline GemvLaunchShape gemv_launch_shape(int nchunk, int wk, int g) {
   return {S, Wk, g};
 }
 
+// The launch of a plain weight-only GEMV of tile (mt, rpw) over rows of nchunk lane chunks: wk
+// waves along K (0 = min(S, 8)) and g row groups (0 = one at one token, otherwise as many as fit 8
+// waves), the grid over N rows, and the reduction's red[G][Wk][rpw * mt] floats of LDS. The one
+// place these defaults live: the tile sweeps behind them are with wo8_gemv.
+struct WoGemvLaunch {
+  int S, Wk, G, grid, threads;
+  size_t lds;
+};
+static inline WoGemvLaunch wo_gemv_launch(int nchunk, int N, int mt, int rpw, int wk, int g) {
+  const GemvLaunchShape sh =
+      gemv_launch_shape(nchunk, wk > 0 ? wk : 8, g > 0 ? g : (mt == 1 ? 1 : 8));
+  const int rows_per_wg = sh.G * rpw;
+  return {sh.S, sh.Wk, sh.G, (N + rows_per_wg - 1) / rows_per_wg, 64 * sh.Wk * sh.G,
+          (size_t)sh.G * sh.Wk * rpw * mt * sizeof(float)};
+}
+
+// The one switch over the GEMV's tile: f is called with MT and RPW of wo_gemv_tile(m) as
+// compile-time constants, rows per wave replaced by tuned_rpw (2 or 8) at one token,
+//   dispatch_gemv_tile(m, tu.rpw, [&](auto mt, auto rpw) { return launch<mt(), rpw()>(...); });
+// The cases are the instances every format compiles; which m takes which is wo_gemv_tile's.
+template <typename F>
+static inline int dispatch_gemv_tile(int m, int tuned_rpw, F&& f) {
+  WoGemvTile t = wo_gemv_tile(m);
+  if (t.mt == 1 && (tuned_rpw == 2 || tuned_rpw == 8)) t.rpw = tuned_rpw;
+#define TAO_TILE(MT, RPW) \
+  case MT * 16 + RPW: return f(std::integral_constant<int, MT>{}, std::integral_constant<int, RPW>{})
+  switch (t.mt * 16 + t.rpw) {
+    TAO_TILE(1, 2);
+    TAO_TILE(1, 8);
+    TAO_TILE(2, 4);
+    TAO_TILE(4, 2);
+    TAO_TILE(8, 1);
+    default: return f(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
+  }
+#undef TAO_TILE
+}
+
+// A GEMV of M tokens as launches over pieces of at most 8 (kWoGemvMaxM): one launch wherever the
+// route rule chose the GEMV, a sequence of them where a caller forces it beyond (or calls the
+// entry on a shape the op would dequantize). f(x, y, m) launches one piece; the first non-zero
+// status ends the loop.
+template <typename F>
+static inline int for_gemv_pieces(const uint16_t* x, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                                  F&& f) {
+  for (int64_t m0 = 0; m0 < M; m0 += kWoGemvMaxM) {
+    const int m = (int)(M - m0 < kWoGemvMaxM ? M - m0 : kWoGemvMaxM);
+    if (const int rc = f(x + m0 * K, y + m0 * N, m)) return rc;
+  }
+  return TAO_OK;
+}
+
 // ---- cross-wave combine ----------------------------------------------------------------------------
 // v0 is this lane's v[0] after wave_reduce_scatter<V>: the wave's total of value lane >> (6 - T)
 // in the owner lanes (T = log2 V). Wk == 1: the owners write. Wk > 1: the owners park their
@@ -152,6 +213,18 @@ __device__ __forceinline__ WgTotal<T> wg_combine(T v0, T* red, int lane, int wk,
   }
   return t;
 }
+
+// ---- the plain weight-only GEMVs' tail ------------------------------------------------------------
+// The five kernels (int8wo, fp8wo, nf4, fp6wo, uintx) end alike: acc[RPW][MT] flattened into
+// v[RPW * MT], wave_reduce_scatter, wg_combine, and in the writing lane of output (n, m), after
+// the n < N && m < M test,
+//   y[m][n] = bf16(out)  or, with a bias,  bf16(bf16(out) + bias[n])
+// where out is the format's bf16 output (its roundings and row scale). The tail stays written out
+// in each kernel: a __device__ __forceinline__ gemv_tail<MT, RPW>(acc, ..., out) with the format's
+// `out` as a lambda compiled every instance of all five to the same instructions and registers
+// except the Wk > 1 test of wg_combine, which came out as s_cmp_lt_i32 Wk, 2 / s_cbranch_scc1 in
+// place of s_cmp_gt_i32 Wk, 1 / s_cbranch_scc0. Only byte-identical machine code was to be taken
+// (experiments/asm_same.py), so it was not.
 
 // ---- row-pair epilogues (M == 1) -------------------------------------------------------------------
 // Agent-scope (sc1) store: COH stores are read by other workgroups of the same launch
@@ -238,37 +311,31 @@ __device__ __forceinline__ float sumsq_piece(uint4 v, bool ok, float ss) {
 // M > 1 (int8 <4, 2>: 7 of the slice's 12 loads issued before the first wait instead of 10) and
 // measured 3-19% slower at M = 4, so it was not kept.
 // A Kernel describes what to launch: scale_t, kernel<MT, RPW>() and the name check_launch records.
-// wk, g: 0 = the default shape, Wk = min(S, 8) and as many row groups as fit 8 waves
+// wk, g: 0 = the default shape (wo_gemv_launch)
 template <typename Kernel, int MT, int RPW>
 static int wo8_launch(const uint16_t* x, const void* w, const typename Kernel::scale_t* scale,
                       const uint16_t* bias, uint16_t* y, int M, int N, int K, hipStream_t stream,
-                      int wk = 0, int g = 0) {
-  const GemvLaunchShape sh = gemv_launch_shape(K / 16, wk > 0 ? wk : 8, g > 0 ? g : 8);
-  const int rows_per_wg = sh.G * RPW;
-  const int grid = (N + rows_per_wg - 1) / rows_per_wg;
-  const size_t lds = (size_t)sh.G * sh.Wk * RPW * MT * sizeof(float);
-  launch(Kernel::template kernel<MT, RPW>(), dim3(grid), dim3(64 * sh.Wk * sh.G), lds, stream, x,
-         reinterpret_cast<const uint4*>(w), scale, bias, y, M, N, K, sh.Wk, sh.G, sh.S);
+                      int wk, int g) {
+  const WoGemvLaunch L = wo_gemv_launch(K / 16, N, MT, RPW, wk, g);
+  launch(Kernel::template kernel<MT, RPW>(), dim3(L.grid), dim3(L.threads), L.lds, stream, x,
+         reinterpret_cast<const uint4*>(w), scale, bias, y, M, N, K, L.Wk, L.G, L.S);
   return check_launch(Kernel::name);
 }
 
 // M == 1: rpw rows per wave (0 = 4), wk waves along K (0 = min(S, 8)), g row groups (0 = 1):
 // experiments/sweep_int8.py, profiles/r1_sweep_int8.jsonl: 4 rows per wave, Wk = min(S, 8), G = 1
 // is within 1% of the per-shape best on every Llama-3-8B linear (the head 77.8 -> 72.7 us).
-// M > 1 keeps V = RPW * MT = 8 partials per lane on the default shape.
+// M > 1 keeps V = RPW * MT = 8 partials per lane on the default shape: the byte-weight hooks
+// (tao_tune_int8_gemv, tao_tune_fp8_gemv) shape the one-token launch only.
 template <typename Kernel>
 static int wo8_gemv(const uint16_t* x, const void* w, const typename Kernel::scale_t* scale,
                     const uint16_t* bias, uint16_t* y, int M, int N, int K, hipStream_t stream,
                     int rpw, int wk, int g) {
-  if (M <= 1) {
-    if (g <= 0) g = 1;
-    if (rpw == 2) return wo8_launch<Kernel, 1, 2>(x, w, scale, bias, y, M, N, K, stream, wk, g);
-    if (rpw == 8) return wo8_launch<Kernel, 1, 8>(x, w, scale, bias, y, M, N, K, stream, wk, g);
-    return wo8_launch<Kernel, 1, 4>(x, w, scale, bias, y, M, N, K, stream, wk, g);
-  }
-  if (M <= 2) return wo8_launch<Kernel, 2, 4>(x, w, scale, bias, y, M, N, K, stream);
-  if (M <= 4) return wo8_launch<Kernel, 4, 2>(x, w, scale, bias, y, M, N, K, stream);
-  return wo8_launch<Kernel, 8, 1>(x, w, scale, bias, y, M, N, K, stream);
+  return dispatch_gemv_tile(M, rpw, [&](auto mt, auto r) {
+    constexpr int MT = decltype(mt)::value, RPW = decltype(r)::value;
+    return wo8_launch<Kernel, MT, RPW>(x, w, scale, bias, y, M, N, K, stream, MT == 1 ? wk : 0,
+                                       MT == 1 ? g : 0);
+  });
 }
 
 // ---- byte-weight weight-only decode (M == 1 with the fusions): one kernel, one host path -------

@@ -84,6 +84,40 @@ std::optional<Tensor> bf16_bias(const std::optional<Tensor>& bias) {
   return bias->to(at::kBFloat16).contiguous();
 }
 
+// ---- the linears with a route rule (NF4, FP6, uintx) --------------------------------------------
+// What nf4_linear, fp6_weight_only_linear and uintx_weight_only_linear do around their weight
+// checks, in two parts so that each op's checks fire in its own order: check_wo_x before them,
+// wo_routed_linear after. The format supplies its op name for the messages and three callables:
+//   route(M)                  tao_*_linear_route for this weight (2 = dequantize + matmul);
+//   dequant()                 the weight as [N, K] bf16 in a temporary of the caching allocator;
+//   launch(x2, bias, y, M)    the C entry (GEMV or MFMA GEMM) on raw pointers, status checked.
+void check_wo_x(const Tensor& x, const char* op) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, op, " (HIP) needs bf16 x, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1, op, ": x must have at least one dimension");
+}
+template <class Route, class Dequant, class Launch>
+Tensor wo_routed_linear(const char* op, const Tensor& x, int64_t N, int64_t K,
+                        const std::optional<Tensor>& bias, Route route, Dequant dequant,
+                        Launch launch) {
+  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
+  TORCH_CHECK(!bias.has_value() || bias->numel() == N, op, ": bias must have N = ", N, " elements");
+  check_device(x, bias, "bias");
+  const Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  if (M > 0 && N > 0 && route(M) == 2) {
+    // the reference's own form with a fast dequantizer: W^ into a temporary, then the bf16
+    // matmul; the bias is a second rounding, as on the other routes
+    Tensor y = at::linear(x2, dequant());
+    if (b) y = y + *b;
+    return y.reshape(out_shape(x, N));
+  }
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  launch(cptr<uint16_t>(x2), b ? cptr<uint16_t>(*b) : nullptr, mptr<uint16_t>(y), M);
+  return y.reshape(out_shape(x, N));
+}
+
 // ---- int4 weight-only (ops.py _int4_linear_cuda) ----------------------------------------------
 Tensor int4_weight_only_linear(const Tensor& x, const Tensor& packed_w, const Tensor& sz,
                                int64_t group_size, const std::optional<Tensor>& bias) {
@@ -1051,37 +1085,22 @@ Tensor nf4_dequantize(const Tensor& codes, const Tensor& qscalers, const Tensor&
 Tensor nf4_linear(const Tensor& x, const Tensor& codes, const Tensor& qscalers,
                   const Tensor& qfactor, const Tensor& mean, const Tensor& levels, int64_t N,
                   const std::optional<Tensor>& bias) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "nf4_linear (HIP) needs bf16 x, got ",
-              x.scalar_type());
-  TORCH_CHECK(x.dim() >= 1, "nf4_linear: x must have at least one dimension");
+  check_wo_x(x, "nf4_linear");
   TORCH_CHECK(N >= 0, "nf4_linear: N must be non-negative, got ", N);
-  const int64_t K = x.size(-1);
+  const int64_t K = x.size(-1);  // the weight is flat: K is x's
   TORCH_CHECK(K > 0 && K % 64 == 0, "nf4_linear: K (", K,
               ") must be a positive multiple of the block size 64");
   check_device(x, codes, "codes");
   const Nf4Parts p = check_nf4(codes, qscalers, qfactor, mean, levels, N * K, "nf4_linear");
-  TORCH_CHECK(!bias.has_value() || bias->numel() == N, "nf4_linear: bias must have N = ", N,
-              " elements");
-  check_device(x, bias, "bias");
-  const Tensor x2 = rows_of(x, K);
-  const int64_t M = x2.size(0);
-  const std::optional<Tensor> b = bf16_bias(bias);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  if (M > 0 && N > 0 && tao_nf4_linear_route(M, N, K) == 2) {
-    // the reference's own form with a fast dequantizer: W^ into a temporary of the caching
-    // allocator, then the bf16 matmul; the bias is a second rounding, as on the other route
-    const Tensor w = nf4_dequantize_flat(p, N * K).reshape({N, K});
-    Tensor y = at::linear(x2, w);
-    if (b) y = y + *b;
-    return y.reshape(out_shape(x, N));
-  }
-  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
-  check_rc(tao_nf4_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(p.codes), cptr<int8_t>(p.qs),
-                               cptr<uint16_t>(p.qf), cptr<uint16_t>(p.mean),
-                               cptr<uint16_t>(p.levels), b ? cptr<uint16_t>(*b) : nullptr,
-                               mptr<uint16_t>(y), M, N, K, stream_of(x)),
-           "tao_nf4_linear_bf16");
-  return y.reshape(out_shape(x, N));
+  return wo_routed_linear(
+      "nf4_linear", x, N, K, bias, [&](int64_t M) { return tao_nf4_linear_route(M, N, K); },
+      [&] { return nf4_dequantize_flat(p, N * K).reshape({N, K}); },
+      [&](const uint16_t* x2, const uint16_t* b, uint16_t* y, int64_t M) {
+        check_rc(tao_nf4_linear_bf16(x2, cptr<uint8_t>(p.codes), cptr<int8_t>(p.qs),
+                                     cptr<uint16_t>(p.qf), cptr<uint16_t>(p.mean),
+                                     cptr<uint16_t>(p.levels), b, y, M, N, K, stream_of(x)),
+                 "tao_nf4_linear_bf16");
+      });
 }
 
 // ---- FP6 weight-only (torchao/dtypes/floatx/floatx_tensor_core_layout.py; csrc/fp6.hip) ---------
@@ -1153,36 +1172,21 @@ Tensor fp6_dequantize(const Tensor& codes, const Tensor& scale, int64_t ebits, i
 Tensor fp6_weight_only_linear(const Tensor& x, const Tensor& codes, const Tensor& scale,
                               int64_t ebits, int64_t mbits, const std::optional<Tensor>& bias) {
   check_fp6_format(ebits, mbits, "fp6_weight_only_linear");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "fp6_weight_only_linear (HIP) needs bf16 x, got ",
-              x.scalar_type());
-  TORCH_CHECK(x.dim() >= 1, "fp6_weight_only_linear: x must have at least one dimension");
+  check_wo_x(x, "fp6_weight_only_linear");
   check_device(x, codes, "codes");
   const Fp6Weight p = check_fp6_weight(codes, scale, "fp6_weight_only_linear");
   const int64_t N = p.N, K = p.K;
   TORCH_CHECK(K > 0 && K % 64 == 0, "fp6_weight_only_linear: K (", K,
               ") must be a positive multiple of 64");
-  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
-  TORCH_CHECK(!bias.has_value() || bias->numel() == N, "fp6_weight_only_linear: bias must have N = ",
-              N, " elements");
-  check_device(x, bias, "bias");
-  const Tensor x2 = rows_of(x, K);
-  const int64_t M = x2.size(0);
-  const std::optional<Tensor> b = bf16_bias(bias);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  if (M > 0 && N > 0 && tao_fp6_linear_route(M, N, K) == 2) {
-    // W^ into a temporary of the caching allocator, then the bf16 matmul; the bias is a second
-    // rounding, as on the other route
-    const Tensor w = fp6_dequantize_checked(p, ebits, mbits);
-    Tensor y = at::linear(x2, w);
-    if (b) y = y + *b;
-    return y.reshape(out_shape(x, N));
-  }
-  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
-  check_rc(tao_fp6_linear_bf16(cptr<uint16_t>(x2), cptr<uint32_t>(p.codes),
-                               cptr<uint16_t>(p.scale), b ? cptr<uint16_t>(*b) : nullptr,
-                               mptr<uint16_t>(y), M, N, K, (int)ebits, (int)mbits, stream_of(x)),
-           "tao_fp6_linear_bf16");
-  return y.reshape(out_shape(x, N));
+  return wo_routed_linear(
+      "fp6_weight_only_linear", x, N, K, bias,
+      [&](int64_t M) { return tao_fp6_linear_route(M, N, K); },
+      [&] { return fp6_dequantize_checked(p, ebits, mbits); },
+      [&](const uint16_t* x2, const uint16_t* b, uint16_t* y, int64_t M) {
+        check_rc(tao_fp6_linear_bf16(x2, cptr<uint32_t>(p.codes), cptr<uint16_t>(p.scale), b, y, M,
+                                     N, K, (int)ebits, (int)mbits, stream_of(x)),
+                 "tao_fp6_linear_bf16");
+      });
 }
 
 // ---- MoE expert FFN over many tokens (torchao/prototype/moe_quant; csrc/moe_gemm.hip) -----------
@@ -1379,33 +1383,20 @@ Tensor uintx_weight_only_linear(const Tensor& x, const std::optional<Tensor>& s4
                                 const Tensor& scale, const Tensor& zero_point, int64_t bits,
                                 int64_t group, const std::optional<Tensor>& bias) {
   const char* op = "uintx_weight_only_linear";
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16, op, " (HIP) needs bf16 x, got ", x.scalar_type());
-  TORCH_CHECK(x.dim() >= 1, op, ": x must have at least one dimension");
+  check_wo_x(x, op);
   const UintxWeight p = check_uintx_weight(s4, s2, s1, scale, zero_point, bits, group, op);
   check_device(x, p.scale, "the weight");
   const int64_t N = p.N, K = p.K;
-  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
-  TORCH_CHECK(!bias.has_value() || bias->numel() == N, op, ": bias must have N = ", N, " elements");
-  check_device(x, bias, "bias");
-  const Tensor x2 = rows_of(x, K);
-  const int64_t M = x2.size(0);
-  const std::optional<Tensor> b = bf16_bias(bias);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  if (M > 0 && N > 0 && tao_uintx_linear_route_g(M, N, K, (int)bits, (int)group) == 2) {
-    // W^ into a temporary of the caching allocator, then the bf16 matmul; the bias is a second
-    // rounding, as on the other route
-    const Tensor w = uintx_dequantize_checked(p, bits, group);
-    Tensor y = at::linear(x2, w);
-    if (b) y = y + *b;
-    return y.reshape(out_shape(x, N));
-  }
-  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
-  check_rc(tao_uintx_linear_bf16(cptr<uint16_t>(x2), p.p4(), p.p2(), p.p1(),
-                                 cptr<uint16_t>(p.scale), cptr<int32_t>(p.zp),
-                                 b ? cptr<uint16_t>(*b) : nullptr, mptr<uint16_t>(y), M, N, K,
-                                 (int)bits, (int)group, stream_of(x)),
-           "tao_uintx_linear_bf16");
-  return y.reshape(out_shape(x, N));
+  return wo_routed_linear(
+      op, x, N, K, bias,
+      [&](int64_t M) { return tao_uintx_linear_route_g(M, N, K, (int)bits, (int)group); },
+      [&] { return uintx_dequantize_checked(p, bits, group); },
+      [&](const uint16_t* x2, const uint16_t* b, uint16_t* y, int64_t M) {
+        check_rc(tao_uintx_linear_bf16(x2, p.p4(), p.p2(), p.p1(), cptr<uint16_t>(p.scale),
+                                       cptr<int32_t>(p.zp), b, y, M, N, K, (int)bits, (int)group,
+                                       stream_of(x)),
+                 "tao_uintx_linear_bf16");
+      });
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // uintx (torch.uint1 .. torch.uint7) weight-only linear (UIntXWeightOnlyConfig): the decode GEMV
 // and the dequantizer behind tao_uintx_linear_bf16 and tao_uintx_dequant_bf16
-// (torchao/dtypes/uintx/uintx_layout.py). The route rule, the GEMV's tile and its lane unit are in
-// uintx_host.h. A third route, the UintxWO policy of gemm_mfma_kernel (gemm_mfma_policy.h), reads the
+// (torchao/dtypes/uintx/uintx_layout.py). The measured boundary of the route rule, the GEMV's lane
+// unit and where it reads x are in uintx_host.h; the rule, the GEMV's tile, launch and tail are the
+// weight-only front end's (wo_host.h, tao_gemv.h). A third route, the UintxWO policy of gemm_mfma_kernel (gemm_mfma_policy.h), reads the
 // same shards; tao_uintx_linear_bf16 reaches it through tao_tune_uintx_mfma until the route rule
 // names it.
 //
@@ -240,6 +241,7 @@ __global__ __launch_bounds__(512) void uintx_gemv_kernel(
     }
   }
 
+  // the tail, written out in each GEMV kernel (tao_gemv.h, "the plain weight-only GEMVs' tail")
   float v[V];
 #pragma unroll
   for (int r = 0; r < RPW; ++r)
@@ -270,16 +272,11 @@ struct UintxArgs {
   hipStream_t stream;
 };
 
-
-// wk, g: 0 = the default shape, Wk = min(S, 8) waves along K and as many row groups as fit 8 waves
-// (M > 1), one row group at M == 1: the byte-weight GEMVs' choice (tao_gemv.h wo8_gemv).
+// wk, g: tao_tune_uintx's, 0 = the default shape (tao_gemv.h wo_gemv_launch)
 template <int BITS, int MT, int RPW, int U, bool XL = false>
 int uintx_gemv_launch(const UintxArgs& a, int wk, int g) {
-  const GemvLaunchShape sh =
-      gemv_launch_shape(a.K / (8 * U), wk > 0 ? wk : 8, g > 0 ? g : (MT == 1 ? 1 : 8));
-  const int rows_per_wg = sh.G * RPW;
-  const int grid = (a.N + rows_per_wg - 1) / rows_per_wg;
-  size_t lds = (size_t)sh.G * sh.Wk * RPW * MT * sizeof(float);
+  const WoGemvLaunch L = wo_gemv_launch(a.K / (8 * U), a.N, MT, RPW, wk, g);
+  size_t lds = L.lds;
   if constexpr (XL) {
     lds = ((lds + 15) & ~(size_t)15) + uintx_x_lds_bytes(a.K, MT);
     // beyond 64 KiB a kernel's dynamic LDS has to be allowed first
@@ -287,31 +284,29 @@ int uintx_gemv_launch(const UintxArgs& a, int wk, int g) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return set_error(TAO_ERR_HIP, "uintx linear: %zu bytes of LDS for the staged x refused", lds);
   }
-  launch(uintx_gemv_kernel<BITS, MT, RPW, U, XL>, dim3(grid), dim3(64 * sh.Wk * sh.G), lds, a.stream,
-         a.x, a.s4, a.s2, a.s1, a.scale, a.zp, a.bias, a.y, a.M, a.N, a.K, a.group,
-         uintx_group_mul(a.group), sh.Wk, sh.G, sh.S);
+  launch(uintx_gemv_kernel<BITS, MT, RPW, U, XL>, dim3(L.grid), dim3(L.threads), lds, a.stream, a.x,
+         a.s4, a.s2, a.s1, a.scale, a.zp, a.bias, a.y, a.M, a.N, a.K, a.group,
+         uintx_group_mul(a.group), L.Wk, L.G, L.S);
   return check_launch("uintx_gemv_kernel");
 }
 
+// The format's own two cases on top of the shared tile switch: 8 rows per wave never meet a
+// 16-byte unit (uintx_unit caps it, so the <1, 8, 16> instances do not exist; the built-in 4 rows
+// stand in), and the 4 x 2 and 8 x 1 tiles have an instance with x staged in LDS (uintx_x_lds).
 template <int BITS, int U>
 int uintx_gemv(const UintxArgs& a, const Tuning& tu) {
-  const UintxGemvTile tile = uintx_gemv_tile(a.M);
-#define TAO_UINTX(MT, RPW) return uintx_gemv_launch<BITS, MT, RPW, U>(a, tu.uintx_wk, tu.uintx_g)
-  if (tile.mt == 1) {
-    if (tu.uintx_rpw == 2) TAO_UINTX(1, 2);
-    if constexpr (U < 16) {  // uintx_unit: 8 rows per wave never meet a 16-byte unit
-      if (tu.uintx_rpw == 8) TAO_UINTX(1, 8);
+  return dispatch_gemv_tile(a.M, tu.uintx.rpw, [&](auto mt, auto rpw) {
+    constexpr int MT = decltype(mt)::value, RPW = decltype(rpw)::value;
+    if constexpr (MT == 1 && RPW == 8 && U == 16) {
+      return uintx_gemv_launch<BITS, 1, 4, U>(a, tu.uintx.wk, tu.uintx.g);
+    } else {
+      if constexpr (MT >= 4) {
+        if (uintx_x_lds(a.K, BITS, a.M, tu.uintx_xlds))
+          return uintx_gemv_launch<BITS, MT, RPW, U, true>(a, tu.uintx.wk, tu.uintx.g);
+      }
+      return uintx_gemv_launch<BITS, MT, RPW, U>(a, tu.uintx.wk, tu.uintx.g);
     }
-    TAO_UINTX(1, 4);
-  }
-  if (tile.mt == 2) TAO_UINTX(2, 4);
-  if (uintx_x_lds(a.K, BITS, a.M, tu.uintx_xlds)) {
-    if (tile.mt == 4) return uintx_gemv_launch<BITS, 4, 2, U, true>(a, tu.uintx_wk, tu.uintx_g);
-    return uintx_gemv_launch<BITS, 8, 1, U, true>(a, tu.uintx_wk, tu.uintx_g);
-  }
-  if (tile.mt == 4) TAO_UINTX(4, 2);
-  TAO_UINTX(8, 1);
-#undef TAO_UINTX
+  });
 }
 
 // The one switch over the width: f is called with it as a compile-time constant.
@@ -378,7 +373,8 @@ extern "C" int tao_uintx_dequant_bf16(const uint8_t* s4, const uint8_t* s2, cons
 extern "C" int tao_uintx_linear_route_g(int64_t M, int64_t N, int64_t K, int bits,
                                         int group_size) {
   const tao::Tuning& tu = tao::tuning();
-  return tao::uintx_route(M, N, K, bits, tu.uintx_route, tu.uintx_max_m, tu.uintx_mfma, group_size);
+  (void)N;
+  return tao::uintx_route(M, K, bits, group_size, tu.uintx.route, tu.uintx.max_m, tu.uintx_mfma);
 }
 
 extern "C" int tao_uintx_linear_route(int64_t M, int64_t N, int64_t K, int bits) {
@@ -387,12 +383,12 @@ extern "C" int tao_uintx_linear_route(int64_t M, int64_t N, int64_t K, int bits)
 
 extern "C" int tao_uintx_gemv_unit(int64_t M, int64_t K, int bits) {
   const tao::Tuning& tu = tao::tuning();
-  const int64_t m = M < tao::kUintxGemvMaxM ? M : tao::kUintxGemvMaxM;
-  return tao::uintx_unit(K, bits, m, tu.uintx_unit, tu.uintx_rpw);
+  const int64_t m = M < tao::kWoGemvMaxM ? M : tao::kWoGemvMaxM;
+  return tao::uintx_unit(K, bits, m, tu.uintx_unit, tu.uintx.rpw);
 }
 
 extern "C" int tao_uintx_gemv_x_lds(int64_t M, int64_t K, int bits) {
-  const int64_t m = M < tao::kUintxGemvMaxM ? M : tao::kUintxGemvMaxM;
+  const int64_t m = M < tao::kWoGemvMaxM ? M : tao::kWoGemvMaxM;
   return tao::uintx_x_lds(K, bits, m, tao::tuning().uintx_xlds) ? 1 : 0;
 }
 
@@ -413,28 +409,23 @@ extern "C" int tao_uintx_linear_bf16(const uint16_t* x, const uint8_t* s4, const
   if (bias != nullptr) TAO_CHECK_ALIGN(bias, 2, "bias");
   const Tuning& tu = tuning();
   // the UintxWO policy of gemm_mfma_kernel where the rule names it (tao_tune_uintx_mfma)
-  if (uintx_route(M, N, K, bits, tu.uintx_route, tu.uintx_max_m, tu.uintx_mfma, group_size) ==
-      kUintxRouteMfma)
+  if (uintx_route(M, K, bits, group_size, tu.uintx.route, tu.uintx.max_m, tu.uintx_mfma) ==
+      kWoRouteMfma)
     return dispatch_uintx_bits(bits, [&](auto b) {
       return uintx_mm_launch<decltype(b)::value>(x, s4, s2, s1, scale, zero_point, bias, y, (int)M,
                                                  (int)N, (int)K, group_size, as_stream(stream));
     });
-  // 8-token pieces: one launch wherever the route rule chose the GEMV, a sequence of them where
-  // a caller forces it beyond (or calls this entry on a shape the op would dequantize)
-  for (int64_t m0 = 0; m0 < M; m0 += kUintxGemvMaxM) {
-    const int m = (int)(M - m0 < kUintxGemvMaxM ? M - m0 : kUintxGemvMaxM);
-    const UintxArgs a{x + m0 * K, s4,    s2,     s1,     scale,           zero_point,
-                      bias,       y + m0 * N, m, (int)N, (int)K, group_size, as_stream(stream)};
-    const int unit = uintx_unit(K, bits, m, tu.uintx_unit, tu.uintx_rpw);
-    const int rc = dispatch_uintx_bits(bits, [&](auto b) {
+  return for_gemv_pieces(x, y, M, N, K, [&](const uint16_t* xm, uint16_t* ym, int m) {
+    const UintxArgs a{xm,   s4, s2, s1,     scale,  zero_point,
+                      bias, ym, m,  (int)N, (int)K, group_size, as_stream(stream)};
+    const int unit = uintx_unit(K, bits, m, tu.uintx_unit, tu.uintx.rpw);
+    return dispatch_uintx_bits(bits, [&](auto b) {
       constexpr int B = decltype(b)::value;
       if (unit == 4) return uintx_gemv<B, 4>(a, tu);
       if (unit == 8) return uintx_gemv<B, 8>(a, tu);
       return uintx_gemv<B, 16>(a, tu);
     });
-    if (rc != TAO_OK) return rc;
-  }
-  return TAO_OK;
+  });
 }
 
 extern "C" int tao_tune_uintx_mfma(int on) {
@@ -446,26 +437,15 @@ extern "C" int tao_tune_uintx_mfma(int on) {
 extern "C" int tao_tune_uintx(int route, int max_gemv_m, int rows_per_wave, int waves_k,
                               int row_groups, int unit, int x_lds) {
   using namespace tao;
-  TAO_CHECK_ARG(route >= kUintxRouteAuto && route <= kUintxRouteDequantMm,
-                "tune: uintx route must be 0 (auto), 1 (gemv) or 2 (dequant + mm)");
-  TAO_CHECK_ARG(max_gemv_m >= 0, "tune: uintx max_gemv_m must be >= 0");
-  TAO_CHECK_ARG(rows_per_wave == 0 || rows_per_wave == 2 || rows_per_wave == 4 ||
-                    rows_per_wave == 8,
-                "tune: uintx rows_per_wave must be 0, 2, 4 or 8");
-  TAO_CHECK_ARG(waves_k >= 0 && waves_k <= 8, "tune: uintx waves_k must be in [0, 8]");
-  TAO_CHECK_ARG(row_groups >= 0 && row_groups <= 8, "tune: uintx row_groups must be in [0, 8]");
-  TAO_CHECK_ARG(waves_k * row_groups <= 8, "tune: uintx waves_k * row_groups must be <= 8");
+  if (int rc = check_wo_tune("uintx", route, max_gemv_m, rows_per_wave, waves_k, row_groups))
+    return rc;
   TAO_CHECK_ARG(unit == 0 || unit == 4 || unit == 8 || unit == 16,
                 "tune: uintx unit must be 0 (built-in), 4, 8 or 16 bytes");
   TAO_CHECK_ARG(x_lds >= 0 && x_lds <= 2,
                 "tune: uintx x_lds must be 0 (built-in), 1 (through L1) or 2 (staged in LDS)");
   Tuning& tu = tuning();
-  tu.uintx_xlds = x_lds;
-  tu.uintx_route = route;
-  tu.uintx_max_m = max_gemv_m;
-  tu.uintx_rpw = rows_per_wave;
-  tu.uintx_wk = waves_k;
-  tu.uintx_g = row_groups;
+  tu.uintx = {route, max_gemv_m, rows_per_wave, waves_k, row_groups};
   tu.uintx_unit = unit;
+  tu.uintx_xlds = x_lds;
   return TAO_OK;
 }

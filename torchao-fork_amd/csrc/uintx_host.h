@@ -1,10 +1,13 @@
-// Host-side arithmetic of the uintx (1- to 7-bit) weight-only linear (uintx.hip, torch_ops.cpp):
-// which shards a width has, which route serves a call, the decode GEMV's instantiation for a
-// token count and its lane unit. Plain functions of their arguments, so that a stand-alone host
-// program can run them on the CPU. Internal header.
+// Host-side arithmetic of the uintx (1- to 7-bit) weight-only linear (uintx.hip, torch_ops.cpp)
+// that is the format's own: which shards a width has, the measured boundary of its route rule,
+// what the MFMA GEMM serves, the decode GEMV's lane unit and where it reads x. The rule itself and
+// the GEMV's instantiation for a token count are in wo_host.h. Plain functions of their arguments,
+// so that a stand-alone host program can run them on the CPU. Internal header.
 #pragma once
 
 #include <stdint.h>
+
+#include "wo_host.h"
 
 namespace tao {
 
@@ -28,14 +31,8 @@ static inline uint32_t uintx_group_mul(int64_t group) {
   return (uint32_t)(((1LL << 32) + group - 1) / group);
 }
 
-enum { kUintxRouteAuto = 0, kUintxRouteGemv = 1, kUintxRouteDequantMm = 2, kUintxRouteMfma = 3 };
-
-// The most tokens one GEMV launch serves (uintx_gemv_kernel<*, 8, 1, *>); a forced GEMV beyond it
-// is a sequence of launches over 8-token pieces.
-constexpr int kUintxGemvMaxM = 8;
-
-// Two built-in routes: the decode GEMV, and the dequantizer into a temporary + the bf16 matmul. force:
-// tao_tune_uintx's route (kUintxRoute*); max_gemv_m > 0 moves the boundary (tao_tune_uintx too).
+// Two built-in routes (wo_route): the decode GEMV, and the dequantizer into a temporary + the bf16
+// matmul. force: tao_tune_uintx's route (kWoRoute*); max_gemv_m > 0 moves the boundary (tao_tune_uintx too).
 // The built-in boundary is measured per width (experiments/bench_uintx.py --boundary,
 // profiles/uintx_bench_boundary.jsonl, both routes forced at M = 4, 8, 12, 16; us GEMV vs
 // dequantize + matmul at 4096^2, 6144 x 4096, 14336 x 4096, 4096 x 14336). M = 8: uint1 13.5 /
@@ -65,25 +62,10 @@ static inline bool uintx_mfma_ok(int64_t K, int64_t group) {
 // that uintx_mfma_ok serves, goes to the MFMA GEMM instead. A forced route still wins, and
 // max_gemv_m still moves the GEMV boundary. The built-in rule does not name it yet (measurements
 // and the boundary they suggest: DESIGN 4.23.1).
-static inline int uintx_route(int64_t M, int64_t N, int64_t K, int bits, int force,
-                              int max_gemv_m, int mfma = 0, int64_t group = 0) {
-  (void)N;
-  if (force == kUintxRouteGemv || force == kUintxRouteDequantMm) return force;
-  const int64_t lim = max_gemv_m > 0 ? max_gemv_m : uintx_default_max_m(bits);
-  if (M <= lim) return kUintxRouteGemv;
-  return mfma && uintx_mfma_ok(K, group) ? kUintxRouteMfma : kUintxRouteDequantMm;
-}
-
-// Tokens per lane set (MT) and rows per wave (RPW) of the GEMV launch that serves m <= 8 tokens:
-// V = MT * RPW partials per lane, 4 at one token and 8 beyond, as fp6_host.h keeps it.
-struct UintxGemvTile {
-  int mt, rpw;
-};
-static inline UintxGemvTile uintx_gemv_tile(int m) {
-  if (m <= 1) return {1, 4};
-  if (m <= 2) return {2, 4};
-  if (m <= 4) return {4, 2};
-  return {8, 1};
+static inline int uintx_route(int64_t M, int64_t K, int bits, int64_t group, int force,
+                              int max_gemv_m, int mfma) {
+  return wo_route(M, force, max_gemv_m, uintx_default_max_m(bits),
+                  mfma && uintx_mfma_ok(K, group));
 }
 
 // Bytes of each shard stream per lane unit (U = 4, 8 or 16: 32, 64 or 128 codes); a row has
