@@ -564,6 +564,55 @@ int tao_fp6_linear_bf16(const uint16_t* x, const uint32_t* codes, const uint16_t
                         const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                         int ebits, int mbits, void* stream);
 
+/* ---- NVFP4 (csrc/nvfp4.hip; NVFP4InferenceConfig, torchao/prototype/mx_formats/nvfp4_tensor.py)
+ * A weight [N][K] is qdata uint8 [N][K / 2], e2m1 codes with element 2 j of a row in the HIGH
+ * nibble of byte j, one e4m3fn scale byte per 16 elements of a row, either row-major [N][K / 16]
+ * (swizzled = 0) or in the 128 x 4 "blocked" layout of cuBLAS (swizzled = 1: scale (r, c) at byte
+ * (((r / 128) * ceil(K / 64) + c / 4) * 32 + r % 32) * 16 + ((r % 128) / 32) * 4 + c % 4, the rows
+ * padded to a multiple of 128 and the columns to a multiple of 4 with zero bytes), and an optional
+ * fp32 per-tensor scale. Every per-tensor scale is a pointer to ONE float in device memory, or
+ * null: the kernels read it themselves, so no call synchronises and all can be graph-captured. */
+
+/* Per block of 16 elements of x bf16 [rows][K], K % 16 == 0, in fp32 with IEEE divisions:
+ *   b = amax|x| / 6 (then / per_tensor_scale);  scale = e4m3fn_rne(clamp(b, 2^-6, 448))
+ *   code = e2m1_rne_sat(clamp(x / (scale, or per_tensor_scale * scale), -6, 6))
+ * the reference's nvfp4_quantize (nvfp4_tensor.py:726-799) as the CPU computes it, bit for bit on
+ * finite rows, in one read of x; with swizzled = 1 the scales land at their blocked offsets and the
+ * padding bytes are written as zero (to_blocked). qdata [rows][K / 2]; scales rows * K / 16 bytes, or
+ * ceil(rows / 128) * 128 * ceil(K / 64) * 4 swizzled. x and qdata 16-B aligned. */
+int tao_nvfp4_quantize_rows_bf16(const uint16_t* x, uint8_t* qdata, uint8_t* scales,
+                                 const float* per_tensor_scale, int64_t rows, int64_t K,
+                                 int swizzled, void* stream);
+
+/* y = x snapped to its NVFP4 grid: bf16(value(code) * scale) with the quantizer's code and scale.
+ * The product is a bf16 number (at most 6 significant bits), so nothing is rounded; the per-tensor
+ * scale enters the block scales only and is NOT multiplied back (the linear applies it to its fp32
+ * total). DYNAMIC mode's activation step beyond one token; replaces the to_nvfp4 of the activation
+ * in nvfp4_linear (nvfp4_tensor.py:646-652). x, y bf16 [rows][K], 16-B aligned. */
+int tao_nvfp4_act_qdq_bf16(const uint16_t* x, uint16_t* y, const float* per_tensor_scale,
+                           int64_t rows, int64_t K, void* stream);
+
+/* w[n][k] = bf16(value(code) * float(t)), t = scale, or bf16(bf16(per_tensor_scale) * scale): the
+ * bits of the reference's NVFP4Tensor.to_dtype(bfloat16) (nvfp4_tensor.py:199-248) with a 0-dim
+ * per-tensor scale. K % 16 == 0; qdata and w 16-B aligned. */
+int tao_nvfp4_dequant_bf16(const uint8_t* qdata, const uint8_t* scales,
+                           const float* per_tensor_scale, uint16_t* w, int64_t N, int64_t K,
+                           int swizzled, void* stream);
+
+/* y[m][n] = bf16(alpha * sum_k xq[m][k] * value(code[n][k]) * scale[n][k / 16] + bias[n]), sums in
+ * fp32 (a block's 16 products first, then times its scale), one rounding. alpha = per_tensor_scale
+ * (1 if null) * act_per_tensor_scale (1 if null). dynamic = 0: xq = x, M >= 0 tokens, one launch of
+ * the decode GEMV (nvfp4_gemv_kernel) per 8. dynamic = 1: xq = x snapped as tao_nvfp4_act_qdq_bf16
+ * does under act_per_tensor_scale, inside the same launch; one token of K <= 16384
+ * (tao_nvfp4_linear_fused_snap), bit-identical to the snap followed by dynamic = 0. The op
+ * torchao::nvfp4_linear calls it up to the boundary of tao_nvfp4_linear_route and dequantizes +
+ * matmuls above. N % 16 == 0, K % 64 == 0; x and qdata 16-B aligned, scales 2-B aligned. Replaces
+ * F.linear(x, W.to_dtype()) and torch._scaled_mm on sm100 of nvfp4_linear (nvfp4_tensor.py:628). */
+int tao_nvfp4_linear_bf16(const uint16_t* x, const uint8_t* qdata, const uint8_t* scales,
+                          const float* per_tensor_scale, const float* act_per_tensor_scale,
+                          const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                          int swizzled, int dynamic, void* stream);
+
 /* ---- MoE expert FFN over many tokens (csrc/moe_gemm.hip; torchao/prototype/moe_quant) ----------
  * T tokens, A = top-k, R = T * A token activations, E experts. E <= 256, A <= 8. None of the three
  * kernels waits on another workgroup; each result is a pure function of its inputs. */

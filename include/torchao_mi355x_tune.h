@@ -230,6 +230,16 @@ int tao_fp6_linear_route(int64_t M, int64_t N, int64_t K);
  * 0 = built-in, 1 = 24 B (a 2048-code wave slice), 2 = 48 B (a 4096-code wave slice). */
 int tao_tune_fp6(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups,
                  int chunk_groups);
+/* The route torchao::nvfp4_linear takes for this call under the calling thread's tao_tune_nvfp4:
+ * 1 = the GEMV, tao_nvfp4_linear_bf16 (up to the built-in boundary M of csrc/nvfp4_host.h);
+ * 2 = tao_nvfp4_dequant_bf16 into a temporary and the bf16 matmul (after tao_nvfp4_act_qdq_bf16 in
+ * DYNAMIC mode), which needs an allocator and lives in the op (csrc/torch_ops.cpp). */
+int tao_nvfp4_linear_route(int64_t M, int64_t N, int64_t K);
+/* 1 where tao_nvfp4_linear_bf16 takes dynamic = 1 (one token whose snapped copy fits LDS). */
+int tao_nvfp4_linear_fused_snap(int64_t M, int64_t K);
+/* Route and launch shape of the NVFP4 linear (calling thread only; tests and A/B runs); the
+ * arguments of tao_tune_nf4. */
+int tao_tune_nvfp4(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups);
 /* The MFMA route of the FP6 linear (the Fp6WO policy of gemm_mfma_kernel, reading the 6-bit
  * storage in place): 0 = built-in route, 1 = every call the rule would send to dequantize + matmul
  * runs on the MFMA GEMM inside tao_fp6_linear_bf16 instead, and tao_fp6_linear_route returns 3

@@ -32,6 +32,19 @@ __device__ __forceinline__ float mx_divisor(uint32_t byte) {
   return __builtin_bit_cast(float, (byte > 1u ? byte : 1u) << 23);
 }
 
+// e2m1 code of the fp32 y (the MXFP4 and NVFP4 quantizers), round to nearest even, saturating. Magnitudes at or above 6 (inf too)
+// -> 7; below 1 the codes 0, 1, 2 lie 0.5 apart (ties 0.25 -> 0, 0.75 -> 2); in [1, 6) the code is
+// the top of the pattern rebiased from 127 to 1 and rounded at bit 22, ties to the even code. A
+// NaN pattern takes the last formula, its low byte kept.
+__device__ __forceinline__ uint32_t mxfp4_code(float y) {
+  const uint32_t bits = __builtin_bit_cast(uint32_t, y);
+  const uint32_t a = bits & 0x7FFFFFFFu;
+  const uint32_t norm = ((a - (126u << 23) + 0x1FFFFFu + ((a >> 22) & 1u)) >> 22) & 0xFFu;
+  const uint32_t sub = a > 0x3E800000u ? (a >= 0x3F400000u ? 2u : 1u) : 0u;
+  uint32_t c = a < 0x3F800000u ? sub : norm;
+  c = (a >= 0x40C00000u && a <= 0x7F800000u) ? 7u : c;
+  return ((bits >> 28) & 8u) | (c & 0xFu);
+}
 // d * 2^(xb - 127) * 2^(wb - 127); a byte 255 is NaN
 __device__ __forceinline__ float mx_scaled(float d, uint32_t xb, uint32_t wb) {
   const float v = ldexpf(d, (int)(xb + wb) - 254);

@@ -17,7 +17,7 @@
 // The divisor is a power of two between 2^-126 and 2^126, so x / divisor is the exact product with
 // its reciprocal (2^(127 - max(byte, 1)) 2^127 as one exponent field 254 - max(byte, 1)); byte 255
 // multiplies by 0: finite -> +-0, inf and NaN -> NaN, as dividing by +inf gives. The rounding is
-// integer arithmetic on the fp32 pattern (mxfp4_code). A NaN pattern takes the rounding of the
+// integer arithmetic on the fp32 pattern (mxfp4_code, mx_block.h). A NaN pattern takes the rounding of the
 // normal range, as the reference's arithmetic does (the default NaN gives magnitude code 3); an inf
 // in a NaN block gives 0xB (inf / inf is the default NaN of the host the reference ran on, sign
 // set). The whole block dequantizes to NaN either way.
@@ -65,19 +65,6 @@ __device__ __forceinline__ uint32_t mxfp4_scale_byte(uint32_t amax15) {
 __device__ __forceinline__ float mxfp4_recip(uint32_t byte) {
   const uint32_t b = byte > 1u ? byte : 1u;
   return __builtin_bit_cast(float, byte == 255u ? 0u : (254u - b) << 23);
-}
-// e2m1 code of the fp32 y, round to nearest even, saturating. Magnitudes at or above 6 (inf too)
-// -> 7; below 1 the codes 0, 1, 2 lie 0.5 apart (ties 0.25 -> 0, 0.75 -> 2); in [1, 6) the code is
-// the top of the pattern rebiased from 127 to 1 and rounded at bit 22, ties to the even code. A
-// NaN pattern takes the last formula, its low byte kept.
-__device__ __forceinline__ uint32_t mxfp4_code(float y) {
-  const uint32_t bits = __builtin_bit_cast(uint32_t, y);
-  const uint32_t a = bits & 0x7FFFFFFFu;
-  const uint32_t norm = ((a - (126u << 23) + 0x1FFFFFu + ((a >> 22) & 1u)) >> 22) & 0xFFu;
-  const uint32_t sub = a > 0x3E800000u ? (a >= 0x3F400000u ? 2u : 1u) : 0u;
-  uint32_t c = a < 0x3F800000u ? sub : norm;
-  c = (a >= 0x40C00000u && a <= 0x7F800000u) ? 7u : c;
-  return ((bits >> 28) & 8u) | (c & 0xFu);
 }
 // the 8 bf16 of one 16-B piece -> 8 nibbles, element 2 j in the high nibble of byte j
 __device__ __forceinline__ uint32_t mxfp4_quant8(const uint4 v, float recip, bool nan_block) {

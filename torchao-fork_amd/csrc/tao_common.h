@@ -56,7 +56,7 @@ int graph_workspace_count();
 // default instead.
 bool fence_free_validated();
 
-// What tao_tune_nf4, tao_tune_fp6 and tao_tune_uintx share: the linear's route (kWoRoute*,
+// What tao_tune_nf4, tao_tune_fp6, tao_tune_uintx and tao_tune_nvfp4 share: the linear's route (kWoRoute*,
 // wo_host.h) and GEMV boundary, and the GEMV's launch shape (rows per wave at one token, waves
 // along K, row groups).
 struct WoTune {
@@ -109,6 +109,7 @@ struct Tuning {
   int attn_prefill_nw = 0;  // prefill attention: waves per query block (0 built-in, 1, 2, 4)
   int gemv_lds = 0;  // int4 GEMV: minimum dynamic LDS per workgroup (caps residency; tao_tune_int4_lds)
   WoTune nf4, fp6, uintx;                        // tao_tune_nf4 / tao_tune_fp6 / tao_tune_uintx
+  WoTune nvfp4;                                  // tao_tune_nvfp4
   int fp6_groups = 0;                            // FP6 GEMV 32-code groups per lane chunk
   int fp6_mfma = 0;                              // FP6 linear: 1 = MFMA GEMM where the rule says dequant + mm
   int uintx_xlds = 0;                            // uintx GEMV x: 0 built-in, 1 through L1, 2 staged in LDS

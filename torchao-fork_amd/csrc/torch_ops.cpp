@@ -11,7 +11,8 @@
 // rowwise_scaled_linear_cutlass_s8s4, int8_quantize_per_token_f32, int4_quantize_rows_packed,
 // w4a8_dyn_linear, and the NF4 set nf4_quantize_blocks, nf4_dequantize, nf4_linear, and the FP6 set
 // fp6_quantize_rows, fp6_dequantize, fp6_weight_only_linear, and the MoE set moe_route,
-// int4_grouped_linear, moe_combine, and the uintx set uintx_dequantize, uintx_weight_only_linear.
+// int4_grouped_linear, moe_combine, and the uintx set uintx_dequantize, uintx_weight_only_linear,
+// and the NVFP4 set nvfp4_quantize, nvfp4_act_qdq, nvfp4_dequantize, nvfp4_linear.
 //
 // The schemas stay defined in torchao/ops.py (the reference's registration pattern,
 // torchao/ops.py:12-21); this library only supplies their CUDA kernels, so a call goes
@@ -31,6 +32,7 @@
 #include "../../include/torchao_mi355x_tune.h"  // tao_nf4_linear_route, tao_fp6_linear_route
 #include "fp6_host.h"
 #include "moe_host.h"
+#include "nvfp4_host.h"
 #include "uintx_host.h"
 
 namespace {
@@ -1399,9 +1401,155 @@ Tensor uintx_weight_only_linear(const Tensor& x, const std::optional<Tensor>& s4
       });
 }
 
+// ---- NVFP4 (torchao/prototype/mx_formats/nvfp4_tensor.py; csrc/nvfp4.hip) -----------------------
+// qdata uint8 [N, K / 2]; scales K / 16 one-byte e4m3fn codes per row, flat, row-major or swizzled
+// (with its padding); per-tensor scales fp32 tensors of one element, read on the device.
+const float* nvfp4_pts(const Tensor& like, const std::optional<Tensor>& pts, const char* op,
+                       const char* name) {
+  if (!pts.has_value()) return nullptr;
+  TORCH_CHECK(pts->scalar_type() == at::kFloat && pts->numel() == 1, op, ": ", name,
+              " must be one fp32 element, got ", pts->scalar_type(), " ", pts->sizes());
+  check_device(like, *pts, name);
+  return cptr<float>(*pts);
+}
+
+Tensor nvfp4_rows(const Tensor& x, const char* op) {
+  TORCH_CHECK(x.is_cuda(), op, ": expected x on a HIP device, got ", x.device());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, op, " (HIP) needs bf16 x, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) % tao::kNvfp4Block == 0, op,
+              ": the last dimension must be a multiple of 16, got ", x.sizes());
+  return rows_of(x, x.size(-1));
+}
+
+std::tuple<Tensor, Tensor> nvfp4_quantize(const Tensor& x, const std::optional<Tensor>& pts,
+                                          bool swizzled) {
+  const char* op = "nvfp4_quantize";
+  const Tensor x2 = nvfp4_rows(x, op);
+  TORCH_CHECK(x.dim() == 2, op, ": x must be 2D, got ", x.dim(), "D");
+  const float* p = nvfp4_pts(x, pts, op, "per_tensor_scale");
+  const int64_t rows = x2.size(0), K = x2.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor q = at::empty({rows, K / 2}, x.options().dtype(at::kByte));
+  Tensor s = at::empty({tao::nvfp4_scale_bytes(rows, K, swizzled)}, x.options().dtype(at::kByte));
+  check_rc(tao_nvfp4_quantize_rows_bf16(cptr<uint16_t>(x2), mptr<uint8_t>(q), mptr<uint8_t>(s), p,
+                                        rows, K, swizzled, stream_of(x)),
+           "tao_nvfp4_quantize_rows_bf16");
+  return {q, s};
+}
+
+Tensor nvfp4_act_qdq(const Tensor& x, const std::optional<Tensor>& pts) {
+  const char* op = "nvfp4_act_qdq";
+  const Tensor x2 = nvfp4_rows(x, op);
+  const float* p = nvfp4_pts(x, pts, op, "per_tensor_scale");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty(x2.sizes(), x.options());
+  check_rc(tao_nvfp4_act_qdq_bf16(cptr<uint16_t>(x2), mptr<uint16_t>(y), p, x2.size(0), x2.size(1),
+                                  stream_of(x)),
+           "tao_nvfp4_act_qdq_bf16");
+  return y.reshape(x.sizes());
+}
+
+struct Nvfp4Weight {
+  Tensor q, s;
+  int64_t N, K;
+};
+Nvfp4Weight check_nvfp4_weight(const Tensor& qdata, const Tensor& scales, bool swizzled,
+                               const char* op) {
+  TORCH_CHECK(qdata.is_cuda(), op, ": expected qdata on a HIP device, got ", qdata.device());
+  TORCH_CHECK(qdata.dim() == 2 && qdata.scalar_type() == at::kByte, op,
+              ": qdata must be a 2D uint8 [N, K / 2] tensor, got ", qdata.scalar_type(), " ",
+              qdata.sizes());
+  const int64_t N = qdata.size(0), K = qdata.size(1) * 2;
+  TORCH_CHECK(K % tao::kNvfp4Block == 0, op, ": K (", K, ") must be a multiple of 16");
+  TORCH_CHECK(scales.element_size() == 1 && scales.numel() == tao::nvfp4_scale_bytes(N, K, swizzled),
+              op, ": scales must hold ", tao::nvfp4_scale_bytes(N, K, swizzled),
+              " one-byte elements (", swizzled ? "swizzled" : "row-major", " [", N, ", ", K / 16,
+              "]), got ", scales.numel(), " of ", scales.scalar_type());
+  check_device(qdata, scales, "scales");
+  Tensor q = qdata;
+  if (!q.is_contiguous() || reinterpret_cast<uintptr_t>(q.data_ptr()) % 16) q = q.clone();
+  Tensor s = scales.reshape({-1});
+  if (!s.is_contiguous() || reinterpret_cast<uintptr_t>(s.data_ptr()) % 2) s = s.clone();
+  return {q, s, N, K};
+}
+
+Tensor nvfp4_dequantize_checked(const Nvfp4Weight& w, const float* pts, bool swizzled) {
+  Tensor out = at::empty({w.N, w.K}, w.q.options().dtype(at::kBFloat16));
+  check_rc(tao_nvfp4_dequant_bf16(cptr<uint8_t>(w.q), cptr<uint8_t>(w.s), pts, mptr<uint16_t>(out),
+                                  w.N, w.K, swizzled, stream_of(w.q)),
+           "tao_nvfp4_dequant_bf16");
+  return out;
+}
+
+Tensor nvfp4_dequantize(const Tensor& qdata, const Tensor& scales,
+                        const std::optional<Tensor>& pts, bool swizzled) {
+  const char* op = "nvfp4_dequantize";
+  const Nvfp4Weight w = check_nvfp4_weight(qdata, scales, swizzled, op);
+  const float* p = nvfp4_pts(qdata, pts, op, "per_tensor_scale");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qdata.device());
+  return nvfp4_dequantize_checked(w, p, swizzled);
+}
+
+// Up to the route's boundary the GEMV (DYNAMIC: the snap inside the launch at one token, the snap
+// kernel first beyond); above it the snap, the dequantizer into a temporary and the bf16 matmul,
+// the per-tensor scales and the bias meeting the product in fp32.
+Tensor nvfp4_linear(const Tensor& x, const Tensor& qdata, const Tensor& scales,
+                    const std::optional<Tensor>& pts, const std::optional<Tensor>& bias,
+                    bool swizzled, bool dynamic, const std::optional<Tensor>& act_pts) {
+  const char* op = "nvfp4_linear";
+  check_wo_x(x, op);
+  check_device(x, qdata, "qdata");
+  const Nvfp4Weight w = check_nvfp4_weight(qdata, scales, swizzled, op);
+  const int64_t N = w.N, K = w.K;
+  TORCH_CHECK(tao::nvfp4_shape_ok(N, K), op, ": N (", N, ") must be a positive multiple of 16 and K (",
+              K, ") of 64");
+  const float* wp = nvfp4_pts(x, pts, op, "per_tensor_scale");
+  const float* ap = nvfp4_pts(x, act_pts, op, "act_per_tensor_scale");
+  TORCH_CHECK(x.size(-1) == K, "x last dim ", x.size(-1), " != K ", K);
+  TORCH_CHECK(!bias.has_value() || bias->numel() == N, op, ": bias must have N = ", N, " elements");
+  check_device(x, bias, "bias");
+  Tensor x2 = rows_of(x, K);
+  const int64_t M = x2.size(0);
+  const std::optional<Tensor> b = bf16_bias(bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  if (M == 0) return at::empty(out_shape(x, N), x.options());
+  const bool gemv = tao_nvfp4_linear_route(M, N, K) != 2;
+  const bool fused = dynamic && gemv && tao_nvfp4_linear_fused_snap(M, K);
+  if (dynamic && !fused) {
+    Tensor xq = at::empty_like(x2);
+    check_rc(tao_nvfp4_act_qdq_bf16(cptr<uint16_t>(x2), mptr<uint16_t>(xq), ap, M, K, stream_of(x)),
+             "tao_nvfp4_act_qdq_bf16");
+    x2 = xq;
+  }
+  if (!gemv) {
+    // W^ without the per-tensor scale: value(code) * scale, a bf16 number, so the temporary is
+    // exact; the per-tensor scales and the bias meet the matmul's bf16 output in fp32
+    Tensor y = at::linear(x2, nvfp4_dequantize_checked(w, nullptr, swizzled));
+    if (wp != nullptr || ap != nullptr) {
+      Tensor yf = y.to(at::kFloat);
+      if (wp != nullptr) yf = yf * *pts;
+      if (ap != nullptr) yf = yf * *act_pts;
+      y = (b ? yf + b->to(at::kFloat) : yf).to(at::kBFloat16);
+    } else if (b) {
+      y = y + *b;
+    }
+    return y.reshape(out_shape(x, N));
+  }
+  Tensor y = at::empty({M, N}, x.options().dtype(at::kBFloat16));
+  check_rc(tao_nvfp4_linear_bf16(cptr<uint16_t>(x2), cptr<uint8_t>(w.q), cptr<uint8_t>(w.s), wp, ap,
+                                 b ? cptr<uint16_t>(*b) : nullptr, mptr<uint16_t>(y), M, N, K,
+                                 swizzled, fused, stream_of(x)),
+           "tao_nvfp4_linear_bf16");
+  return y.reshape(out_shape(x, N));
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(torchao, CUDA, m) {
+  m.impl("nvfp4_quantize", &nvfp4_quantize);
+  m.impl("nvfp4_act_qdq", &nvfp4_act_qdq);
+  m.impl("nvfp4_dequantize", &nvfp4_dequantize);
+  m.impl("nvfp4_linear", &nvfp4_linear);
   m.impl("uintx_dequantize", &uintx_dequantize);
   m.impl("uintx_weight_only_linear", &uintx_weight_only_linear);
   m.impl("moe_route", &moe_route);
@@ -1513,4 +1661,9 @@ extern "C" const char* tao_torch_ops_served_w4a8(void) {
 // The MXFP4-weight ops served here, a set of their own as well.
 extern "C" const char* tao_torch_ops_served_mxfp4(void) {
   return "mxfp4_quantize_rows,mxfp4w_scaled_mm,mxfp4w_dyn_linear";
+}
+
+// The NVFP4 ops served here; they have no Python kernels either.
+extern "C" const char* tao_torch_ops_served_nvfp4(void) {
+  return "nvfp4_quantize,nvfp4_act_qdq,nvfp4_dequantize,nvfp4_linear";
 }

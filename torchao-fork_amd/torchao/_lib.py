@@ -110,6 +110,13 @@ _SIGNATURES = {
     "tao_uintx_gemv_unit": [_i64, _i64, _int],
     "tao_tune_uintx": [_int, _int, _int, _int, _int, _int, _int],
     "tao_uintx_gemv_x_lds": [_i64, _i64, _int],
+    "tao_nvfp4_quantize_rows_bf16": [_p, _p, _p, _p, _i64, _i64, _int, _p],
+    "tao_nvfp4_act_qdq_bf16": [_p, _p, _p, _i64, _i64, _p],
+    "tao_nvfp4_dequant_bf16": [_p, _p, _p, _p, _i64, _i64, _int, _p],
+    "tao_nvfp4_linear_bf16": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p],
+    "tao_nvfp4_linear_route": [_i64, _i64, _i64],
+    "tao_nvfp4_linear_fused_snap": [_i64, _i64],
+    "tao_tune_nvfp4": [_int, _int, _int, _int, _int],
     "tao_moe_route": [_p, _i64, _i64, _i64, _p, _p, _p, _p],
     "tao_int4wo_grouped_linear_bf16": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _p,
                                        _i64, _i64, _i64, _p],

@@ -57,6 +57,8 @@ _KNOBS = {
     # 1: the MFMA GEMM wherever the uintx route rule says dequantize + matmul and the kernel serves
     # the shape (group_size a multiple of 32)
     "uintx_mfma": ("tao_tune_uintx_mfma", 1),
+    # (route, max_gemv_m, rows per wave, waves along K, row groups as for nf4)
+    "nvfp4": ("tao_tune_nvfp4", 5),
     # (rows per tile of the grouped MoE GEMM: 0 built-in, 16, 32, 64; gate and up: 0 built-in,
     # 1 = two launches, 2 = one)
     "moe": ("tao_tune_moe", 2),

@@ -228,6 +228,21 @@ lib_fp6.define("fp6_dequantize(Tensor codes, Tensor scale, int ebits, int mbits)
 lib_fp6.define(
     "fp6_weight_only_linear(Tensor x, Tensor codes, Tensor scale, int ebits, int mbits, "
     "Tensor? bias=None) -> Tensor")
+# The NVFP4 ops (NVFP4InferenceConfig, torchao/prototype/mx_formats/nvfp4_tensor.py;
+# csrc/nvfp4.hip), on a fragment of their own; opchecked in tests/test_gpu_nvfp4.py. bf16 HIP
+# tensors only: everything else runs the plain-torch formulation in nvfp4_tensor.py. scales are the
+# one-byte e4m3fn codes, flat, row-major or swizzled; a per-tensor scale is one fp32 element on the
+# device. Their CUDA kernels exist in C++ only (csrc/torch_ops.cpp).
+lib_nvfp4 = torch.library.Library("torchao", "FRAGMENT")
+lib_nvfp4.define(
+    "nvfp4_quantize(Tensor x, Tensor? per_tensor_scale, bool swizzled) -> (Tensor, Tensor)")
+lib_nvfp4.define("nvfp4_act_qdq(Tensor x, Tensor? per_tensor_scale) -> Tensor")
+lib_nvfp4.define(
+    "nvfp4_dequantize(Tensor qdata, Tensor scales, Tensor? per_tensor_scale, bool swizzled) "
+    "-> Tensor")
+lib_nvfp4.define(
+    "nvfp4_linear(Tensor x, Tensor qdata, Tensor scales, Tensor? per_tensor_scale, Tensor? bias, "
+    "bool swizzled, bool dynamic, Tensor? act_per_tensor_scale) -> Tensor")
 # The MoE ops (MoEQuantConfig, torchao/prototype/moe_quant; csrc/moe_gemm.hip), on a fragment of
 # their own; opchecked in tests/test_gpu_moe.py: the stable sort of the token activations by expert,
 # every expert's int4 linear over its own sorted rows in one launch (a second stack: gate and up
@@ -1817,6 +1832,55 @@ def _(x, codes, scale, ebits, mbits, bias=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# NVFP4 (csrc/nvfp4.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
+# ---------------------------------------------------------------------------------------------
+def _nvfp4_scale_bytes(rows, K, swizzled):
+    cols = K // 16
+    return (rows + 127) // 128 * 128 * ((cols + 3) // 4) * 4 if swizzled else rows * cols
+
+
+def _check_nvfp4_weight(qdata, scales, swizzled, op):
+    torch._check(qdata.dtype is torch.uint8 and qdata.dim() == 2,
+                 lambda: f"{op}: qdata must be a 2D uint8 [N, K / 2] tensor")
+    N, K = qdata.shape[0], qdata.shape[1] * 2
+    torch._check(K % 16 == 0, lambda: f"{op}: K ({K}) must be a multiple of 16")
+    torch._check(scales.numel() == _nvfp4_scale_bytes(N, K, swizzled),
+                 lambda: f"{op}: scales must hold {_nvfp4_scale_bytes(N, K, swizzled)} elements")
+    return N, K
+
+
+@torch.library.register_fake("torchao::nvfp4_quantize")
+def _(x, per_tensor_scale, swizzled):
+    torch._check(x.dim() == 2 and x.shape[1] % 16 == 0,
+                 lambda: "nvfp4_quantize: x must be 2D with K a multiple of 16")
+    rows, K = x.shape
+    return (x.new_empty((rows, K // 2), dtype=torch.uint8),
+            x.new_empty((_nvfp4_scale_bytes(rows, K, swizzled),), dtype=torch.uint8))
+
+
+@torch.library.register_fake("torchao::nvfp4_act_qdq")
+def _(x, per_tensor_scale):
+    torch._check(x.dim() >= 1 and x.shape[-1] % 16 == 0,
+                 lambda: "nvfp4_act_qdq: the last dimension must be a multiple of 16")
+    return x.new_empty(x.shape)
+
+
+@torch.library.register_fake("torchao::nvfp4_dequantize")
+def _(qdata, scales, per_tensor_scale, swizzled):
+    N, K = _check_nvfp4_weight(qdata, scales, swizzled, "nvfp4_dequantize")
+    return qdata.new_empty((N, K), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("torchao::nvfp4_linear")
+def _(x, qdata, scales, per_tensor_scale, bias, swizzled, dynamic, act_per_tensor_scale):
+    N, K = _check_nvfp4_weight(qdata, scales, swizzled, "nvfp4_linear")
+    torch._check(N % 16 == 0 and K % 64 == 0,
+                 lambda: f"nvfp4_linear: N ({N}) must be a multiple of 16 and K ({K}) of 64")
+    torch._check(x.shape[-1] == K, lambda: f"x last dim {x.shape[-1]} != K {K}")
+    return x.new_empty((*x.shape[:-1], N), dtype=torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------
 # MoE (csrc/moe_gemm.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
 # ---------------------------------------------------------------------------------------------
 MOE_MAX_EXPERTS = 256
@@ -1916,6 +1980,7 @@ _native_served_w4a8: frozenset = frozenset()
 _native_served_nf4: frozenset = frozenset()
 _native_served_fp6: frozenset = frozenset()
 _native_served_uintx: frozenset = frozenset()
+_native_served_nvfp4: frozenset = frozenset()
 _native_served_moe: frozenset = frozenset()
 _native_error: Optional[str] = None
 if os.environ.get("TORCHAO_MI355X_LIB"):
@@ -1960,6 +2025,9 @@ else:
         _served = _ops_dll.tao_torch_ops_served_uintx
         _served.restype = ctypes.c_char_p
         _native_served_uintx = frozenset(_served().decode().split(","))
+        _served = _ops_dll.tao_torch_ops_served_nvfp4
+        _served.restype = ctypes.c_char_p
+        _native_served_nvfp4 = frozenset(_served().decode().split(","))
         _served = _ops_dll.tao_torch_ops_served_moe
         _served.restype = ctypes.c_char_p
         _native_served_moe = frozenset(_served().decode().split(","))
@@ -2026,6 +2094,11 @@ def native_dispatch_moe() -> frozenset:
 def native_dispatch_uintx() -> frozenset:
     """The uintx ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
     return _native_served_uintx
+
+
+def native_dispatch_nvfp4() -> frozenset:
+    """The NVFP4 ops (they have C++ CUDA kernels only; empty when libtorchao_ops.so did not load)."""
+    return _native_served_nvfp4
 
 
 def native_dispatch_w4a8() -> frozenset:
