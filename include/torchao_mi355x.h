@@ -354,6 +354,40 @@ int tao_int8_dyn_linear_bf16(const uint16_t* x, const int8_t* wq, const uint16_t
                              const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                              void* stream);
 
+/* ---- 2:4 sparse int8 weight under int8 dynamic activations (csrc/sparse24.hip) -----------------
+ * Storage of a dense int8 weight [N][K] (K % 128 == 0) with at most two nonzeros in every aligned
+ * group of four k: values int8 [N][K/2] (the two kept elements of each group, ascending position)
+ * and meta int32 [N][K/32] (dword j of a row: bits [2i+1:2i] = the position 0-3 of value 16 j + i
+ * inside its group): 0.625 B per dense weight, the operand layout of v_smfmac_i32_16x16x128_i8.
+ * Kept positions: the group's nonzero positions, padded with its lowest zero positions, ascending.
+ * Replaces torch._cslt_compress (torchao/dtypes/uintx/semi_sparse_layout.py:60-73). A group with
+ * more than two nonzeros ORs 1 into *err (int32 in device memory, zeroed by the caller). */
+int tao_int8_sp24_compress(const int8_t* w, int8_t* values, int32_t* meta, int32_t* err, int64_t N,
+                           int64_t K, void* stream);
+
+/* The inverse: dense int8 [N][K] from (values, meta). Replaces the matmul by the identity of
+ * SemiSparseAQTTensorImpl.get_plain (torchao/dtypes/uintx/semi_sparse_layout.py:42-58). */
+int tao_int8_sp24_decompress(const int8_t* values, const int32_t* meta, int8_t* w, int64_t N,
+                             int64_t K, void* stream);
+
+/* tao_int8_scaled_mm_bf16 on the compressed weight, bit-identical to it on the decompressed one:
+ * y[M][N] = bf16( bf16( bf16(xq @ W^T) * xs[m] ) * ws[n] ) (+ bias), exact int32 accumulation.
+ * Few tokens: a GEMV over values + meta; more: the sparse MFMA GEMM (route: csrc/sparse24_host.h).
+ * Replaces torch._cslt_sparse_mm and its scale epilogue
+ * (torchao/dtypes/uintx/semi_sparse_layout.py:173-206), which rounds after the weight scale first.
+ * K % 128 == 0, M < 2^20; xq, values 16-B aligned, y 8-B aligned. */
+int tao_int8_sp24_scaled_mm_bf16(const int8_t* xq, const uint16_t* xs, const int8_t* values,
+                                 const int32_t* meta, const uint16_t* ws, const uint16_t* bias,
+                                 uint16_t* y, int64_t M, int64_t N, int64_t K, void* stream);
+
+/* One token (M <= 1): tao_int8_quant_per_token and the sparse GEMV in ONE launch, bit-identical to
+ * the two calls (K % 128 == 0, K <= 32768). Replaces the quantize-then-F.linear of
+ * linear_activation_quantized_tensor.py _quantized_linear_op on a SemiSparseLayout weight at
+ * decode (quant_api.py:1258-1273 + semi_sparse_layout.py:173-206). */
+int tao_int8_sp24_dyn_linear_bf16(const uint16_t* x, const int8_t* values, const int32_t* meta,
+                                  const uint16_t* ws, const uint16_t* bias, uint16_t* y, int64_t M,
+                                  int64_t N, int64_t K, void* stream);
+
 /* SmoothQuant activation quantization of x [M][K] bf16 in one launch: t = bf16(x / smooth)
  * (tao_act_prescale_bf16's bits; smooth bf16 [K]; t is never written), then
  *   act_scale == NULL (dynamic): s[m] = max(bf16(amax(|t[m]|) / 127), 2^-7), the default eps of

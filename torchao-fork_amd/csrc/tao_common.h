@@ -116,6 +116,8 @@ struct Tuning {
   int uintx_unit = 0;                            // uintx GEMV bytes of a shard piece per lane unit
   int uintx_mfma = 0;                            // uintx linear: 1 = MFMA GEMM where the rule says dequant + mm
   int moe_bm = 0, moe_dual = 0;                  // grouped (MoE) int4 GEMM row tile / dual form (tao_tune_moe)
+  WoTune sp24;                                   // 2:4 sparse int8 linear (tao_tune_sp24; route 2 = sparse MFMA GEMM)
+  int sp24_bm = 0, sp24_nwv = 0, sp24_kg = 0;    // sparse MFMA GEMM shape (tao_tune_sp24_gemm)
 };
 Tuning& tuning();
 

@@ -26,6 +26,8 @@ from .uintx import (
     CutlassInt4PackedLayout,
     Int4PackedTensorImpl,
     PlainAQTTensorImpl,
+    SemiSparseAQTTensorImpl,
+    SemiSparseLayout,
     TensorCoreTiledAQTTensorImpl,
     TensorCoreTiledLayout,
     UintxAQTTensorImpl,
@@ -41,6 +43,8 @@ __all__ = [
     "Layout",
     "PlainLayout",
     "PlainAQTTensorImpl",
+    "SemiSparseLayout",
+    "SemiSparseAQTTensorImpl",
     "TensorCoreTiledLayout",
     "TensorCoreTiledAQTTensorImpl",
     "CutlassInt4PackedLayout",

@@ -40,6 +40,10 @@ from torchao.dtypes.uintx.plain_layout import (
     _linear_int8_act_int8_weight_check,
     _linear_int8_act_int8_weight_impl,
 )
+from torchao.dtypes.uintx.semi_sparse_layout import (
+    _linear_int8_act_int8_sp24_weight_check,
+    _linear_int8_act_int8_sp24_weight_impl,
+)
 from torchao.dtypes.uintx.tensor_core_tiled_layout import (
     _linear_bf16_act_uint4_weight_check,
     _linear_bf16_act_uint4_weight_impl,
@@ -88,6 +92,7 @@ AffineQuantizedTensor._quantized_linear_op = staticmethod(_quantized_linear_op)
 
 for _cond, _impl in [
     (_linear_int8_act_int8_weight_check, _linear_int8_act_int8_weight_impl),
+    (_linear_int8_act_int8_sp24_weight_check, _linear_int8_act_int8_sp24_weight_impl),
     (_linear_fp_act_int8_weight_check, _linear_fp_act_int8_weight_impl),
     (_linear_bf16_act_uint4_weight_check, _linear_bf16_act_uint4_weight_impl),
     (_linear_fp_act_fp8_weight_check, _linear_fp_act_fp8_weight_impl),

@@ -1743,6 +1743,214 @@ def _w4a8_dyn_linear_cuda(x, weight, weight_scale, bias=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# 2:4 sparse int8 weight under int8 dynamic activations (csrc/sparse24.hip)
+# ---------------------------------------------------------------------------------------------
+# Storage: values int8 [N, K/2] (the two kept elements of every group of four dense k, ascending
+# position), meta int32 [N, K/32] (bits [2i+1:2i] of dword j: the position of value 16 j + i inside
+# its group). On CPU tensors every op evaluates its definition in plain torch (the functions
+# below); on the GPU bf16 only, through the kernels.
+lib_sp24 = torch.library.Library("torchao", "FRAGMENT")
+lib_sp24.define("int8_sp24_compress(Tensor w) -> (Tensor, Tensor, Tensor)")
+lib_sp24.define("int8_sp24_decompress(Tensor values, Tensor meta) -> Tensor")
+lib_sp24.define("int8_sp24_scaled_mm(Tensor x_int8, Tensor x_scale, Tensor values, Tensor meta, "
+                "Tensor w_scale, Tensor? bias=None) -> Tensor")
+lib_sp24.define("int8_sp24_dyn_linear(Tensor x, Tensor values, Tensor meta, Tensor w_scale, "
+                "Tensor? bias=None) -> Tensor")
+
+
+def _check_sp24_dense(w):
+    torch._check(w.dim() == 2 and w.dtype is torch.int8, lambda: "w must be a 2D int8 tensor")
+    torch._check(w.size(1) % 128 == 0, lambda: f"K ({w.size(1)}) must be a multiple of 128")
+    return w.shape
+
+
+def _check_sp24_weight(values, meta, w_scale=None):
+    torch._check(values.dim() == 2 and values.dtype is torch.int8,
+                 lambda: "values must be a 2D int8 [N, K/2] tensor")
+    N, K = values.size(0), values.size(1) * 2
+    torch._check(K % 128 == 0, lambda: f"K ({K}) must be a multiple of 128")
+    torch._check(meta.dtype is torch.int32 and tuple(meta.shape) == (N, K // 32),
+                 lambda: f"meta must be int32 [N, K/32] = ({N}, {K // 32}), got "
+                         f"{meta.dtype} {tuple(meta.shape)}")
+    torch._check(w_scale is None or w_scale.numel() == N, lambda: "w_scale must have N elements")
+    return N, K
+
+
+def _sp24_compress_ref(w: Tensor):
+    """(values, meta, err) of a dense int8 [N, K]: of every group of four, its nonzero positions
+    ascending, padded with its lowest zero positions, sorted; err[0] = 1 where a group has more
+    than two nonzeros (its lowest two are kept)."""
+    N, K = _check_sp24_dense(w)
+    g = w.reshape(N, K // 4, 4)
+    nz = g != 0
+    key = (~nz).to(torch.int64) * 4 + torch.arange(4, device=w.device)
+    pos = key.argsort(dim=-1)[..., :2].sort(dim=-1).values
+    values = torch.gather(g, -1, pos).reshape(N, K // 2)
+    code = (pos[..., 0] | (pos[..., 1] << 2)).reshape(N, K // 32, 8)
+    m = (code << (4 * torch.arange(8, device=w.device))).sum(-1)
+    meta = torch.where(m >= 2 ** 31, m - 2 ** 32, m).to(torch.int32)
+    err = (nz.sum(-1) > 2).any().to(torch.int32).reshape(1)
+    return values.contiguous(), meta, err
+
+
+def _sp24_decompress_ref(values: Tensor, meta: Tensor) -> Tensor:
+    N, K = _check_sp24_weight(values, meta)
+    m = meta.to(torch.int64) & 0xFFFFFFFF
+    code = ((m.unsqueeze(-1) >> (4 * torch.arange(8, device=meta.device))) & 0xF).reshape(
+        N, K // 4)
+    pos = torch.stack([code & 3, code >> 2], dim=-1)
+    w = torch.zeros((N, K // 4, 4), dtype=torch.int8, device=values.device)
+    w.scatter_(-1, pos, values.reshape(N, K // 4, 2))
+    return w.reshape(N, K)
+
+
+def _int8_scaled_mm_ref(x_int8, x_scale, w_int8, w_scale, bias):
+    """tao_int8_scaled_mm_bf16's definition: exact integer product, then
+    bf16(bf16(bf16(acc) * xs[m]) * ws[n]) (+ bias) in torch bf16 ops."""
+    x2 = x_int8.reshape(-1, x_int8.size(-1))
+    acc = torch.mm(x2.to(torch.int64), w_int8.t().to(torch.int64))
+    y = acc.to(torch.int32).to(torch.bfloat16) * x_scale.reshape(-1, 1).to(torch.bfloat16)
+    y = y * w_scale.reshape(-1).to(torch.bfloat16)
+    if bias is not None:
+        y = y + bias.to(torch.bfloat16)
+    return y.reshape(_linear_out_shape(x_int8, w_int8.size(0)))
+
+
+def _int8_quant_per_token_ref(x):
+    """tao_int8_quant_per_token's definition in torch bf16 ops."""
+    x = x.to(torch.bfloat16)
+    s = (x.abs().amax(dim=-1, keepdim=True) / 127).clamp(min=1e-5)
+    q = torch.clamp(torch.round(x * (1.0 / s)), -127, 127).to(torch.int8)
+    return q, s
+
+
+def _int8_sp24_compress_cpu(w):
+    return _sp24_compress_ref(w)
+
+
+def _int8_sp24_scaled_mm_cpu(x_int8, x_scale, values, meta, w_scale, bias=None):
+    _check_sp24_weight(values, meta, w_scale)
+    return _int8_scaled_mm_ref(x_int8, x_scale, _sp24_decompress_ref(values, meta), w_scale, bias)
+
+
+def _int8_sp24_dyn_linear_cpu(x, values, meta, w_scale, bias=None):
+    _check_sp24_weight(values, meta, w_scale)
+    q, s = _int8_quant_per_token_ref(x)
+    return _int8_scaled_mm_ref(q, s, _sp24_decompress_ref(values, meta), w_scale, bias)
+
+
+@torch.library.register_fake("torchao::int8_sp24_compress")
+def _(w):
+    N, K = _check_sp24_dense(w)
+    return (w.new_empty((N, K // 2)), w.new_empty((N, K // 32), dtype=torch.int32),
+            w.new_empty((1,), dtype=torch.int32))
+
+
+@torch.library.register_fake("torchao::int8_sp24_decompress")
+def _(values, meta):
+    N, K = _check_sp24_weight(values, meta)
+    return values.new_empty((N, K))
+
+
+@torch.library.register_fake("torchao::int8_sp24_scaled_mm")
+def _(x_int8, x_scale, values, meta, w_scale, bias=None):
+    N, K = _check_sp24_weight(values, meta, w_scale)
+    torch._check(x_int8.size(-1) == K, lambda: f"x last dim {x_int8.size(-1)} != K {K}")
+    return x_int8.new_empty(_linear_out_shape(x_int8, N), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("torchao::int8_sp24_dyn_linear")
+def _(x, values, meta, w_scale, bias=None):
+    N, K = _check_sp24_weight(values, meta, w_scale)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N), dtype=torch.bfloat16)
+
+
+def _int8_sp24_compress_cuda(w):
+    N, K = _check_sp24_dense(w)
+    w = w.contiguous()
+    values = torch.empty((N, K // 2), dtype=torch.int8, device=w.device)
+    meta = torch.empty((N, K // 32), dtype=torch.int32, device=w.device)
+    err = torch.zeros((1,), dtype=torch.int32, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("tao_int8_sp24_compress", _ptr(w), _ptr(values), _ptr(meta), _ptr(err), N, K,
+                  _stream(w))
+    return values, meta, err
+
+
+def _int8_sp24_decompress_cuda(values, meta):
+    N, K = _check_sp24_weight(values, meta)
+    _same_device(values, meta=meta)
+    values, meta = values.contiguous(), meta.contiguous()
+    w = torch.empty((N, K), dtype=torch.int8, device=values.device)
+    with torch.cuda.device(values.device):
+        _lib.call("tao_int8_sp24_decompress", _ptr(values), _ptr(meta), _ptr(w), N, K,
+                  _stream(values))
+    return w
+
+
+def _sp24_operands(values, meta, w_scale, bias):
+    ws = w_scale.reshape(-1).to(torch.bfloat16).contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    return values.contiguous(), meta.contiguous(), ws, bias
+
+
+def _int8_sp24_scaled_mm_cuda(x_int8, x_scale, values, meta, w_scale, bias=None):
+    N, K = _check_sp24_weight(values, meta, w_scale)
+    torch._check(x_int8.dtype is torch.int8, lambda: "x_int8 must be int8")
+    torch._check(x_int8.size(-1) == K, lambda: f"x last dim {x_int8.size(-1)} != K {K}")
+    _same_device(x_int8, x_scale=x_scale, values=values, meta=meta, w_scale=w_scale, bias=bias)
+    x2 = x_int8.reshape(-1, K).contiguous()
+    M = x2.size(0)
+    xs = x_scale.reshape(-1).to(torch.bfloat16).contiguous()
+    torch._check(xs.numel() == M, lambda: "x_scale must have one entry per row")
+    values, meta, ws, bias = _sp24_operands(values, meta, w_scale, bias)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x_int8.device)
+    with torch.cuda.device(x_int8.device):
+        _lib.call("tao_int8_sp24_scaled_mm_bf16", _ptr(x2), _ptr(xs), _ptr(values), _ptr(meta),
+                  _ptr(ws), _ptr(bias), _ptr(y), M, N, K, _stream(x_int8))
+    return y.reshape(_linear_out_shape(x_int8, N))
+
+
+def _int8_sp24_dyn_linear_cuda(x, values, meta, w_scale, bias=None):
+    """The whole linear from a bf16 activation. One token: quantisation + sparse GEMV in one
+    launch. More: int8_quantize_per_token's kernel into buffers of the caching allocator, then
+    the sparse scaled mm; bit-identical to calling the two ops."""
+    N, K = _check_sp24_weight(values, meta, w_scale)
+    torch._check(x.dtype is torch.bfloat16, lambda: "int8_sp24_dyn_linear (HIP) needs bf16 x")
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    _same_device(x, values=values, meta=meta, w_scale=w_scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    values, meta, ws, bias = _sp24_operands(values, meta, w_scale, bias)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        if M == 1 and K <= 32768:
+            _lib.call("tao_int8_sp24_dyn_linear_bf16", _ptr(x2), _ptr(values), _ptr(meta),
+                      _ptr(ws), _ptr(bias), _ptr(y), 1, N, K, _stream(x))
+        elif M > 0:
+            q = torch.empty((M, K), dtype=torch.int8, device=x.device)
+            s = torch.empty((M,), dtype=torch.bfloat16, device=x.device)
+            _lib.call("tao_int8_quant_per_token", _ptr(x2), _ptr(q), _ptr(s), M, K, _stream(x))
+            _lib.call("tao_int8_sp24_scaled_mm_bf16", _ptr(q), _ptr(s), _ptr(values), _ptr(meta),
+                      _ptr(ws), _ptr(bias), _ptr(y), M, N, K, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
+for _name, _cpu, _cuda in [
+    ("int8_sp24_compress", _int8_sp24_compress_cpu, _int8_sp24_compress_cuda),
+    ("int8_sp24_decompress", _sp24_decompress_ref, _int8_sp24_decompress_cuda),
+    ("int8_sp24_scaled_mm", _int8_sp24_scaled_mm_cpu, _int8_sp24_scaled_mm_cuda),
+    ("int8_sp24_dyn_linear", _int8_sp24_dyn_linear_cpu, _int8_sp24_dyn_linear_cuda),
+]:
+    lib_sp24.impl(_name, _cpu, "CPU")
+    lib_sp24.impl(_name, _cuda, "CUDA")
+
+
+# ---------------------------------------------------------------------------------------------
 # NF4 (csrc/nf4.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
 # ---------------------------------------------------------------------------------------------
 def _check_nf4_parts(codes, qscalers, qfactor, mean, levels, numel, op):

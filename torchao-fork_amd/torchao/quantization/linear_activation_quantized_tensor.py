@@ -93,6 +93,7 @@ def _fused_int8_dyn_decode(x, weight_tensor, bias):
     recipe, shape or device returns None and takes the reference path above."""
     from torchao.dtypes.affine_quantized_tensor import AffineQuantizedTensor
     from torchao.dtypes.uintx.plain_layout import PlainLayout, _aqt_is_int8
+    from torchao.dtypes.uintx.semi_sparse_layout import SemiSparseLayout
     from torchao.quantization.quant_api import _int8_symm_per_token_reduced_range_quant
 
     if weight_tensor.input_quant_func is not _int8_symm_per_token_reduced_range_quant:
@@ -103,6 +104,13 @@ def _fused_int8_dyn_decode(x, weight_tensor, bias):
     if not (x.is_cuda and x.dtype == torch.bfloat16 and K % 16 == 0 and x.numel() == K):
         return None
     w = weight_tensor.original_weight_tensor
+    if (isinstance(w, AffineQuantizedTensor) and isinstance(w._layout, SemiSparseLayout)
+            and _aqt_is_int8(w) and w.dtype == torch.bfloat16 and w.shape[1] == K and K <= 32768
+            and w.tensor_impl.values.is_cuda):
+        # the 2:4 compressed weight: its own one launch
+        impl = w.tensor_impl
+        return torch.ops.torchao.int8_sp24_dyn_linear(
+            x, impl.values, impl.meta, impl.scale.reshape(-1), bias)
     if not (isinstance(w, AffineQuantizedTensor) and _aqt_is_int8(w) and w.dtype == torch.bfloat16
             and isinstance(w._layout, PlainLayout) and len(w.shape) == 2 and w.shape[1] == K
             and w.tensor_impl.int_data.is_cuda):

@@ -41,6 +41,7 @@ from torchao.dtypes.floatx.float8_layout import Float8Layout, Float8MMConfig
 from torchao.dtypes.uintx.cutlass_int4_packed_layout import CutlassInt4PackedLayout
 from torchao.dtypes.uintx.plain_layout import PlainAQTTensorImpl
 from torchao.dtypes.uintx.tensor_core_tiled_layout import TensorCoreTiledLayout
+from torchao.dtypes.uintx.semi_sparse_layout import SemiSparseLayout
 from torchao.dtypes.utils import Layout, PlainLayout
 from torchao.quantization.granularity import Granularity, PerRow, PerTensor
 from torchao.quantization.linear_activation_quantized_tensor import (
@@ -384,6 +385,19 @@ class Int8DynamicActivationInt8WeightConfig(AOBaseConfig):
 int8_dynamic_activation_int8_weight = Int8DynamicActivationInt8WeightConfig
 
 
+def _check_semi_sparse_weight(weight):
+    """What the 2:4 sparse int8 linear serves (csrc/sparse24.hip)."""
+    if weight.dim() != 2 or weight.shape[-1] % 128 != 0:
+        raise NotImplementedError(
+            "SemiSparseLayout serves 2-D weights whose in_features are a multiple of 128, got "
+            f"{tuple(weight.shape)}"
+        )
+    if weight.is_cuda and weight.dtype != torch.bfloat16:
+        raise NotImplementedError(
+            f"SemiSparseLayout serves bf16 modules on the GPU, got {weight.dtype}"
+        )
+
+
 def _int8_dynamic_activation_int8_weight_quantize_tensor(weight, config):
     if weight.shape[-1] <= 16:
         logger.info(
@@ -391,8 +405,10 @@ def _int8_dynamic_activation_int8_weight_quantize_tensor(weight, config):
             f"{weight.shape} because `in_feature` is <= 16: {weight.shape[-1]}"
         )
         return weight
-    if not isinstance(config.layout, PlainLayout):
+    if not isinstance(config.layout, (PlainLayout, SemiSparseLayout)):
         raise NotImplementedError("only PlainLayout is supported for int8 dynamic quantization")
+    if isinstance(config.layout, SemiSparseLayout):
+        _check_semi_sparse_weight(weight)
     if config.act_mapping_type != MappingType.SYMMETRIC:
         raise NotImplementedError("asymmetric activation quantization is out of scope")
     input_quant_func = (
@@ -424,6 +440,23 @@ def _int8_dynamic_activation_int8_weight_transform(
     return _swap_weight(
         module, _int8_dynamic_activation_int8_weight_quantize_tensor(module.weight, config)
     )
+
+
+def _int8_dynamic_activation_int8_weight_precheck(module, config):
+    """Layouts other than PlainLayout and SemiSparseLayout, and weights the 2:4 sparse linear does
+    not serve, are refused for every selected module before any weight is swapped."""
+    if not isinstance(config.layout, (PlainLayout, SemiSparseLayout)):
+        raise NotImplementedError("only PlainLayout is supported for int8 dynamic quantization")
+    if isinstance(config.layout, SemiSparseLayout) and hasattr(module, "weight"):
+        if module.weight.shape[-1] <= 16:  # the handler leaves such a module as it is
+            return
+        _check_semi_sparse_weight(module.weight)
+
+
+# quantize_ runs this over every selected module before the first swap
+_int8_dynamic_activation_int8_weight_transform.precheck = (
+    _int8_dynamic_activation_int8_weight_precheck
+)
 
 
 # ---------------------------------------------------------------------------------------------
