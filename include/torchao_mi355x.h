@@ -388,6 +388,34 @@ int tao_int8_sp24_dyn_linear_bf16(const uint16_t* x, const int8_t* values, const
                                   const uint16_t* ws, const uint16_t* bias, uint16_t* y, int64_t M,
                                   int64_t N, int64_t K, void* stream);
 
+/* ---- 2:4 sparse int4 weight-only linear (csrc/int4_sparse24.hip) ---------------------------------
+ * Storage of a dense weight of uint4 codes [N][K] (symmetric, zero point 8; K % 128 == 0) with at
+ * most two codes != 8 in every aligned group of four k: values int32 [N][K/16] (dword j: the eight
+ * kept codes of dense k 16 j .. 16 j + 15, code i in bits [4i+3:4i], ascending position), meta
+ * int32 [N][K/32] (as tao_int8_sp24_compress) and scale bf16 [K/group_size][N]: 0.375 B per dense
+ * weight plus scales. codes are int32 [N][K], what get_plain() returns. Replaces the Marlin 2:4
+ * pre-packing of MarlinSparseAQTTensorImpl.from_plain
+ * (torchao/dtypes/uintx/marlin_sparse_layout.py:170-224, torchao/sparsity/marlin). A group with more
+ * than two codes != 8 ORs 1 into *err (int32 in device memory, zeroed by the caller). */
+int tao_int4_sp24_compress(const int32_t* codes, int32_t* values, int32_t* meta, int32_t* err,
+                           int64_t N, int64_t K, void* stream);
+
+/* The inverse: int32 codes [N][K] (8 at pruned positions) from (values, meta). Replaces the
+ * unpacking of MarlinSparseAQTTensorImpl.get_plain
+ * (torchao/dtypes/uintx/marlin_sparse_layout.py:139-168, torchao/sparsity/marlin). */
+int tao_int4_sp24_decompress(const int32_t* values, const int32_t* meta, int32_t* codes, int64_t N,
+                             int64_t K, void* stream);
+
+/* y[M][N] = bf16( sum_g scale[g][n] * sum_{k in g} x[m][k] (q[n][k] - 8) + bias[n] ), fp32 sums,
+ * one rounding; x, bias, y bf16. Few tokens: a GEMV over values + meta; more: a GEMM on
+ * v_smfmac_f32_16x16x64_bf16 (route: csrc/int4_sparse24_host.h). Replaces
+ * torchao.ops.marlin_24_gemm as called by _linear_fp_act_int4_weight_sparse_marlin_impl
+ * (torchao/dtypes/uintx/marlin_sparse_layout.py:37-74, torchao/sparsity/marlin), CUDA and fp16 only
+ * there. K % 128 == 0, group_size 128 or K, M < 2^20; x, values 16-B, meta, scale, y 8-B aligned. */
+int tao_int4_sp24_linear_bf16(const uint16_t* x, const int32_t* values, const int32_t* meta,
+                              const uint16_t* scale, const uint16_t* bias, uint16_t* y, int64_t M,
+                              int64_t N, int64_t K, int64_t group_size, void* stream);
+
 /* SmoothQuant activation quantization of x [M][K] bf16 in one launch: t = bf16(x / smooth)
  * (tao_act_prescale_bf16's bits; smooth bf16 [K]; t is never written), then
  *   act_scale == NULL (dynamic): s[m] = max(bf16(amax(|t[m]|) / 127), 2^-7), the default eps of

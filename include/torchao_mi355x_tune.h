@@ -251,6 +251,17 @@ int tao_tune_sp24(int route, int max_gemv_m, int rows_per_wave, int waves_k, int
 /* Launch shape of the sparse MFMA GEMM (0 = built-in): tokens per tile 16 / 32 / 64, waves of 16
  * output features per k-group 1 / 2 / 4, and the most k-groups per workgroup. */
 int tao_tune_sp24_gemm(int bm, int waves_n, int k_groups);
+/* The route tao_int4_sp24_linear_bf16 takes for this call under the calling thread's
+ * tao_tune_int4_sp24: 1 = the sparse GEMV (up to the built-in boundary M of
+ * csrc/int4_sparse24_host.h, where the tokens fit LDS), 2 = the sparse MFMA GEMM. */
+int tao_int4_sp24_route(int64_t M, int64_t N, int64_t K);
+/* Route and launch shapes of the 2:4 sparse int4 linear (calling thread only; tests and A/B runs):
+ * route 0 = built-in rule, 1 = the GEMV at every M (launches over 8-token pieces), 2 = the sparse
+ * MFMA GEMM at every M; max_gemv_m, rows_per_wave, waves_k, row_groups as tao_tune_nf4's; then the
+ * GEMM's tokens per tile 16 / 32 / 64, waves of 16 output features per k-group 1 / 2 / 4 and the
+ * most k-groups per workgroup (0 = built-in). */
+int tao_tune_int4_sp24(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups,
+                       int bm, int waves_n, int k_groups);
 /* The MFMA route of the FP6 linear (the Fp6WO policy of gemm_mfma_kernel, reading the 6-bit
  * storage in place): 0 = built-in route, 1 = every call the rule would send to dequantize + matmul
  * runs on the MFMA GEMM inside tao_fp6_linear_bf16 instead, and tao_fp6_linear_route returns 3

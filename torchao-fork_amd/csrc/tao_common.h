@@ -118,6 +118,8 @@ struct Tuning {
   int moe_bm = 0, moe_dual = 0;                  // grouped (MoE) int4 GEMM row tile / dual form (tao_tune_moe)
   WoTune sp24;                                   // 2:4 sparse int8 linear (tao_tune_sp24; route 2 = sparse MFMA GEMM)
   int sp24_bm = 0, sp24_nwv = 0, sp24_kg = 0;    // sparse MFMA GEMM shape (tao_tune_sp24_gemm)
+  WoTune i4sp24;                                 // 2:4 sparse int4 linear (tao_tune_int4_sp24; route 2 = sparse MFMA GEMM)
+  int i4sp24_bm = 0, i4sp24_nwv = 0, i4sp24_kg = 0;  // its GEMM shape
 };
 Tuning& tuning();
 

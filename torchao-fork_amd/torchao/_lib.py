@@ -94,6 +94,11 @@ _SIGNATURES = {
     "tao_int8_sp24_route": [_i64, _i64, _i64],
     "tao_tune_sp24": [_int, _int, _int, _int, _int],
     "tao_tune_sp24_gemm": [_int, _int, _int],
+    "tao_int4_sp24_compress": [_p, _p, _p, _p, _i64, _i64, _p],
+    "tao_int4_sp24_decompress": [_p, _p, _p, _i64, _i64, _p],
+    "tao_int4_sp24_linear_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p],
+    "tao_int4_sp24_route": [_i64, _i64, _i64],
+    "tao_tune_int4_sp24": [_int, _int, _int, _int, _int, _int, _int, _int],
     "tao_int8_quant_per_token_f32": [_p, _p, _p, _i64, _i64, _p],
     "tao_int4_quantize_rows_packed_bf16": [_p, _p, _p, _i64, _i64, _p],
     "tao_w4a8_scaled_mm_bf16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],

@@ -25,6 +25,8 @@ from .floatx import (
 from .uintx import (
     CutlassInt4PackedLayout,
     Int4PackedTensorImpl,
+    MarlinSparseAQTTensorImpl,
+    MarlinSparseLayout,
     PlainAQTTensorImpl,
     SemiSparseAQTTensorImpl,
     SemiSparseLayout,
@@ -44,6 +46,8 @@ __all__ = [
     "PlainLayout",
     "PlainAQTTensorImpl",
     "SemiSparseLayout",
+    "MarlinSparseLayout",
+    "MarlinSparseAQTTensorImpl",
     "SemiSparseAQTTensorImpl",
     "TensorCoreTiledLayout",
     "TensorCoreTiledAQTTensorImpl",

@@ -34,6 +34,10 @@ from torchao.dtypes.uintx.cutlass_int4_packed_layout import (
     _linear_int8_act_int4_weight_cutlass_check,
     _linear_int8_act_int4_weight_cutlass_impl,
 )
+from torchao.dtypes.uintx.marlin_sparse_layout import (
+    _linear_fp_act_int4_weight_sparse_marlin_check,
+    _linear_fp_act_int4_weight_sparse_marlin_impl,
+)
 from torchao.dtypes.uintx.plain_layout import (
     _linear_fp_act_int8_weight_check,
     _linear_fp_act_int8_weight_impl,
@@ -94,6 +98,7 @@ for _cond, _impl in [
     (_linear_int8_act_int8_weight_check, _linear_int8_act_int8_weight_impl),
     (_linear_int8_act_int8_sp24_weight_check, _linear_int8_act_int8_sp24_weight_impl),
     (_linear_fp_act_int8_weight_check, _linear_fp_act_int8_weight_impl),
+    (_linear_fp_act_int4_weight_sparse_marlin_check, _linear_fp_act_int4_weight_sparse_marlin_impl),
     (_linear_bf16_act_uint4_weight_check, _linear_bf16_act_uint4_weight_impl),
     (_linear_fp_act_fp8_weight_check, _linear_fp_act_fp8_weight_impl),
     (_linear_fp8_act_fp8_weight_check, _linear_fp8_act_fp8_weight_impl),

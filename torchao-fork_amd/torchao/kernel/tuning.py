@@ -65,6 +65,10 @@ _KNOBS = {
     # sparse MFMA GEMM: (tokens per tile 16 / 32 / 64, waves of 16 features per k-group 1 / 2 / 4,
     # most k-groups per workgroup); 0 = built-in
     "sp24_gemm": ("tao_tune_sp24_gemm", 3),
+    # 2:4 sparse int4 weight-only linear: (route 0 auto / 1 gemv / 2 sparse MFMA gemm, max_gemv_m,
+    # rows per wave, waves along K, row groups, GEMM tokens per tile, waves of 16 features per
+    # k-group, most k-groups); 0 = built-in
+    "int4_sp24": ("tao_tune_int4_sp24", 8),
     # (rows per tile of the grouped MoE GEMM: 0 built-in, 16, 32, 64; gate and up: 0 built-in,
     # 1 = two launches, 2 = one)
     "moe": ("tao_tune_moe", 2),

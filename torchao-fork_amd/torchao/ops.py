@@ -1951,6 +1951,155 @@ for _name, _cpu, _cuda in [
 
 
 # ---------------------------------------------------------------------------------------------
+# 2:4 sparse int4 weight-only linear (csrc/int4_sparse24.hip), MarlinSparseLayout
+# ---------------------------------------------------------------------------------------------
+# Storage: codes are uint4 with zero point 8 (int32 [N, K], what get_plain() returns; a pruned weight
+# is code 8). values int32 [N, K/16]: dword j holds the eight kept codes of dense k 16 j .. 16 j + 15,
+# code i in bits [4i+3:4i], ascending position; meta int32 [N, K/32] as int8_sp24's; scale
+# [K/group_size, N]. On CPU tensors every op evaluates its definition in plain torch.
+lib_int4_sp24 = torch.library.Library("torchao", "FRAGMENT")
+lib_int4_sp24.define("int4_sp24_compress(Tensor codes) -> (Tensor, Tensor, Tensor)")
+lib_int4_sp24.define("int4_sp24_decompress(Tensor values, Tensor meta) -> Tensor")
+lib_int4_sp24.define("int4_sp24_weight_only_linear(Tensor x, Tensor values, Tensor meta, "
+                     "Tensor scale, int group_size, Tensor? bias=None) -> Tensor")
+
+
+def _check_int4_sp24_codes(codes):
+    torch._check(codes.dim() == 2 and codes.dtype is torch.int32,
+                 lambda: "codes must be a 2D int32 tensor")
+    torch._check(codes.size(1) % 128 == 0,
+                 lambda: f"K ({codes.size(1)}) must be a multiple of 128")
+    return codes.shape
+
+
+def _check_int4_sp24_weight(values, meta, scale=None, group_size=None):
+    torch._check(values.dim() == 2 and values.dtype is torch.int32,
+                 lambda: "values must be a 2D int32 [N, K/16] tensor")
+    N, K = values.size(0), values.size(1) * 16
+    torch._check(K % 128 == 0, lambda: f"K ({K}) must be a multiple of 128")
+    torch._check(meta.dtype is torch.int32 and tuple(meta.shape) == (N, K // 32),
+                 lambda: f"meta must be int32 [N, K/32] = ({N}, {K // 32}), got "
+                         f"{meta.dtype} {tuple(meta.shape)}")
+    if scale is not None:
+        torch._check(group_size == 128 or group_size == K,
+                     lambda: f"group_size ({group_size}) must be 128 or K ({K})")
+        torch._check(tuple(scale.shape) == (K // group_size, N),
+                     lambda: f"scale must be [K/group_size, N] = ({K // group_size}, {N}), got "
+                             f"{tuple(scale.shape)}")
+    return N, K
+
+
+def _int4_sp24_compress_ref(codes: Tensor):
+    """(values, meta, err) of int32 codes [N, K]: of every group of four, its non-8 positions
+    ascending, padded with its lowest code-8 positions, sorted; err[0] = 1 where a group has more
+    than two codes != 8 (its lowest two are kept)."""
+    N, K = _check_int4_sp24_codes(codes)
+    g = (codes & 15).to(torch.int64).reshape(N, K // 4, 4)
+    nz = g != 8
+    key = (~nz).to(torch.int64) * 4 + torch.arange(4, device=codes.device)
+    pos = key.argsort(dim=-1)[..., :2].sort(dim=-1).values
+    kept = torch.gather(g, -1, pos).reshape(N, K // 16, 8)
+    v = (kept << (4 * torch.arange(8, device=codes.device))).sum(-1)
+    code = (pos[..., 0] | (pos[..., 1] << 2)).reshape(N, K // 32, 8)
+    m = (code << (4 * torch.arange(8, device=codes.device))).sum(-1)
+    wrap = lambda t: torch.where(t >= 2 ** 31, t - 2 ** 32, t).to(torch.int32)
+    err = (nz.sum(-1) > 2).any().to(torch.int32).reshape(1)
+    return wrap(v), wrap(m), err
+
+
+def _int4_sp24_decompress_ref(values: Tensor, meta: Tensor) -> Tensor:
+    N, K = _check_int4_sp24_weight(values, meta)
+    ar = 4 * torch.arange(8, device=meta.device)
+    kept = (((values.to(torch.int64) & 0xFFFFFFFF).unsqueeze(-1) >> ar) & 0xF).reshape(
+        N, K // 4, 2)
+    code = (((meta.to(torch.int64) & 0xFFFFFFFF).unsqueeze(-1) >> ar) & 0xF).reshape(N, K // 4)
+    pos = torch.stack([code & 3, code >> 2], dim=-1)
+    w = torch.full((N, K // 4, 4), 8, dtype=torch.int64, device=values.device)
+    w.scatter_(-1, pos, kept)
+    return w.reshape(N, K).to(torch.int32)
+
+
+def _int4_sp24_linear_cpu(x, values, meta, scale, group_size, bias=None):
+    """F.linear on the dequantized weight (codes - 8) * scale, in x's dtype."""
+    _check_int4_sp24_weight(values, meta, scale, group_size)
+    q = (_int4_sp24_decompress_ref(values, meta) - 8).to(torch.float32)
+    w = q * scale.t().to(torch.float32).repeat_interleave(group_size, dim=1)
+    return torch.nn.functional.linear(x, w.to(x.dtype), None if bias is None else bias.to(x.dtype))
+
+
+@torch.library.register_fake("torchao::int4_sp24_compress")
+def _(codes):
+    N, K = _check_int4_sp24_codes(codes)
+    return (codes.new_empty((N, K // 16)), codes.new_empty((N, K // 32)), codes.new_empty((1,)))
+
+
+@torch.library.register_fake("torchao::int4_sp24_decompress")
+def _(values, meta):
+    N, K = _check_int4_sp24_weight(values, meta)
+    return values.new_empty((N, K))
+
+
+@torch.library.register_fake("torchao::int4_sp24_weight_only_linear")
+def _(x, values, meta, scale, group_size, bias=None):
+    N, K = _check_int4_sp24_weight(values, meta, scale, group_size)
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    return x.new_empty(_linear_out_shape(x, N))
+
+
+def _int4_sp24_compress_cuda(codes):
+    N, K = _check_int4_sp24_codes(codes)
+    codes = codes.contiguous()
+    values = torch.empty((N, K // 16), dtype=torch.int32, device=codes.device)
+    meta = torch.empty((N, K // 32), dtype=torch.int32, device=codes.device)
+    err = torch.zeros((1,), dtype=torch.int32, device=codes.device)
+    with torch.cuda.device(codes.device):
+        _lib.call("tao_int4_sp24_compress", _ptr(codes), _ptr(values), _ptr(meta), _ptr(err), N,
+                  K, _stream(codes))
+    return values, meta, err
+
+
+def _int4_sp24_decompress_cuda(values, meta):
+    N, K = _check_int4_sp24_weight(values, meta)
+    _same_device(values, meta=meta)
+    values, meta = values.contiguous(), meta.contiguous()
+    codes = torch.empty((N, K), dtype=torch.int32, device=values.device)
+    with torch.cuda.device(values.device):
+        _lib.call("tao_int4_sp24_decompress", _ptr(values), _ptr(meta), _ptr(codes), N, K,
+                  _stream(values))
+    return codes
+
+
+def _int4_sp24_linear_cuda(x, values, meta, scale, group_size, bias=None):
+    N, K = _check_int4_sp24_weight(values, meta, scale, group_size)
+    torch._check(x.dtype is torch.bfloat16,
+                 lambda: "int4_sp24_weight_only_linear (HIP) needs bf16 x")
+    torch._check(x.size(-1) == K, lambda: f"x last dim {x.size(-1)} != K {K}")
+    _same_device(x, values=values, meta=meta, scale=scale, bias=bias)
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous() or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    M = x2.size(0)
+    values, meta = values.contiguous(), meta.contiguous()
+    scale = scale.to(torch.bfloat16).contiguous()
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("tao_int4_sp24_linear_bf16", _ptr(x2), _ptr(values), _ptr(meta), _ptr(scale),
+                  _ptr(bias), _ptr(y), M, N, K, group_size, _stream(x))
+    return y.reshape(_linear_out_shape(x, N))
+
+
+for _name, _cpu, _cuda in [
+    ("int4_sp24_compress", _int4_sp24_compress_ref, _int4_sp24_compress_cuda),
+    ("int4_sp24_decompress", _int4_sp24_decompress_ref, _int4_sp24_decompress_cuda),
+    ("int4_sp24_weight_only_linear", _int4_sp24_linear_cpu, _int4_sp24_linear_cuda),
+]:
+    lib_int4_sp24.impl(_name, _cpu, "CPU")
+    lib_int4_sp24.impl(_name, _cuda, "CUDA")
+
+
+# ---------------------------------------------------------------------------------------------
 # NF4 (csrc/nf4.hip): fake kernels only; the CUDA kernels are C++ (csrc/torch_ops.cpp)
 # ---------------------------------------------------------------------------------------------
 def _check_nf4_parts(codes, qscalers, qfactor, mean, levels, numel, op):

@@ -39,6 +39,7 @@ from torchao.dtypes.affine_quantized_tensor import (
 )
 from torchao.dtypes.floatx.float8_layout import Float8Layout, Float8MMConfig
 from torchao.dtypes.uintx.cutlass_int4_packed_layout import CutlassInt4PackedLayout
+from torchao.dtypes.uintx.marlin_sparse_layout import MarlinSparseLayout
 from torchao.dtypes.uintx.plain_layout import PlainAQTTensorImpl
 from torchao.dtypes.uintx.tensor_core_tiled_layout import TensorCoreTiledLayout
 from torchao.dtypes.uintx.semi_sparse_layout import SemiSparseLayout
@@ -80,8 +81,11 @@ __all__ = [
     "LAYOUT_TO_PRESERVE_ZEROS",
 ]
 
-LAYOUT_TO_ZERO_POINT_DOMAIN = {TensorCoreTiledLayout: [ZeroPointDomain.FLOAT]}
-LAYOUT_TO_PRESERVE_ZEROS = {TensorCoreTiledLayout: False}
+LAYOUT_TO_ZERO_POINT_DOMAIN = {
+    TensorCoreTiledLayout: [ZeroPointDomain.FLOAT],
+    MarlinSparseLayout: [ZeroPointDomain.INT],
+}
+LAYOUT_TO_PRESERVE_ZEROS = {TensorCoreTiledLayout: False, MarlinSparseLayout: True}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -221,7 +225,8 @@ class Int4WeightOnlyConfig(AOBaseConfig):
     """
 
     group_size: int = 128
-    layout: Optional[TensorCoreTiledLayout] = TensorCoreTiledLayout(inner_k_tiles=8)
+    layout: Optional[Union[TensorCoreTiledLayout, MarlinSparseLayout]] = TensorCoreTiledLayout(
+        inner_k_tiles=8)
     use_hqq: bool = False
     zero_point_domain: Optional[ZeroPointDomain] = ZeroPointDomain.NONE
     set_inductor_config: bool = True
@@ -262,9 +267,17 @@ def _int4_weight_only_quantize_tensor(weight: torch.Tensor, config: Int4WeightOn
         else LAYOUT_TO_PRESERVE_ZEROS[type(layout)]
     )
     block_size = tuple([1] * (weight.ndim - 1) + [group_size])
+    mapping_type = MappingType.ASYMMETRIC
+    if isinstance(layout, MarlinSparseLayout):
+        # the 2:4 sparse int4 linear is symmetric (zero point 8), per group of 128 or per channel
+        mapping_type = MappingType.SYMMETRIC
+        assert group_size == 128 or group_size == weight.shape[-1], (
+            "MarlinSparseLayout only supports 128 group size or per channel quantization, got "
+            f"{group_size}"
+        )
     return to_affine_quantized_intx(
         weight,
-        MappingType.ASYMMETRIC,
+        mapping_type,
         block_size,
         torch.int32,
         0,
@@ -284,12 +297,33 @@ def _swap_weight(module: nn.Module, new_weight: torch.Tensor) -> nn.Module:
     return module
 
 
+def _int4_weight_only_precheck(module: nn.Module, config: Int4WeightOnlyConfig) -> None:
+    """What the 2:4 sparse int4 linear (csrc/int4_sparse24.hip) does not serve is refused for every
+    selected module before any weight is swapped."""
+    if not isinstance(config.layout, MarlinSparseLayout):
+        return
+    if config.use_hqq:
+        raise NotImplementedError(
+            "Int4WeightOnlyConfig(use_hqq=True) is not implemented for MarlinSparseLayout")
+    weight = getattr(module, "weight", None)
+    if weight is None or weight.shape[-1] % config.group_size != 0:  # the handler skips these
+        return
+    if weight.dim() != 2 or weight.shape[-1] % 128 != 0:
+        raise NotImplementedError(
+            "MarlinSparseLayout serves 2-D weights whose in_features are a multiple of 128, got "
+            f"{tuple(weight.shape)}"
+        )
+
+
 @register_quantize_module_handler(Int4WeightOnlyConfig)
 def _int4_weight_only_transform(module: nn.Module, config: Int4WeightOnlyConfig) -> nn.Module:
     if config.set_inductor_config:
         torchao.quantization.utils.recommended_inductor_config_setter()
     assert hasattr(module, "weight"), "int4 weight-only quant requires a module with a weight"
     return _swap_weight(module, _int4_weight_only_quantize_tensor(module.weight, config))
+
+
+_int4_weight_only_transform.precheck = _int4_weight_only_precheck
 
 
 # ---------------------------------------------------------------------------------------------
