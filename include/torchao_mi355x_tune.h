@@ -233,13 +233,21 @@ int tao_tune_fp6(int route, int max_gemv_m, int rows_per_wave, int waves_k, int 
 /* The route torchao::nvfp4_linear takes for this call under the calling thread's tao_tune_nvfp4:
  * 1 = the GEMV, tao_nvfp4_linear_bf16 (up to the built-in boundary M of csrc/nvfp4_host.h);
  * 2 = tao_nvfp4_dequant_bf16 into a temporary and the bf16 matmul (after tao_nvfp4_act_qdq_bf16 in
- * DYNAMIC mode), which needs an allocator and lives in the op (csrc/torch_ops.cpp). */
+ * DYNAMIC mode), which needs an allocator and lives in the op (csrc/torch_ops.cpp);
+ * 3 = the MFMA GEMM, tao_nvfp4_linear_bf16 too (only under tao_tune_nvfp4_mfma; after
+ * tao_nvfp4_act_qdq_bf16 in DYNAMIC mode). */
 int tao_nvfp4_linear_route(int64_t M, int64_t N, int64_t K);
 /* 1 where tao_nvfp4_linear_bf16 takes dynamic = 1 (one token whose snapped copy fits LDS). */
 int tao_nvfp4_linear_fused_snap(int64_t M, int64_t K);
 /* Route and launch shape of the NVFP4 linear (calling thread only; tests and A/B runs); the
  * arguments of tao_tune_nf4. */
 int tao_tune_nvfp4(int route, int max_gemv_m, int rows_per_wave, int waves_k, int row_groups);
+/* The MFMA route of the NVFP4 linear (the Nvfp4WO policy of gemm_mfma_kernel, reading the codes
+ * and the scale bytes in place, either scale layout): 0 = built-in route, 1 = every call the rule
+ * would send to dequantize + matmul runs on the MFMA GEMM inside tao_nvfp4_linear_bf16 instead,
+ * and tao_nvfp4_linear_route returns 3 where it returned 2. A route forced through tao_tune_nvfp4
+ * (1 or 2) still wins, and its max_gemv_m still moves the GEMV boundary. Calling thread only. */
+int tao_tune_nvfp4_mfma(int on);
 /* The route tao_int8_sp24_scaled_mm_bf16 takes for this call under the calling thread's
  * tao_tune_sp24: 1 = the sparse GEMV (up to the built-in boundary M of csrc/sparse24_host.h, where
  * the tokens fit LDS), 2 = the sparse MFMA GEMM. */

@@ -1,6 +1,6 @@
 // Skinny GEMM on MFMA for the quantized linears at M > 4 (prefill / batched decode):
 //   y[M][N] = epilogue( x[M][K] . W[N][K]^T )
-// eleven weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
+// twelve weight/activation formats share one kernel template (the policies: gemm_mfma_policy.h):
 //   UintxWO : bf16 x, 1- to 7-bit group-quant W read from its bit-sliced shards, x gathered in the
 //             shards' segment order, per-group scale and zero point applied to each MFMA's fp32
 //             product,                                               v_mfma_f32_16x16x32_bf16
@@ -9,6 +9,8 @@
 //   Fp8WO   : bf16 x, e4m3fn per-channel W (fp32 scales),            v_mfma_f32_16x16x32_bf16
 //   Fp6WO   : bf16 x, OCP FP6 (e3m2 / e2m3) per-channel W read from its 6-bit stream, decoded by
 //             v_cvt_scalef32_pk32_bf16_{bf6,fp6},                    v_mfma_f32_16x16x32_bf16
+//   Nvfp4WO : bf16 x, NVFP4 W (e2m1 codes, one e4m3 scale byte per 16, either scale layout) read
+//             in place, decoded and scaled to exact bf16 in registers, v_mfma_f32_16x16x32_bf16
 //   Int8Dyn : int8 x (per-token scale), int8 W (per-channel scale),   v_mfma_i32_16x16x64_i8
 //   Int8DynW4: int8 x (per-token fp32 scale), int4 W two per byte (per-channel fp32 scale),
 //             expanded to int8 x 16 in registers,                    v_mfma_i32_16x16x64_i8
@@ -41,6 +43,7 @@
 
 #include "fp8_dyn_host.h"
 #include "gemm_mfma_policy.h"
+#include "nvfp4_host.h"
 #include "tao_gemm.h"
 #include "uintx_host.h"
 
@@ -410,6 +413,8 @@ __global__ __launch_bounds__(256 * KG) TAO_GEMM_WPE_ATTR void gemm_mfma_kernel(
     const int nn = bn[c] < N ? bn[c] : N - 1;
     if constexpr (!P::kColF)
       colf[c] = 1.f;
+    else if constexpr (P::kColUniform)
+      colf[c] = pol.col_uniform();  // one factor for all columns, from device memory (Nvfp4WO)
     else if constexpr (std::is_same_v<decltype(pol.col_factor()), const float*>)
       colf[c] = pol.col_factor()[nn];  // fp32 factors (Fp8WO)
     else
@@ -769,6 +774,32 @@ int uintx_mm_launch<TAO_GEMM_UINTX_TU>(const uint16_t* x, const uint8_t* s4, con
 }
 
 }  // namespace tao
+#elif defined(TAO_GEMM_NVFP4_TU)
+// The Nvfp4WO instances: one more object of this file (Makefile), with the packed fp32
+// instructions its fragments use, holding nvfp4_mm_launch and nothing else.
+// NVFP4 (nvfp4.hip): the calls its route rule gives to the MFMA route (nvfp4_host.h)
+int nvfp4_mm_launch(const uint16_t* x, const uint8_t* qdata, const uint8_t* scales,
+                    const float* w_pts, const float* a_pts, const uint16_t* bias, uint16_t* y,
+                    int M, int N, int K, int swizzled, hipStream_t stream) {
+  // one buffer descriptor per operand, 32-bit byte counts and offsets (a lane's offset runs up to
+  // one step past the end of the codes or the scales before the range check drops it)
+  constexpr int64_t kMaxBytes = (1LL << 32) - 4096;
+  TAO_CHECK_ARG((int64_t)N * (K / 2) <= kMaxBytes &&
+                    nvfp4_scale_bytes(N, K, swizzled != 0) <= kMaxBytes &&
+                    (int64_t)M * K * 2 <= kMaxBytes,
+                "nvfp4 linear (MFMA route): codes and scales (N x K = %d x %d) and x (M = %d) must "
+                "each be below 4 GiB", N, K, M);
+  auto go = [&](auto pol) {
+    pol.wq = reinterpret_cast<const uint4*>(qdata);
+    pol.ws = scales;
+    pol.w_pts = w_pts;
+    pol.a_pts = a_pts;
+    return launch_gemm(x, pol, bias, y, M, N, K, stream);
+  };
+  return swizzled ? go(Nvfp4WO<true>{}) : go(Nvfp4WO<false>{});
+}
+
+}  // namespace tao
 #else
 // the skinny-M crossover, for the single-fetch partials entry (gemm_sf.hip), which serves only
 // shapes the plain linear runs on the single-fetch kernel
@@ -1015,4 +1046,4 @@ extern "C" int tao_tune_gemm(int m_tile, int k_groups, int splits) {
   tao::tuning().splits = splits;
   return TAO_OK;
 }
-#endif  // TAO_GEMM_FP6_TU / TAO_GEMM_UINTX_TU
+#endif  // TAO_GEMM_FP6_TU / TAO_GEMM_UINTX_TU / TAO_GEMM_NVFP4_TU

@@ -52,6 +52,7 @@ struct PolicyDefaults {
   // whether the instance (BM, KG, NW) is built: its one LDS array must fit (Fp6WO overrides)
   static constexpr bool fits(int, int, int) { return true; }
   static constexpr bool kRowF = false, kColF = false;  // no per-row / per-column factor
+  static constexpr bool kColUniform = false;  // (kColF) one factor for every column: col_uniform()
   __device__ __forceinline__ const uint16_t* row_factor() const { return nullptr; }
   __device__ __forceinline__ const uint16_t* col_factor() const { return nullptr; }
 };
@@ -620,6 +621,151 @@ struct UintxWO : PolicyDefaults {
   }
   // the GEMV's output (uintx.hip): bf16(sum); the bias add and its rounding follow in the kernel
   __device__ __forceinline__ float epi(float acc, float, float) const { return round_bf16(acc); }
+};
+
+// Nvfp4WO<SWZ>: bf16 x, NVFP4 W (nvfp4.hip) read in place: e2m1 codes two per byte, element 2 j of
+// a row in the HIGH nibble of byte j, one e4m3fn scale byte per 16 codes, row-major [N][K / 16]
+// (SWZ false) or in the swizzled 128 x 4 layout (SWZ true; nvfp4_scale_offset, nvfp4_host.h), and
+// optional fp32 per-tensor scales in device memory. Int4WO's tile: 256 k per step = 128 B of codes
+// per row, one full line (LineLoader<128>) regrouped through the 2-KiB per-wave stage, after which
+// lane (n, kq) holds the 16-B chunks kq and 4 + kq of row n, 32 k each; MFMA s = 4 h + t takes
+// dword t of chunk 4 h + kq, the 8 k of x slot 4 (4 h + kq) + t (Int4WO's slot map and x mask).
+//  * Scales: a row has 16 scale bytes per step. Chunk c is blocks 2 c and 2 c + 1, so lane (n, kq)
+//    loads the byte pairs at scale columns 16 st + 2 kq and 16 st + 8 + 2 kq of row n: two aligned
+//    2-B loads per step riding in the weight ring, adjacent bytes in either layout (K % 64 == 0
+//    makes a row a multiple of four columns, so the swizzled layout has no column padding). All
+//    layout arithmetic is in setup(): a step advances the offset by 16 B (row-major) or by four
+//    column tiles = 2048 B (swizzled), a chunk's second pair lies 8 B or 1024 B on. Rows past N are
+//    clamped to N - 1, so the swizzled layout's zero-padded rows are never addressed.
+//  * Every step offset rides in the vector offset, which the descriptor's range check covers (the
+//    scalar one is not checked): past the end of the codes or the scales a K tail reads 0.
+//  * K tail: inside the buffers a tail reads the next row's codes and whatever scale bytes follow,
+//    and a scale byte may be a NaN (0x7F / 0xFF). The weight would then be NaN and NaN x 0 reaches
+//    the accumulator whatever the LDS store zeroes in x, so the scale bytes of a chunk past K are
+//    replaced by 0 (kMaskTail; K % 32 == 0: a chunk is wholly inside the row or wholly past it).
+//    The codes need no mask: every e2m1 value is finite, and value x 0 x 0 adds exactly 0.
+//  * Fragment: v_cvt_scalef32_pk_bf16_fp4 applies only the exponent of its scale operand
+//    (nvfp4.hip), and gfx950 has no packed bf16 multiply for the 3-bit mantissa factor that would
+//    remain: that form goes through fp32 as well and splits every scale byte on top. So each byte
+//    of a code dword is decoded at unit scale by one v_cvt_scalef32_pk_f32_fp4, the pair is
+//    multiplied by its block's fp32 scale with one v_pk_mul_f32 and packed by one
+//    v_cvt_pk_bf16_f32: 12 VALU per 8 weights, each step exact (value x scale has at most 2 + 4
+//    significant bits and lies in [2^-10, 2688]). The four scale bytes become fp32 with two
+//    v_cvt_scalef32_pk_f32_fp8 per step (the eight frag() calls share them).
+//  * Nibble order: the converter emits (low nibble, high nibble) = (w[2 j + 1], w[2 j]). The weight
+//    is left alone; instead every x dword is rotated by 16 bits on its way into the LDS image
+//    (kXPerm / xperm(): four v_alignbit_b32 per 16-B piece per workgroup, nothing per weight).
+//  * Epilogue: alpha = the per-tensor scales present, multiplied, read once per lane before the
+//    weights (kColUniform); bf16(acc * alpha + bias) in fp32, one rounding: the GEMV's formula.
+template <bool SWZ>
+struct Nvfp4WO : PolicyDefaults {
+  static constexpr int kPathId = 11;  // no measured table entries: the heuristic shapes
+  static constexpr bool kMaskTail = true;
+  static constexpr bool kXPerm = true;
+  static constexpr int kABytes = 2;   // bf16 x
+  static constexpr int kKStep = 256;  // 128 B of codes per row per step: one full line
+  static constexpr int kMfma = 8;
+  static constexpr int kMaxBM = 64;  // 512-B x rows, as Int4WO
+  static constexpr int kPrefKG = 2;
+  static constexpr int kMinSlice = 4;
+  typedef LineLoader<128> Lines;
+  static constexpr int kStage = Lines::kStage;
+  static constexpr uint32_t kScaleStep = SWZ ? 2048u : 16u;  // scale bytes a step advances
+  static constexpr uint32_t kScaleHalf = SWZ ? 1024u : 8u;   // chunk 4 + kq's pair after chunk kq's
+  const uint4* wq;     // [N][K/32] 16-B chunks of codes
+  const uint8_t* ws;   // e4m3fn scale bytes
+  const float* w_pts;  // per-tensor scales (device memory), or null
+  const float* a_pts;
+  struct Lane {
+    Lines::Lane c;
+    Rsrc s;
+    uint32_t sv;  // byte offset of the scale pair of chunk kq of row n at step 0
+  };
+  struct Chunk {
+    Lines::Chunk c;
+    uint32_t s0, s1;  // the scale pairs of chunks kq and 4 + kq
+  };
+  struct Prep {
+    uint32_t w[8];  // dwords of chunks kq (0..3) and 4 + kq (4..7)
+    uint32_t sc;    // scale bytes of blocks 2 kq, 2 kq + 1, 8 + 2 kq, 9 + 2 kq of the step
+  };
+  __device__ __forceinline__ Lane setup(int bn, int lane, int N, int K) const {
+    const uint32_t n = bn < N ? bn : N - 1, kq = lane >> 4;
+    const uint32_t scols = (uint32_t)K >> 4;  // scale bytes per row, a multiple of 4
+    Lane L;
+    L.c.w = make_rsrc(wq, (uint32_t)N * (uint32_t)(K >> 1));
+    Lines::offsets(L.c, (uint32_t)(K >> 1), bn, lane, N);
+    if constexpr (SWZ) {
+      // nvfp4_scale_offset(n, 2 kq, scols / 4): tile row n / 128 of scols / 4 tiles of 512 B
+      L.s = make_rsrc(ws, (((uint32_t)N + 127u) & ~127u) * scols);
+      L.sv = (n >> 7) * (scols * 128u) + (n & 31u) * 16u + ((n & 127u) >> 5) * 4u +
+             (kq >> 1) * 512u + (kq & 1u) * 2u;
+    } else {
+      L.s = make_rsrc(ws, (uint32_t)N * scols);
+      L.sv = n * scols + 2u * kq;
+    }
+    return L;
+  }
+  __device__ __forceinline__ Chunk load(const Lane& L, int st) const {
+    Chunk ch;
+    ch.c.v[0] = bload16<kNT>(L.c.w, L.c.wv0 + (uint32_t)st * 128u, 0);
+    ch.c.v[1] = bload16<kNT>(L.c.w, L.c.wv1 + (uint32_t)st * 128u, 0);
+    const uint32_t so = L.sv + (uint32_t)st * kScaleStep;
+    ch.s0 = bload2<kNT>(L.s, so, 0);
+    ch.s1 = bload2<kNT>(L.s, so + kScaleHalf, 0);
+    return ch;
+  }
+  __device__ __forceinline__ Prep prep(const Chunk& ch, uint4* stage, int lane) const {
+    const Lines::Chunk q = Lines::regroup(ch.c, stage, lane);
+    const uint4 p0 = q.v[0], p1 = q.v[1];
+    Prep p;
+    p.w[0] = p0.x;
+    p.w[1] = p0.y;
+    p.w[2] = p0.z;
+    p.w[3] = p0.w;
+    p.w[4] = p1.x;
+    p.w[5] = p1.y;
+    p.w[6] = p1.z;
+    p.w[7] = p1.w;
+    p.sc = __builtin_amdgcn_perm(ch.s1, ch.s0, 0x05040100u);  // (s0 bytes 0, 1 | s1 bytes 0, 1)
+    return p;
+  }
+  // the scale bytes of a chunk at or past K -> 0 (AND masks, no select on the loaded value)
+  static __device__ __forceinline__ void mask_tail(Prep& p, int st, int kq, int K) {
+    const int k0 = st * kKStep + 32 * kq;
+    p.sc &= (k0 < K ? 0x0000FFFFu : 0u) | (k0 + 128 < K ? 0xFFFF0000u : 0u);
+  }
+  // B fragment of MFMA s = 4 h + t: dword t of chunk 4 h + kq under the scale of block
+  // 2 (4 h + kq) + (t >> 1), pairs in the converter's order (w[2 j + 1], w[2 j])
+  __device__ __forceinline__ bf16x8_t frag(const Prep& p, int s) const {
+    const f32x2_t two = s < 4 ? __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(p.sc, 1.0f, false)
+                              : __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(p.sc, 1.0f, true);
+    const float sc = (s & 2) ? two[1] : two[0];
+    const f32x2_t sv = {sc, sc};
+    const uint32_t d = p.w[s];
+    const f32x2_t w0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, 1.0f, 0) * sv;
+    const f32x2_t w1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, 1.0f, 1) * sv;
+    const f32x2_t w2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, 1.0f, 2) * sv;
+    const f32x2_t w3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, 1.0f, 3) * sv;
+    return as_bf16x8(pack_bf16x2(w0[0], w0[1]), pack_bf16x2(w1[0], w1[1]),
+                     pack_bf16x2(w2[0], w2[1]), pack_bf16x2(w3[0], w3[1]));
+  }
+  static __device__ __forceinline__ int slot(int s, int kq) { return Int4WO::slot(s, kq); }
+  static __device__ __forceinline__ int xswz(int row) { return Int4WO::xswz(row); }
+  // a 16-B x piece with the bf16 of every pair exchanged: the B fragment's order
+  static __device__ __forceinline__ uint4 xperm(const uint4& v) {
+    return make_uint4(__builtin_amdgcn_alignbit(v.x, v.x, 16), __builtin_amdgcn_alignbit(v.y, v.y, 16),
+                      __builtin_amdgcn_alignbit(v.z, v.z, 16), __builtin_amdgcn_alignbit(v.w, v.w, 16));
+  }
+  // the GEMV's epilogue (nvfp4.hip): the fp32 sum times alpha; the bias add and the one bf16
+  // rounding follow in the kernel
+  static constexpr bool kColF = true, kColUniform = true;
+  __device__ __forceinline__ float col_uniform() const {
+    float alpha = w_pts != nullptr ? *w_pts : 1.0f;
+    if (a_pts != nullptr) alpha *= *a_pts;
+    return alpha;
+  }
+  __device__ __forceinline__ float epi(float acc, float, float alpha) const { return acc * alpha; }
 };
 
 struct Int8Dyn : ByteWeights<256> {

@@ -36,9 +36,14 @@
 // the hardware e4m3 converter. DYN (one token): the workgroup snaps the token into LDS first, with
 // the snap kernel's arithmetic, so DYNAMIC decode is one launch, bit-identical to the snap kernel
 // followed by the plain GEMV.
+//
+// MFMA route (M above the GEMV's boundary): the Nvfp4WO policy of gemm_mfma_kernel
+// (gemm_mfma_policy.h) on the same bytes, with the same epilogue, reached through
+// tao_tune_nvfp4_mfma until the route rule names it.
 #include "fp8_convert.h"
 #include "mx_block.h"
 #include "nvfp4_host.h"
+#include "tao_gemm.h"
 #include "tao_gemv.h"
 
 namespace tao {
@@ -410,9 +415,8 @@ extern "C" int tao_nvfp4_dequant_bf16(const uint8_t* qdata, const uint8_t* scale
 }
 
 extern "C" int tao_nvfp4_linear_route(int64_t M, int64_t N, int64_t K) {
-  (void)N;
-  (void)K;
-  return tao::nvfp4_route(M, tao::tuning().nvfp4.route, tao::tuning().nvfp4.max_m);
+  return tao::nvfp4_route(M, N, K, tao::tuning().nvfp4.route, tao::tuning().nvfp4.max_m,
+                          tao::tuning().nvfp4_mfma);
 }
 
 extern "C" int tao_nvfp4_linear_fused_snap(int64_t M, int64_t K) {
@@ -448,6 +452,11 @@ extern "C" int tao_nvfp4_linear_bf16(const uint16_t* x, const uint8_t* qdata,
   const WoTune& tu = tuning().nvfp4;
   const Nvfp4Args a{x, reinterpret_cast<const uint4*>(qdata), scales, per_tensor_scale,
                     act_per_tensor_scale, bias, y, (int)N, (int)K};
+  // the Nvfp4WO policy of gemm_mfma_kernel where the rule names it (tao_tune_nvfp4_mfma); x is
+  // already snapped in DYNAMIC mode (the rule keeps one token, the fused snap's, on the GEMV)
+  if (nvfp4_route(M, N, K, tu.route, tu.max_m, tuning().nvfp4_mfma) == kWoRouteMfma)
+    return nvfp4_mm_launch(x, qdata, scales, per_tensor_scale, act_per_tensor_scale, bias, y,
+                           (int)M, (int)N, (int)K, swizzled, st);
   if (dynamic)
     return swizzled ? nvfp4_gemv<true, true>(a, x, y, 1, st, tu)
                     : nvfp4_gemv<false, true>(a, x, y, 1, st, tu);
@@ -463,5 +472,11 @@ extern "C" int tao_tune_nvfp4(int route, int max_gemv_m, int rows_per_wave, int 
   if (int rc = check_wo_tune("nvfp4", route, max_gemv_m, rows_per_wave, waves_k, row_groups))
     return rc;
   tuning().nvfp4 = {route, max_gemv_m, rows_per_wave, waves_k, row_groups};
+  return TAO_OK;
+}
+
+extern "C" int tao_tune_nvfp4_mfma(int on) {
+  TAO_CHECK_ARG(on == 0 || on == 1, "tune: nvfp4 mfma must be 0 (built-in route) or 1");
+  tao::tuning().nvfp4_mfma = on;
   return TAO_OK;
 }

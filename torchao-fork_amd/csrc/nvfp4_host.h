@@ -54,9 +54,17 @@ static inline bool nvfp4_shape_ok(int64_t N, int64_t K) {
 // at M = 8, the 8-token instance, it wins at two and loses at two (22.3 vs 35.9, 33.0 vs 36.4,
 // 74.4 vs 67.6, 95.2 vs 62.8); at M = 16, two launches, it loses at all four. N and K do not
 // enter: the rule is M <= 4, the last count at which the GEMV wins everywhere.
+// A third route, the Nvfp4WO policy of gemm_mfma_kernel (gemm_mfma.hip), is behind a hook of its
+// own (mfma: tao_tune_nvfp4_mfma): with it on, every call this rule would send to dequantize +
+// matmul goes to the MFMA GEMM instead, in both modes and both scale layouts. A forced route still
+// wins, and max_gemv_m still moves the GEMV boundary. The built-in rule does not name it yet
+// (measurements: DESIGN §4.25.1).
 constexpr int kNvfp4GemvDefaultM = 4;
-static inline int nvfp4_route(int64_t M, int force, int max_gemv_m) {
-  return wo_route(M, force, max_gemv_m, kNvfp4GemvDefaultM, false);
+// The MFMA GEMM serves every shape the linear serves: its step is 256 k with 64-k tails masked.
+static inline bool nvfp4_mfma_ok(int64_t N, int64_t K) { return nvfp4_shape_ok(N, K); }
+static inline int nvfp4_route(int64_t M, int64_t N, int64_t K, int force, int max_gemv_m,
+                              int mfma) {
+  return wo_route(M, force, max_gemv_m, kNvfp4GemvDefaultM, mfma != 0 && nvfp4_mfma_ok(N, K));
 }
 
 }  // namespace tao

@@ -110,6 +110,7 @@ struct Tuning {
   int gemv_lds = 0;  // int4 GEMV: minimum dynamic LDS per workgroup (caps residency; tao_tune_int4_lds)
   WoTune nf4, fp6, uintx;                        // tao_tune_nf4 / tao_tune_fp6 / tao_tune_uintx
   WoTune nvfp4;                                  // tao_tune_nvfp4
+  int nvfp4_mfma = 0;                            // NVFP4 linear: 1 = MFMA GEMM where the rule says dequant + mm
   int fp6_groups = 0;                            // FP6 GEMV 32-code groups per lane chunk
   int fp6_mfma = 0;                              // FP6 linear: 1 = MFMA GEMM where the rule says dequant + mm
   int uintx_xlds = 0;                            // uintx GEMV x: 0 built-in, 1 through L1, 2 staged in LDS

@@ -51,7 +51,7 @@ int launch_gemm32_int4(const uint16_t* x, const uint32_t* packed, const uint16_t
                        hipStream_t stream, int tbm = 0, int tsplits = 0);
 
 // gemm_mfma.hip: the skinny-M crossovers and the MFMA launches of the scaled-mm entries
-// (fp8_dyn.hip, mx_fp8.hip, mx_fp4.hip, block_fp8.hip, int8_dyn.hip, w4a8.hip, fp6.hip)
+// (fp8_dyn.hip, mx_fp8.hip, mx_fp4.hip, block_fp8.hip, int8_dyn.hip, w4a8.hip, fp6.hip, nvfp4.hip)
 bool int4_linear_takes_gemv(int64_t M, int64_t N, int64_t K);
 bool fp8dyn_takes_gemv(int64_t M, int64_t N, int64_t K);
 bool mx_takes_gemv(int64_t M, int64_t N, int64_t K);
@@ -75,6 +75,10 @@ int int8_scaled_mm_launch(const int8_t* xq, const uint16_t* xs, const int8_t* wq
 int fp6_mm_launch(const uint16_t* x, const uint32_t* codes, const uint16_t* scale,
                   const uint16_t* bias, uint16_t* y, int M, int N, int K, int fmt,
                   hipStream_t stream);
+// w_pts / a_pts: the per-tensor scales in device memory, or null (gemm_mfma.hip TAO_GEMM_NVFP4_TU)
+int nvfp4_mm_launch(const uint16_t* x, const uint8_t* qdata, const uint8_t* scales,
+                    const float* w_pts, const float* a_pts, const uint16_t* bias, uint16_t* y,
+                    int M, int N, int K, int swizzled, hipStream_t stream);
 // one specialisation per width 1..7, each in an object of its own (gemm_mfma.hip TAO_GEMM_UINTX_TU)
 template <int BITS>
 int uintx_mm_launch(const uint16_t* x, const uint8_t* s4, const uint8_t* s2, const uint8_t* s1,

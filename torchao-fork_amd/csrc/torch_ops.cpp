@@ -1492,7 +1492,9 @@ Tensor nvfp4_dequantize(const Tensor& qdata, const Tensor& scales,
 
 // Up to the route's boundary the GEMV (DYNAMIC: the snap inside the launch at one token, the snap
 // kernel first beyond); above it the snap, the dequantizer into a temporary and the bf16 matmul,
-// the per-tensor scales and the bias meeting the product in fp32.
+// the per-tensor scales and the bias meeting the product in fp32. Under tao_tune_nvfp4_mfma the
+// route above the boundary is 3 instead: the snap, then the MFMA GEMM on the stored bytes inside
+// tao_nvfp4_linear_bf16, which every route other than 2 calls (`gemv` below).
 Tensor nvfp4_linear(const Tensor& x, const Tensor& qdata, const Tensor& scales,
                     const std::optional<Tensor>& pts, const std::optional<Tensor>& bias,
                     bool swizzled, bool dynamic, const std::optional<Tensor>& act_pts) {

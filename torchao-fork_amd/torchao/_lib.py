@@ -129,6 +129,7 @@ _SIGNATURES = {
     "tao_nvfp4_linear_route": [_i64, _i64, _i64],
     "tao_nvfp4_linear_fused_snap": [_i64, _i64],
     "tao_tune_nvfp4": [_int, _int, _int, _int, _int],
+    "tao_tune_nvfp4_mfma": [_int],
     "tao_moe_route": [_p, _i64, _i64, _i64, _p, _p, _p, _p],
     "tao_int4wo_grouped_linear_bf16": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _p,
                                        _i64, _i64, _i64, _p],

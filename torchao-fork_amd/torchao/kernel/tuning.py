@@ -59,6 +59,8 @@ _KNOBS = {
     "uintx_mfma": ("tao_tune_uintx_mfma", 1),
     # (route, max_gemv_m, rows per wave, waves along K, row groups as for nf4)
     "nvfp4": ("tao_tune_nvfp4", 5),
+    # 1: the MFMA GEMM wherever the nvfp4 route rule says dequantize + matmul
+    "nvfp4_mfma": ("tao_tune_nvfp4_mfma", 1),
     # 2:4 sparse int8 linear: (route 0 auto / 1 gemv / 2 sparse MFMA gemm, max_gemv_m, rows per
     # wave, waves along K, row groups)
     "sp24": ("tao_tune_sp24", 5),
